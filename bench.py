@@ -2,6 +2,7 @@
 """bench.py -- headline benchmark of the CSR x CSR hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4] [--gather] [--exact]
+                    [--dump-outputs DIR] [--full]
 
 Default workload (BASELINE.json configs[1], `--config c1`): A (50 000 x 50 000) times B (50 000 x
 50 000), both uniform random CSR of density 0.01 with uniform[0,1) float64 values -- the
@@ -22,13 +23,24 @@ every GPU (SURVEY 8e option ii: 200 000^2, d = 0.001, rows split over the ranks:
 `python bench.py --gpus N` without a launcher starts its N ranks itself (torch.distributed.run
 as a child process, before this process touches the GPU).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype and ms_per_step (the wall time
+of one timed step), plus
   roofline     -- algorithmic bytes of one product / duration of the numeric phase's kernels,
-                  measured with HIP events on the launch stream
+                  measured with HIP events on the launch stream during the timed steps
+A plain run does nothing else.  `--full` adds what takes time of its own:
   cpu_baseline -- the reference's own row kernel (src/sparsework.cpp compiled by oracle/Makefile into
                   oracle/_ref/, kind "reference") -- or, where that build is absent, the CPU oracle (a port of
                   the reference's algorithm, kind "port") -- timed on a bounded row sample of the same
-                  operands on this box's host cores
+                  operands on the host's cores, and the last step's result checked against it on that sample
+                  (single GPU, CSR configs[1]; `--no-cpu` skips it)
+  extra_configs -- the default invocation also times the other BASELINE configs, three steps each
+                  (`--no-extra` skips them)
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step returned (rank 0's arrays) as
+DIR/<name>.npy in float64: CSR configs indptr / indices / data, dense configs `dense` / `triple`.  An
+array of more than DUMP_MAX_ELEMS elements is written as a fixed seeded sample, with the sampled flat
+positions in DIR/<name>_positions.npy (at most 48 MB in all).  The inputs come from fixed seeds, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -45,6 +57,22 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8.0 TB/s spec
 NUMERIC_KERNELS = ("smm_numeric", "smm_dense_slab", "smm_emit")      # kernels of the numeric phase (whichever ran)
+DUMP_MAX_ELEMS = 1 << 20  # --dump-outputs: per array, values + positions of a sample are 16 MB in float64
+
+
+def dump_outputs(torch, arrays, out_dir, seed=0):
+    """Write each (name, tensor) of the last timed step to out_dir/<name>.npy as float64 (int32 / int64
+    indices are exact in it).  A tensor of more than DUMP_MAX_ELEMS elements is sampled at sorted, unique
+    flat positions drawn from default_rng(seed) -- the same positions for every run of the same shape --
+    which go to out_dir/<name>_positions.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays:
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            pos = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), size=DUMP_MAX_ELEMS))
+            np.save(os.path.join(out_dir, f"{name}_positions.npy"), pos.astype(np.float64))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), flat.to(torch.float64).cpu().numpy())
 
 
 def cpu_baseline(torch, a, b, cols, gpu_result=None, target_s=12.0):
@@ -136,10 +164,11 @@ def device_identity(torch, local):
         return str(getattr(props, "uuid", f"device{local}"))
 
 
-def run_config(cfg, args, env, steps, warmup, cpu_leg):
+def run_config(cfg, args, env, steps, warmup, cpu_leg, dump_dir=None):
     """Time `steps` passes of one BASELINE config (inputs generated on the device first, resident in HBM
-    before the timed region) and return the fields of its JSON line (rank 0; None elsewhere).  Every
-    buffer of the config is released before returning."""
+    before the timed region) and return the fields of its JSON line (rank 0; None elsewhere).  With
+    `dump_dir`, rank 0 writes the last step's outputs there (dump_outputs).  Every buffer of the config is
+    released before returning."""
     torch, ctx, dist, smm_dist = env["torch"], env["ctx"], env["dist"], env["smm_dist"]
     rank, world, device, rehearsal, tstream = env["rank"], env["world"], env["device"], env["rehearsal"], env["tstream"]
     from sparse_matrix_mult_amd.synthetic import gen_csr_device, gen_symmetric_csr_device
@@ -221,6 +250,7 @@ def run_config(cfg, args, env, steps, warmup, cpu_leg):
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     units = 0
     keep_last = cpu_leg and world == 1 and cfg == "c1"       # rank 0 keeps the last result for the parity check
+    keep_out = keep_last or bool(dump_dir)
     fence()
     t0 = time.perf_counter()
     marks[0].record(tstream)
@@ -228,7 +258,7 @@ def run_config(cfg, args, env, steps, warmup, cpu_leg):
         out = step()
         units = out[3] if len(out) == 4 else out[0].numel()
         marks[it + 1].record(tstream)
-        if it + 1 < steps or not keep_last:
+        if it + 1 < steps or not keep_out:
             del out
     fence()
     elapsed = time.perf_counter() - t0
@@ -237,6 +267,11 @@ def run_config(cfg, args, env, steps, warmup, cpu_leg):
                                                                  "smm_runs", "smm_triple_stage2")}
     ctx.timing(False)
     gather_ms = sum(a.elapsed_time(b) for a, b in gather_ev) / max(len(gather_ev), 1) if gather_ev else None
+    if dump_dir and rank == 0:
+        names = ("indptr", "indices", "data") if len(out) == 4 else ("triple" if cfg == "c3" else "dense",)
+        dump_outputs(torch, list(zip(names, out)), dump_dir)
+    if keep_out and not keep_last:
+        del out
 
     # --verify (N > 1, CSR configs): one more, untimed step; rank 0 then multiplies the row-wise concatenation of every
     # rank's block of A with B on its own GPU and compares -- the exchanged global row pointer always, and with --gather
@@ -397,10 +432,18 @@ def main():
     ap.add_argument("--verify", action="store_true",
                     help="N > 1, CSR configs: after the timed region rank 0 recomputes the product of the concatenated row blocks on "
                          "one GPU and compares it with what the ranks exchanged / gathered (small sizes: rehearsals, first contact)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baseline (cpu_baseline) and, on the default run, the other BASELINE configs "
+                         "(extra_configs); a plain run times only the headline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--no-extra", action="store_true",
-                    help="default run only: skip the short runs of the other BASELINE configs (extra_configs)")
+                    help="--full, default run only: skip the short runs of the other BASELINE configs (extra_configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step returned to DIR/<name>.npy (float64; large "
+                         "arrays as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -449,13 +492,14 @@ def main():
         dist.all_gather_object(ids, device_identity(torch, local))
         rccl = {"backend": dist.get_backend(), "world": world, "devices": ids, "distinct_devices": len(set(ids))}
 
-    line = run_config(args.config, args, env, args.steps, args.warmup, cpu_leg=not args.no_cpu)
+    line = run_config(args.config, args, env, args.steps, args.warmup, cpu_leg=args.full and not args.no_cpu,
+                      dump_dir=args.dump_outputs or None)
     if rank == 0 and rccl is not None:
         line["rccl"] = rccl
 
-    # The default invocation (the driver's `python bench.py --gpus 1`) also times the other BASELINE configs, three
-    # steps each, in this same process: parity-test cases, reported next to the headline, never part of `value`.
-    default_run = (world == 1 and args.config == "c1" and not args.no_extra and not args.exact and not args.gather and
+    # With --full the default invocation also times the other BASELINE configs, three steps each, in this same
+    # process: parity-test cases, reported next to the headline, never part of `value`.
+    default_run = (args.full and world == 1 and args.config == "c1" and not args.no_extra and not args.exact and not args.gather and
                    not (args.rows or args.cols or args.density or args.lds_cols or args.waves or args.hash or args.slab))
     if default_run:
         extra = {}

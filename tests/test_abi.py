@@ -12,6 +12,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "smm_hip.h")
 
 
+def _raw_lib(path):
+    """A handle of its own (prototypes set here stay here), on the HIP runtime the package shares with torch: loading
+    the library before torch with the system ROCm runtime would leave torch's runtime of this process without a device
+    (sparse_matrix_mult_amd/_lib.py, _share_hip_runtime_with_torch) for every later test on a GPU machine."""
+    from sparse_matrix_mult_amd._lib import _share_hip_runtime_with_torch
+    _share_hip_runtime_with_torch()
+    return ctypes.CDLL(path)
+
+
 def _declared_functions():
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -23,7 +32,7 @@ def _declared_functions():
 def test_library_exports_every_declared_symbol():
     from sparse_matrix_mult_amd._lib import LEGACY_SYMBOLS, LIB_PATH, V2_PROTOTYPES
     assert os.path.exists(LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = _raw_lib(LIB_PATH)
     declared = _declared_functions()
     assert len(declared) >= 40
     for name in declared:
@@ -44,7 +53,7 @@ def test_legacy_struct_layout_is_the_reference_wrappers():
 
     assert ctypes.sizeof(SparseMat) == 40 and ctypes.sizeof(DArray) == 16
     from sparse_matrix_mult_amd._lib import LIB_PATH
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = _raw_lib(LIB_PATH)
     lib.create_sparsemat.restype = ctypes.POINTER(SparseMat)
     lib.create_sparsemat.argtypes = [ctypes.c_int] * 3
     m = lib.create_sparsemat(3, 4, 5).contents
@@ -65,7 +74,7 @@ def test_legacy_limits_matches_oracle(oracle):
     class IArray(ctypes.Structure):
         _fields_ = [("array", ctypes.POINTER(ctypes.c_int)), ("rows", ctypes.c_int), ("cols", ctypes.c_int)]
     from sparse_matrix_mult_amd._lib import LIB_PATH
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = _raw_lib(LIB_PATH)
     lib.limits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(IArray)]
     lib.destroy_iarray.argtypes = [ctypes.POINTER(IArray)]
     for rows, procs in ((10, 3), (3, 8), (100, 7), (1, 1), (50000, 8), (17, 17)):
@@ -106,7 +115,7 @@ def test_modifyalloc_resizes_and_frees_like_the_reference():
                     ("rowPtr", ctypes.POINTER(ctypes.c_int)), ("colInd", ctypes.POINTER(ctypes.c_int)),
                     ("values", ctypes.POINTER(ctypes.c_double))]
     from sparse_matrix_mult_amd._lib import LIB_PATH
-    lib = ctypes.CDLL(LIB_PATH)
+    lib = _raw_lib(LIB_PATH)
     lib.create_sparsemat.restype = ctypes.POINTER(SparseMat)
     lib.create_sparsemat.argtypes = [ctypes.c_int] * 3
     lib.modifyalloc.argtypes = [ctypes.POINTER(SparseMat), ctypes.c_int]
