@@ -171,6 +171,12 @@ int64_t smm_csr_nnz(const smm_csr *m);
  * by smm_csr_from_device): only the cached copies are refreshed. */
 int  smm_csr_update_values(smm_ctx *ctx, smm_csr *m, const double *data);
 int  smm_csr_update_values_device(smm_ctx *ctx, smm_csr *m, const double *d_data);
+/* A^T as a new operand owned by the caller (smm_csr_destroy), built on the device: its arrays are exactly those of
+ * scipy's a.tocsc() -- row j of A^T holds A's entries of column j in ascending source-row order, entries of one source
+ * row in their stored order; repeated columns stay repeated, values are copied bit for bit.  Any column length. */
+int  smm_csr_transpose(smm_ctx *ctx, const smm_csr *a, smm_csr **out);
+/* Host copy of an operand's own arrays: indptr (rows+1 int32), indices (nnz int32), data (nnz float64). */
+int  smm_csr_download(smm_ctx *ctx, const smm_csr *m, int32_t *indptr, int32_t *indices, double *data);
 /* HBM held by the handle: its arrays (when owned) plus every cached copy. */
 int64_t smm_csr_device_bytes(const smm_csr *m);
 /* 64-bit content hash of a HOST buffer (no GPU involved): a chain of bijective mixing steps, so changing any
@@ -255,6 +261,38 @@ int  smm_triple_product(smm_ctx *ctx, smm_csr *h, smm_csr *q, int flags,
                         int64_t row_begin, int64_t row_end, double *d_c);
 int  smm_triple_product_host(smm_ctx *ctx, smm_csr *h, smm_csr *q, int flags,
                              int64_t row_begin, int64_t row_end, double *c);
+
+/* ------------------------------------------------------------------ H * Q * H^T, sparse output
+ * The triple product as a CSR held in HBM by the library (not in the reference, whose triple product is dense only:
+ * an n x n array caps n near 1e5 on one device).  Rows [row_begin,row_end) of S = H * Q * H^T; each row holds the
+ * columns k >= i only, in strictly ascending order (canonical CSR).
+ *   Pattern (structural, never value-based): (i,k) is stored iff some j is stored both in row i of T = H * Q (the
+ *   SpGEMM pattern of smm_spgemm_symbolic) and in row k of H.  Entries that cancel to 0.0 are stored.
+ *   Values with SMM_EXACT: bit-identical to what smm_triple_product (dense, without SMM_FULL_MATRIX) writes at (i,k) --
+ *   the reference's loop sum = 0.0; sum += T[i, H.col[jp]] * H.val[jp] over row k of H in stored order
+ *   (sparse_sparse_dense.cpp:201-211), T's unstored entries read as +0.0 -- for any legal H (unsorted rows, repeated
+ *   columns).  Without it: within 1e-10 relative of those numbers (fused multiply-adds).
+ *   SMM_FULL_MATRIX (whole range [0,n) only): the full symmetric matrix, the upper triangle mirrored by
+ *   smm_csr_mirror_symbolic / _fill -- deliberately NOT the reference's compute_full_matrix=1 (S[i,k] + S[k,i] off the
+ *   diagonal), which smm_triple_product keeps reproducing.  Rows stay ascending.  SMM_MIRROR is refused.
+ * Nothing of size n x n or n x K is allocated: H is taken in row blocks whose T fits smm_ctx_tune_triple_sparse's
+ * budget, so nnz(H * Q) beyond 2^31 in total is fine.  Peak HBM: the operands, H^T (cached on H's handle, built by
+ * smm_csr_transpose; it depends on the pattern only, so smm_csr_update_values does not invalidate it), one block's
+ * T and its stage-2 scratch, and the result. */
+typedef struct smm_result smm_result;   /* a CSR result held in HBM by the library; belongs to the context */
+int  smm_triple_product_sparse(smm_ctx *ctx, smm_csr *h, smm_csr *q, int flags, int64_t row_begin, int64_t row_end,
+                               smm_result **out);
+int64_t smm_result_nnz(const smm_result *r);
+int64_t smm_result_rows(const smm_result *r);           /* row_end - row_begin of the call that made it */
+/* Host copy: indptr (rows+1 int64), indices (int32 with index_bytes 4, int64 with 8 -- what a scipy CSR with
+ * nnz >= 2^31 needs), data (nnz float64). */
+int  smm_result_download(smm_ctx *ctx, smm_result *r, int64_t *indptr, void *indices, int index_bytes, double *data);
+/* Device copy into caller-owned HBM buffers of the same sizes (int32 indices). */
+int  smm_result_copy_device(smm_ctx *ctx, smm_result *r, int64_t *d_indptr, int32_t *d_indices, double *d_data);
+void smm_result_destroy(smm_result *r);
+/* Row-block budget of smm_triple_product_sparse: entries of T = H[b] * Q per block, counted as products (an upper
+ * bound of them); 0 = the default, 2^27.  A block holds at least one row.  Results do not depend on it, bit for bit. */
+int  smm_ctx_tune_triple_sparse(smm_ctx *ctx, int64_t max_t_nnz);
 
 /* ------------------------------------------------------------------ device memory helpers
  * (so that hosts without torch can still hold results in HBM) */

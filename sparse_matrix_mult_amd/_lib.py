@@ -81,6 +81,15 @@ V2_PROTOTYPES = {
     "smm_spgemm_dense_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _vp]),
     "smm_triple_product": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _c_i64, _vp]),
     "smm_triple_product_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _c_i64, _vp]),
+    "smm_csr_transpose": (ctypes.c_int, [_vp, _vp, _pp]),
+    "smm_csr_download": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "smm_triple_product_sparse": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _c_i64, _pp]),
+    "smm_result_nnz": (_c_i64, [_vp]),
+    "smm_result_rows": (_c_i64, [_vp]),
+    "smm_result_download": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "smm_result_copy_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "smm_result_destroy": (None, [_vp]),
+    "smm_ctx_tune_triple_sparse": (ctypes.c_int, [_vp, _c_i64]),
     "smm_device_malloc": (ctypes.c_int, [_vp, _c_i64, _pp]),
     "smm_device_free": (ctypes.c_int, [_vp, _vp]),
     "smm_memcpy_d2h": (ctypes.c_int, [_vp, _vp, _vp, _c_i64]),

@@ -5,6 +5,7 @@
 #include "smm_kernels.hpp"
 #include "smm_slab.hpp"
 #include "smm_ring.hpp"
+#include "smm_triple_sparse.hpp"
 #include "../../include/smm_hip.h"
 
 #include <sys/mman.h>
@@ -90,6 +91,7 @@ struct smm_ctx {
     // rows per wave 2 or 4 (8 waves per workgroup: 16 or 32 rows per block)
     int slab_mode = 0, slab_ws = 0, slab_rw = 4;
     int narrow_idx = 1;      // 1: operands with < 65535 columns go through the symbolic phase as uint16 (column stream and lists)
+    int64_t t3_max_t = (int64_t)1 << 27;   // sparse triple product: products of H[b] * Q (an upper bound of nnz(T_b)) per row block
     int n_cu = 256;
     std::vector<PoolBlock> pool;          // free blocks
     std::map<void *, size_t> live;        // blocks handed out
@@ -736,6 +738,7 @@ struct smm_csr {
     int64_t *ring_off = nullptr; short *ring_col = nullptr; double *ring_val = nullptr; unsigned *ring_hdr = nullptr;
     int ring_npieces = 0; bool ring_spread = false; int64_t ring_bytes = 0;
     int64_t derived_bytes = 0;                   // HBM of every other cached copy (tile indices, payloads, ...)
+    smm_csr *tr = nullptr;                       // H^T for the sparse triple product (pattern only: update_values leaves it)
 };
 
 static int validate(smm_ctx *c, smm_csr *m)
@@ -828,6 +831,7 @@ extern "C" void smm_csr_destroy(smm_csr *m)
     (void)hipFree(m->idx16); (void)hipFree(m->idx_pad);
     (void)hipFree(m->ell_off); (void)hipFree(m->ell_col); (void)hipFree(m->ell_val);
     (void)hipFree(m->ring_off); (void)hipFree(m->ring_col); (void)hipFree(m->ring_val); (void)hipFree(m->ring_hdr);
+    smm_csr_destroy(m->tr);
     delete m;
 }
 extern "C" int64_t smm_csr_rows(const smm_csr *m) { return m ? m->rows : -1; }
@@ -847,7 +851,7 @@ extern "C" int64_t smm_csr_device_bytes(const smm_csr *m)
     CTX_LOCK(m->ctx);
     int64_t own = 0;
     if (m->owned) own = (m->rows + 1) * (int64_t)sizeof(int) + (std::max<int64_t>(m->nnz, 1) + 2) * (int64_t)sizeof(int) + std::max<int64_t>(m->nnz, 1) * (int64_t)sizeof(double);
-    return own + m->derived_bytes + m->ell_bytes + m->ring_bytes;
+    return own + m->derived_bytes + m->ell_bytes + m->ring_bytes + (m->tr ? smm_csr_device_bytes(m->tr) : 0);
 }
 
 // Tile geometry: nct coarse tiles of wc = nw*wf columns; fine tile t covers [t*wf,(t+1)*wf).
@@ -2572,6 +2576,326 @@ extern "C" int smm_triple_product_host(smm_ctx *c, smm_csr *h, smm_csr *q, int f
     (void)hipStreamSynchronize(c->stream);
     pool_free(c, d);
     return rc;
+}
+
+// ------------------------------------------------------------------------------ device CSR transpose
+// Segmented sort of distinct int keys in place (segments off[s] .. off[s+1], int64 offsets in HBM).
+static int seg_sort(smm_ctx *c, int64_t nseg, const int64_t *off, int *key)
+{
+    if (nseg <= 0) return SMM_OK;
+    LAUNCH(c, "smm_seg_sort", smm_seg_sort_short, std::min<int64_t>((nseg + 255) / 256, 16384), 256, 0, nseg, off, key);
+    LAUNCH(c, "smm_seg_sort", smm_seg_sort<false>, std::min<int64_t>(nseg, (int64_t)c->n_cu * 4), 1024, 0, nseg, off, key);
+    LAUNCH(c, "smm_seg_sort", smm_seg_sort<true>, std::min<int64_t>(nseg, (int64_t)c->n_cu), 1024, 0, nseg, off, key);
+    LAUNCH_CHECK();
+    return SMM_OK;
+}
+
+// A^T as a new owned operand; arrays exactly those of scipy's a.tocsc().
+static int transpose_impl(smm_ctx *c, const smm_csr *a, smm_csr **out)
+{
+    *out = nullptr;
+    const int64_t rows = a->cols, cols = a->rows, nnz = a->nnz;
+    int *dp = nullptr, *di = nullptr; double *dv = nullptr;
+    if (dev_malloc(c, (void **)&dp, (rows + 1) * sizeof(int)) != hipSuccess ||
+        dev_malloc(c, (void **)&di, (std::max<int64_t>(nnz, 1) + 2) * sizeof(int)) != hipSuccess ||     // (slack as smm_csr_from_host)
+        dev_malloc(c, (void **)&dv, std::max<int64_t>(nnz, 1) * sizeof(double)) != hipSuccess) {
+        (void)hipFree(dp); (void)hipFree(di); (void)hipFree(dv);
+        return fail(SMM_ERR_ALLOC, "hipMalloc of the transposed operand failed");
+    }
+    smm_csr *m = new smm_csr();
+    m->ctx = c; m->rows = rows; m->cols = cols; m->nnz = nnz;
+    m->ptr = dp; m->idx = di; m->val = dv; m->owned = true;
+    int *cnt = nullptr, *key = nullptr; int64_t *off = nullptr;
+    auto drop = [&]() { pool_free(c, cnt); pool_free(c, key); pool_free(c, off); };
+    int rc = pool_get(c, (size_t)rows + 1, &cnt);
+    if (rc == SMM_OK) rc = pool_get(c, (size_t)rows + 1, &off);
+    if (rc == SMM_OK) rc = pool_get(c, (size_t)std::max<int64_t>(nnz, 1), &key);
+    hipError_t e = rc == SMM_OK ? hipMemsetAsync(cnt, 0, ((size_t)rows + 1) * sizeof(int), c->stream) : hipSuccess;
+    const int grid = (int)std::min<int64_t>(std::max<int64_t>((nnz + 255) / 256, 1), (int64_t)c->n_cu * 16);
+    if (rc == SMM_OK && e == hipSuccess) {
+        LAUNCH(c, "smm_transpose_count", smm_transpose_count, grid, 256, 0, nnz, a->idx, (int)rows, cnt);
+        rc = scan_launch<int>(c, rows, cnt, off);
+    }
+    if (rc == SMM_OK && e == hipSuccess) {
+        e = hipMemsetAsync(cnt, 0, ((size_t)rows + 1) * sizeof(int), c->stream);       // (cursor of the scatter)
+        LAUNCH(c, "smm_transpose_scatter", smm_transpose_scatter, grid, 256, 0, nnz, a->idx, (int)rows, (const int64_t *)off, cnt, key);
+        rc = seg_sort(c, rows, off, key);
+    }
+    if (rc == SMM_OK && e == hipSuccess) {
+        const int ggrid = (int)std::min<int64_t>(std::max<int64_t>(std::max(nnz, rows + 1) / 256 + 1, 1), (int64_t)c->n_cu * 16);
+        LAUNCH(c, "smm_transpose_gather", smm_transpose_gather, ggrid, 256, 0, nnz, (int)a->rows, a->ptr, a->val, (const int *)key, (int)rows,
+               (const int64_t *)off, dp, di, dv);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    drop();
+    if (rc == SMM_OK && e != hipSuccess) rc = fail(SMM_ERR_HIP, "smm_csr_transpose: %s", hipGetErrorString(e));
+    if (rc == SMM_OK) rc = validate(c, m);          // (flags of the new operand: sorted rows, repeated columns where A repeats rows)
+    if (rc != SMM_OK) { smm_csr_destroy(m); return rc; }
+    *out = m;
+    return SMM_OK;
+}
+
+extern "C" int smm_csr_transpose(smm_ctx *c, const smm_csr *a, smm_csr **out)
+{
+    if (!out) return fail(SMM_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!c || !a) return fail(SMM_ERR_INVALID, "NULL argument");
+    if (a->ctx != c) return fail(SMM_ERR_INVALID, "operand belongs to another context");
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(validate(c, (smm_csr *)a));
+    return transpose_impl(c, a, out);
+}
+
+extern "C" int smm_csr_download(smm_ctx *c, const smm_csr *m, int32_t *indptr, int32_t *indices, double *data)
+{
+    if (!c || !m || !indptr) return fail(SMM_ERR_INVALID, "NULL argument");
+    if (m->ctx != c) return fail(SMM_ERR_INVALID, "operand belongs to another context");
+    if (m->nnz > 0 && (!indices || !data)) return fail(SMM_ERR_INVALID, "output arrays are NULL but nnz > 0");
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(download(c, indptr, m->ptr, ((size_t)m->rows + 1) * sizeof(int)));
+    CHK(download(c, indices, m->idx, (size_t)m->nnz * sizeof(int)));
+    CHK(download(c, data, m->val, (size_t)m->nnz * sizeof(double)));
+    return SMM_OK;
+}
+
+// ------------------------------------------------------------------------------ triple product, sparse output
+// The result is held by the library as one CSR piece per row block (row blocking: nnz is known only at the end).
+struct smm_result {
+    smm_ctx *ctx = nullptr;
+    int64_t rows = 0, cols = 0, nnz = 0;
+    struct Piece { int64_t rows, nnz; int64_t *ptr; int *idx; double *val; };    // ptr: local, ptr[0] = 0
+    std::vector<Piece> pieces;
+};
+
+extern "C" void smm_result_destroy(smm_result *r)
+{
+    if (!r) return;
+    smm_ctx *c = r->ctx;
+    {
+        CTX_LOCK(c);
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        for (auto &p : r->pieces) { pool_free(c, p.ptr); pool_free(c, p.idx); pool_free(c, p.val); }
+    }
+    delete r;
+}
+extern "C" int64_t smm_result_nnz(const smm_result *r) { return r ? r->nnz : -1; }
+extern "C" int64_t smm_result_rows(const smm_result *r) { return r ? r->rows : -1; }
+
+extern "C" int smm_ctx_tune_triple_sparse(smm_ctx *c, int64_t max_t_nnz)
+{
+    if (!c || max_t_nnz < 0) return fail(SMM_ERR_INVALID, "bad argument");
+    CTX_LOCK(c);
+    c->t3_max_t = max_t_nnz > 0 ? max_t_nnz : (int64_t)1 << 27;
+    return SMM_OK;
+}
+
+// The pieces' row pointers, rebased and joined, into d_ptr (rows+1 int64); indices / values copied behind each other.
+static int result_join(smm_ctx *c, const smm_result *r, int64_t *d_ptr, int32_t *d_idx, double *d_val)
+{
+    int64_t row = 0, base = 0;
+    if (r->pieces.empty()) { HIPCHK(hipMemsetAsync(d_ptr, 0, ((size_t)r->rows + 1) * sizeof(int64_t), c->stream)); return SMM_OK; }
+    for (const auto &p : r->pieces) {
+        LAUNCH(c, "smm_triple_sparse_rebase", smm_triple_sparse_rebase, std::min<int64_t>((p.rows + 256) / 256, 4096), 256, 0, p.rows,
+               (const int64_t *)p.ptr, base, d_ptr + row);
+        LAUNCH_CHECK();
+        if (p.nnz > 0) {
+            HIPCHK(hipMemcpyAsync(d_idx + base, p.idx, (size_t)p.nnz * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d_val + base, p.val, (size_t)p.nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        }
+        row += p.rows; base += p.nnz;
+    }
+    return SMM_OK;
+}
+
+extern "C" int smm_result_copy_device(smm_ctx *c, smm_result *r, int64_t *d_indptr, int32_t *d_indices, double *d_data)
+{
+    if (!c || !r || r->ctx != c || !d_indptr) return fail(SMM_ERR_INVALID, "bad argument");
+    if (r->nnz > 0 && (!d_indices || !d_data)) return fail(SMM_ERR_INVALID, "output arrays are NULL but nnz > 0");
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(result_join(c, r, d_indptr, d_indices, d_data));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SMM_OK;
+}
+
+extern "C" int smm_result_download(smm_ctx *c, smm_result *r, int64_t *indptr, void *indices, int index_bytes, double *data)
+{
+    if (!c || !r || r->ctx != c || !indptr) return fail(SMM_ERR_INVALID, "bad argument");
+    if (index_bytes != 4 && index_bytes != 8) return fail(SMM_ERR_INVALID, "index_bytes must be 4 or 8");
+    if (r->nnz > 0 && (!indices || !data)) return fail(SMM_ERR_INVALID, "output arrays are NULL but nnz > 0");
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    indptr[0] = 0;
+    int64_t row = 0, base = 0;
+    std::vector<int64_t> tmp;
+    for (const auto &p : r->pieces) {
+        tmp.resize((size_t)p.rows + 1);
+        CHK(download(c, tmp.data(), p.ptr, ((size_t)p.rows + 1) * sizeof(int64_t)));
+        for (int64_t i = 1; i <= p.rows; ++i) indptr[row + i] = tmp[(size_t)i] + base;
+        if (p.nnz > 0) {
+            CHK(download(c, (char *)indices + (size_t)base * index_bytes, p.idx, (size_t)p.nnz * sizeof(int), index_bytes == 8));
+            CHK(download(c, data + base, p.val, (size_t)p.nnz * sizeof(double)));
+        }
+        row += p.rows; base += p.nnz;
+    }
+    for (int64_t i = row + 1; i <= r->rows; ++i) indptr[i] = base;        // (no pieces: an empty result)
+    return SMM_OK;
+}
+
+// One row block [b0, b1) of H (global rows): T_b = H[b] * Q, the pattern of its rows of S (k >= i, ascending), their values.
+static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, int flags, int64_t b0, int64_t b1, smm_result::Piece *out)
+{
+    const int64_t nb = b1 - b0, n = h->rows, K = h->cols;
+    const bool exact = (flags & SMM_EXACT) != 0;
+    smm_csr hv = *h;                       // row-range view of H (borrowed arrays, indptr not rebased: see smm_triple_product)
+    hv.ptr = h->ptr + b0; hv.rows = nb; hv.owned = false; hv.segs.clear(); hv.locs.clear(); hv.slabs.clear(); hv.packs.clear(); hv.ccs.clear();
+    hv.idx16 = nullptr; hv.idx_pad = nullptr; hv.tr = nullptr;
+    smm_plan *p1 = nullptr, *p2 = nullptr; smm_csr *tb = nullptr;
+    int64_t tnnz = 0, snnz = 0;
+    int64_t *tptr = nullptr; int *tidx = nullptr, *tptr32 = nullptr, *lists = nullptr; double *tval = nullptr, *dense = nullptr;
+    int64_t *sptr = nullptr; int *sidx = nullptr; double *sval = nullptr;
+    auto drop = [&]() {
+        smm_plan_destroy(p1); smm_plan_destroy(p2); smm_csr_destroy(tb);
+        (void)hipStreamSynchronize(c->stream);
+        pool_free(c, tptr); pool_free(c, tidx); pool_free(c, tval); pool_free(c, tptr32); pool_free(c, lists); pool_free(c, dense);
+    };
+#define BCHK(expr) do { int rc_ = (expr); if (rc_ != SMM_OK) { drop(); pool_free(c, sptr); pool_free(c, sidx); pool_free(c, sval); return rc_; } } while (0)
+    // stage 1: T_b, the engine's SpGEMM (first-touch rows, SMM_EXACT values in the reference's order)
+    BCHK(smm_spgemm_symbolic(c, &hv, q, flags & SMM_EXACT, 0, &p1, &tnnz));
+    BCHK(pool_get(c, (size_t)nb + 1, &tptr));
+    BCHK(pool_get(c, (size_t)std::max<int64_t>(tnnz, 1) + 2, &tidx));
+    BCHK(pool_get(c, (size_t)std::max<int64_t>(tnnz, 1), &tval));
+    BCHK(smm_spgemm_numeric(c, p1, tptr, tidx, tval));
+    smm_plan_destroy(p1); p1 = nullptr;
+    if (tnnz >= INT32_MAX) BCHK(fail(SMM_ERR_INVALID, "sparse triple product: one row of T has >= 2^31 entries"));
+    // stage 2, pattern: T_b (int32 row pointer, borrowed) times H^T, i <= k
+    BCHK(pool_get(c, (size_t)nb + 1, &tptr32));
+    LAUNCH(c, "smm_triple_sparse_narrow", smm_triple_sparse_narrow, std::min<int64_t>((nb + 256) / 256, 4096), 256, 0, nb, (const int64_t *)tptr, tptr32);
+    BCHK(smm_csr_from_device(c, nb, K, tnnz, tptr32, tidx, tval, &tb));
+    BCHK(smm_spgemm_symbolic(c, tb, ht, SMM_SYMMETRIC, b0, &p2, &snnz));
+    BCHK(pool_get(c, (size_t)nb + 1, &sptr));
+    BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sidx));
+    BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sval));
+    BCHK(smm_spgemm_numeric(c, p2, sptr, sidx, sval));        // (its values are T * H^T in T's order: overwritten below)
+    smm_plan_destroy(p2); p2 = nullptr;
+    BCHK(seg_sort(c, nb, sptr, sidx));
+    // stage 2, values: rows binned by the length of T_i
+    if (snnz > 0) {
+        BCHK(pool_get(c, (size_t)3 * nb + 4, &lists));
+        int *cnt = lists + 3 * nb;
+        HIPCHK(hipMemsetAsync(cnt, 0, 4 * sizeof(int), c->stream));
+        LAUNCH(c, "smm_triple_sparse_bin", smm_triple_sparse_bin, std::min<int64_t>((nb + 255) / 256, 4096), 256, 0, (int)nb,
+               (const int64_t *)tptr, (const int64_t *)sptr, lists, cnt);
+        int hc[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        Triple3Args A{};
+        A.m = (int)nb; A.row0 = b0;
+        A.t_ptr = tptr; A.t_idx = tidx; A.t_val = tval;
+        A.s_ptr = sptr; A.s_idx = sidx; A.s_val = sval;
+        A.h_ptr = h->ptr; A.h_idx = h->idx; A.h_val = h->val; A.n = (int)n; A.K = (int)K;
+        A.err = c->d_err;
+        if (hc[0] > 0) {            // one wave per row, four rows per workgroup
+            A.rowlist = lists; A.nrows = hc[0];
+            const size_t lds = (size_t)4 * 512 * (sizeof(double) + sizeof(int));
+            const int grid = (int)std::min<int64_t>((hc[0] + 3) / 4, (int64_t)c->n_cu * 16);
+            if (exact) LAUNCH(c, "smm_triple_sparse_s2", (smm_triple_sparse_s2_hash<512, 9, 64, 4, false>), grid, 256, lds, A);
+            else       LAUNCH(c, "smm_triple_sparse_s2", (smm_triple_sparse_s2_hash<512, 9, 64, 4, true>), grid, 256, lds, A);
+            LAUNCH_CHECK();
+        }
+        if (hc[1] > 0) {            // one workgroup per row
+            A.rowlist = lists + nb; A.nrows = hc[1];
+            const size_t lds = (size_t)8192 * (sizeof(double) + sizeof(int));
+            auto kern = exact ? smm_triple_sparse_s2_hash<8192, 13, 256, 1, false> : smm_triple_sparse_s2_hash<8192, 13, 256, 1, true>;
+            HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            LAUNCH(c, "smm_triple_sparse_s2", kern, std::min<int64_t>(hc[1], (int64_t)c->n_cu), 256, lds, A);
+            LAUNCH_CHECK();
+        }
+        if (hc[2] > 0) {            // a zeroed global row of K doubles per workgroup, a bounded number in flight
+            A.rowlist = lists + 2 * nb; A.nrows = hc[2];
+            const int64_t grid = std::max<int64_t>(1, std::min<int64_t>({(int64_t)hc[2], (int64_t)c->n_cu, ((int64_t)1 << 28) / (8 * K)}));
+            BCHK(pool_get(c, (size_t)grid * (size_t)K, &dense));
+            HIPCHK(hipMemsetAsync(dense, 0, (size_t)grid * (size_t)K * sizeof(double), c->stream));
+            A.dense = dense;
+            if (exact) LAUNCH(c, "smm_triple_sparse_s2", smm_triple_sparse_s2_global<false>, grid, 256, 0, A);
+            else       LAUNCH(c, "smm_triple_sparse_s2", smm_triple_sparse_s2_global<true>, grid, 256, 0, A);
+            LAUNCH_CHECK();
+        }
+    }
+#undef BCHK
+    drop();
+    out->rows = nb; out->nnz = snnz; out->ptr = sptr; out->idx = sidx; out->val = sval;
+    return SMM_OK;
+}
+
+extern "C" int smm_triple_product_sparse(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t row_begin, int64_t row_end, smm_result **out)
+{
+    if (!out) return fail(SMM_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(check_pair(c, h, q));
+    CHK(exact_guard(c, flags));
+    const int64_t n = h->rows, K = h->cols;
+    if (q->cols > K) return fail(SMM_ERR_INVALID, "Q has more columns (%lld) than H (%lld)", (long long)q->cols, (long long)K);
+    if (row_begin < 0 || row_end > n || row_begin > row_end) return fail(SMM_ERR_INVALID, "bad row range");
+    if (flags & SMM_MIRROR) return fail(SMM_ERR_INVALID, "smm_triple_product_sparse: SMM_MIRROR is not a flag of this call (SMM_FULL_MATRIX mirrors)");
+    const bool full = (flags & SMM_FULL_MATRIX) != 0;
+    if (full && (row_begin != 0 || row_end != n)) return fail(SMM_ERR_INVALID, "SMM_FULL_MATRIX needs the whole row range [0,n)");
+    const int64_t nr = row_end - row_begin;
+    smm_result *r = new smm_result();
+    r->ctx = c; r->rows = nr; r->cols = n;
+    if (nr == 0 || h->nnz == 0 || q->nnz == 0 || K == 0) { *out = r; return SMM_OK; }
+    int rc = SMM_OK;
+#define RCHK(expr) do { rc = (expr); if (rc != SMM_OK) { smm_result_destroy(r); return rc; } } while (0)
+    if (!h->tr) RCHK(transpose_impl(c, h, &h->tr));
+    // row blocks: products of H[i] * Q (an upper bound of nnz(T_i)) summed up to the budget, at least one row per block
+    std::vector<int64_t> prod((size_t)nr);
+    {
+        smm_csr hv = *h;
+        hv.ptr = h->ptr + row_begin; hv.rows = nr; hv.owned = false; hv.segs.clear(); hv.locs.clear(); hv.slabs.clear(); hv.packs.clear();
+        hv.ccs.clear(); hv.idx16 = nullptr; hv.idx_pad = nullptr; hv.tr = nullptr;
+        RCHK(smm_row_products(c, &hv, q, prod.data()));
+    }
+    int64_t b0 = row_begin;
+    while (b0 < row_end) {
+        int64_t b1 = b0, acc = 0;
+        while (b1 < row_end && (b1 == b0 || acc + prod[(size_t)(b1 - row_begin)] <= c->t3_max_t)) acc += prod[(size_t)(b1++ - row_begin)];
+        smm_result::Piece pc{0, 0, nullptr, nullptr, nullptr};
+        RCHK(triple_sparse_block(c, h, q, h->tr, flags, b0, b1, &pc));
+        r->pieces.push_back(pc);
+        r->nnz += pc.nnz;
+        b0 = b1;
+    }
+    RCHK(take_plan_error(c, "smm_triple_product_sparse"));
+    if (full) {
+        // the upper triangle joined into one CSR, mirrored on the device (rows stay ascending: mirrored part first, then k >= i)
+        smm_result::Piece up{n, r->nnz, nullptr, nullptr, nullptr}, fp{n, 0, nullptr, nullptr, nullptr};
+        auto drop2 = [&]() { (void)hipStreamSynchronize(c->stream); for (auto *pp : {&up, &fp}) { pool_free(c, pp->ptr); pool_free(c, pp->idx); pool_free(c, pp->val); } };
+#define FCHK(expr) do { rc = (expr); if (rc != SMM_OK) { drop2(); smm_result_destroy(r); return rc; } } while (0)
+        FCHK(pool_get(c, (size_t)n + 1, &up.ptr));
+        FCHK(pool_get(c, (size_t)std::max<int64_t>(up.nnz, 1), &up.idx));
+        FCHK(pool_get(c, (size_t)std::max<int64_t>(up.nnz, 1), &up.val));
+        FCHK(result_join(c, r, up.ptr, up.idx, up.val));
+        FCHK(pool_get(c, (size_t)n + 1, &fp.ptr));
+        FCHK(smm_csr_mirror_symbolic(c, n, up.ptr, up.idx, fp.ptr, &fp.nnz));
+        FCHK(pool_get(c, (size_t)std::max<int64_t>(fp.nnz, 1), &fp.idx));
+        FCHK(pool_get(c, (size_t)std::max<int64_t>(fp.nnz, 1), &fp.val));
+        FCHK(smm_csr_mirror_fill(c, n, up.ptr, up.idx, up.val, fp.ptr, fp.idx, fp.val));
+#undef FCHK
+        (void)hipStreamSynchronize(c->stream);
+        for (auto &p : r->pieces) { pool_free(c, p.ptr); pool_free(c, p.idx); pool_free(c, p.val); }
+        pool_free(c, up.ptr); pool_free(c, up.idx); pool_free(c, up.val);
+        r->pieces.assign(1, fp);
+        r->nnz = fp.nnz;
+    }
+#undef RCHK
+    *out = r;
+    return SMM_OK;
 }
 
 // ------------------------------------------------------------------------------ memory helpers

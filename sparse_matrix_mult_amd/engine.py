@@ -292,6 +292,54 @@ class Context:
         check(self.lib, self.lib.smm_triple_product(self.handle, h.handle, q.handle, _flags(False, exact, full, mirror),
                                                     int(row_begin), int(row_end), ctypes.c_void_p(d_ptr)))
 
+    # ------------------------------------------------------------------ H Q H^T, sparse output
+    def transpose(self, a):
+        """A^T built on the device (smm_csr_transpose) as a new DeviceCSR: its arrays are those of scipy's a.tocsc()."""
+        h = ctypes.c_void_p()
+        check(self.lib, self.lib.smm_csr_transpose(self.handle, a.handle, ctypes.byref(h)))
+        return DeviceCSR(self, h, a.cols, a.rows, a.nnz)
+
+    def tune_triple_sparse(self, max_t_nnz=0):
+        """Row-block budget of the sparse triple product: entries of T = H[b] * Q per block (0 = default 2^27)."""
+        check(self.lib, self.lib.smm_ctx_tune_triple_sparse(self.handle, int(max_t_nnz)))
+
+    def _triple_sparse(self, h, q, full, row_begin, row_end, exact):
+        row_end = h.rows if row_end is None else row_end
+        r = ctypes.c_void_p()
+        check(self.lib, self.lib.smm_triple_product_sparse(self.handle, h.handle, q.handle, _flags(False, exact, full),
+                                                           int(row_begin), int(row_end), ctypes.byref(r)))
+        return r, row_end - row_begin, int(self.lib.smm_result_nnz(r))
+
+    def triple_sparse_host(self, h, q, full=False, row_begin=0, row_end=None, exact=False, index_dtype=None):
+        """Rows [row_begin, row_end) of S = H Q H^T as CSR (smm_triple_product_sparse): columns k >= i in ascending
+        order (full=True: the whole symmetric matrix).  (indptr int64, indices int32 -- int64 when nnz >= 2^31 or
+        index_dtype says so --, data float64) numpy arrays."""
+        r, rows, nnz = self._triple_sparse(h, q, full, row_begin, row_end, exact)
+        try:
+            wide = nnz > np.iinfo(np.int32).max if index_dtype is None else np.dtype(index_dtype) == np.int64
+            indptr = np.empty(rows + 1, dtype=np.int64)
+            indices = np.empty(nnz, dtype=np.int64 if wide else np.int32)
+            data = np.empty(nnz, dtype=np.float64)
+            check(self.lib, self.lib.smm_result_download(self.handle, r, _ptr(indptr), _ptr(indices), 8 if wide else 4, _ptr(data)))
+            return indptr, indices, data
+        finally:
+            self.lib.smm_result_destroy(r)
+
+    def triple_sparse_torch(self, h, q, full=False, row_begin=0, row_end=None, exact=False):
+        """triple_sparse_host with the result left in HBM: (indptr int64, indices int32, data float64) torch tensors."""
+        import torch
+        r, rows, nnz = self._triple_sparse(h, q, full, row_begin, row_end, exact)
+        try:
+            dev = torch.device("cuda", self.device)
+            indptr = torch.empty(rows + 1, dtype=torch.int64, device=dev)
+            indices = torch.empty(nnz, dtype=torch.int32, device=dev)
+            data = torch.empty(nnz, dtype=torch.float64, device=dev)
+            check(self.lib, self.lib.smm_result_copy_device(self.handle, r, ctypes.c_void_p(indptr.data_ptr()),
+                                                            ctypes.c_void_p(indices.data_ptr()), ctypes.c_void_p(data.data_ptr())))
+            return indptr, indices, data
+        finally:
+            self.lib.smm_result_destroy(r)
+
 
 class DeviceCSR:
     def __init__(self, ctx, handle, rows, cols, nnz):
@@ -314,6 +362,14 @@ class DeviceCSR:
         pointer d_ptr (copied over the operand's own array): refresh the cached copies."""
         check(self.ctx.lib, self.ctx.lib.smm_csr_update_values_device(self.ctx.handle, self.handle,
                                                                       ctypes.c_void_p(d_ptr or 0)))
+
+    def to_host(self):
+        """The operand's own arrays copied back: (indptr int32, indices int32, data float64) numpy arrays."""
+        indptr = np.empty(self.rows + 1, dtype=np.int32)
+        indices = np.empty(self.nnz, dtype=np.int32)
+        data = np.empty(self.nnz, dtype=np.float64)
+        check(self.ctx.lib, self.ctx.lib.smm_csr_download(self.ctx.handle, self.handle, _ptr(indptr), _ptr(indices), _ptr(data)))
+        return indptr, indices, data
 
     def device_bytes(self):
         return int(self.ctx.lib.smm_csr_device_bytes(self.handle)) if self.handle else 0

@@ -612,3 +612,59 @@ def sparse_matrix_multiply(matrix_a, matrix_b, output_format='sparse', symmetric
     elif result.nnz == 0:
         print("Multiplication resulted in a zero matrix.")
     return result
+
+
+def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False):
+    """S = H @ Q @ H.T with a SPARSE result, computed on the GPU without any n x n or n x K array.
+
+    matrix_h : n x K, matrix_q : K x K (scipy CSR, anything csr_matrix() accepts, or a PinnedOperand).
+    Returns an n x n scipy CSR (a DeviceCSRResult under set_result_device(True)) holding the upper triangle k >= i
+    with columns in ascending order; compute_full_matrix=True returns the full symmetric matrix (the upper triangle
+    mirrored -- not the reference's doubled off-diagonal of use_triple_product with compute_full_matrix=1).  The
+    pattern is structural: (i, k) is stored iff row i of H @ Q and row k of H share a stored column.  Under
+    set_exact(True) the values are bit-identical to sparse_matrix_multiply(H, Q, use_triple_product=True) at the
+    stored positions; otherwise within 1e-10 relative.  For an S that is nearly full the dense triple product is
+    the faster tool.
+    """
+    matrix_h = _as_csr(matrix_h)
+    matrix_q = _as_csr(matrix_q)
+    if matrix_q.shape[0] != matrix_q.shape[1]:
+        raise ValueError(f"sparse_triple_product: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
+    if matrix_h.shape[1] != matrix_q.shape[0]:
+        raise ValueError("Matrix dimensions are incompatible for multiplication.")
+    n = matrix_h.shape[0]
+    out_shape = (n, n)
+    if matrix_h.nnz == 0 or matrix_q.nnz == 0:
+        if _result_device:
+            return _device_zeros(default_context(), out_shape, True)
+        return csr_matrix(out_shape)
+    ctx = default_context()
+    full = bool(compute_full_matrix)
+
+    def product():
+        cached = _cache_entries > 0
+        key_h = _operand_key(matrix_h) if cached and not isinstance(matrix_h, PinnedOperand) else None
+        key_q = _operand_key(matrix_q) if cached and not isinstance(matrix_q, PinnedOperand) else None
+        lh = _acquire(ctx, matrix_h, key_h, protect=(key_q[0],) if key_q else ())
+        try:
+            lq = _acquire(ctx, matrix_q, key_q)
+            try:
+                if _result_device:
+                    import torch
+                    torch.cuda.current_stream(torch.device("cuda", ctx.device)).synchronize()
+                    out = DeviceCSRResult(*ctx.triple_sparse_torch(lh.handle, lq.handle, full=full, exact=_exact), out_shape)
+                    ctx.synchronize()
+                    return out
+                return _result_csr(*ctx.triple_sparse_host(lh.handle, lq.handle, full=full, exact=_exact), out_shape)
+            finally:
+                lq.release()
+        finally:
+            lh.release()
+
+    try:
+        return product()
+    except SmmError as e:
+        if e.code != SMM_ERR_ALLOC or not (_cache or _plans):
+            raise
+        clear_cache()                                            # the resident operands / plans were in the way
+        return product()
