@@ -293,6 +293,31 @@ void smm_result_destroy(smm_result *r);
 /* Row-block budget of smm_triple_product_sparse: entries of T = H[b] * Q per block, counted as products (an upper
  * bound of them); 0 = the default, 2^27.  A block holds at least one row.  Results do not depend on it, bit for bit. */
 int  smm_ctx_tune_triple_sparse(smm_ctx *ctx, int64_t max_t_nnz);
+/* The sparse triple product on a given pattern: rows [row_begin,row_end) of S = H * Q * H^T at the positions of the
+ * mask L (n x n, canonical: rows strictly ascending, else SMM_ERR_INVALID -- see smm_csr_is_canonical) with k >= i.
+ * L's values are ignored; a position with no structural contribution holds +0.0.  Values as smm_triple_product_sparse
+ * (SMM_EXACT: bit-identical to smm_triple_product at (i,k)).  SMM_FULL_MATRIX (whole range only) mirrors the upper part;
+ * L's entries below the diagonal are ignored.  Stage 1 (T_b = H[b] * Q) and the row-block budget are those of
+ * smm_triple_product_sparse; the stage-2 pattern is L's rows, so H^T is neither built nor used. */
+int  smm_triple_product_sparse_masked(smm_ctx *ctx, smm_csr *h, smm_csr *q, smm_csr *mask, int flags, int64_t row_begin,
+                                      int64_t row_end, smm_result **out);
+
+/* ------------------------------------------------------------------ masked SpGEMM (A * B on a given pattern)
+ * Writes nnz(mask) values, in the mask's order, of C = A * B at the positions of mask (A.rows x B.cols, canonical, else
+ * SMM_ERR_INVALID; its values are ignored, explicitly stored zeros are positions) into caller-owned device memory.
+ * A position that no product A[i,k] * B[k,j] reaches holds +0.0.  A pair (k,j) that row i of A does not store is never
+ * multiplied (an inf in B cannot reach C through a missing A[i,k]).
+ *   SMM_EXACT (the only flag accepted): at every position that smm_spgemm_* stores, bit-identical to its SMM_EXACT value
+ *   (the reference's order), for any legal A and B.  Without it: within 1e-10 relative to (|A| |B|)[i,j].
+ * Two evaluation paths, chosen per row (smm_ctx_tune_masked): the dot path sums row j of B^T against a table of A_i
+ * (cost nnz(A_i) + sum over the mask row of nnz(B^T_j); canonical A only) and the row path walks A_i * B filtered by a
+ * table of the mask row (cost: the row's products).  B^T with values is built on the device and cached on B's handle;
+ * smm_csr_update_values[_device] on B drops it. */
+int  smm_spgemm_masked(smm_ctx *ctx, smm_csr *a, smm_csr *b, smm_csr *mask, int flags, double *d_c_data);
+int  smm_spgemm_masked_host(smm_ctx *ctx, smm_csr *a, smm_csr *b, smm_csr *mask, int flags, double *c_data);
+/* Path of the masked SpGEMM: 0 = per-row cost model (default), 1 = dot path, 2 = row path.  A that is not canonical
+ * always takes the row path.  Results do not depend on it (bit for bit under SMM_EXACT). */
+int  smm_ctx_tune_masked(smm_ctx *ctx, int mode);
 
 /* ------------------------------------------------------------------ device memory helpers
  * (so that hosts without torch can still hold results in HBM) */

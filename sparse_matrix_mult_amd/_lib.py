@@ -90,6 +90,10 @@ V2_PROTOTYPES = {
     "smm_result_copy_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "smm_result_destroy": (None, [_vp]),
     "smm_ctx_tune_triple_sparse": (ctypes.c_int, [_vp, _c_i64]),
+    "smm_triple_product_sparse_masked": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _c_i64, _pp]),
+    "smm_spgemm_masked": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "smm_spgemm_masked_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "smm_ctx_tune_masked": (ctypes.c_int, [_vp, ctypes.c_int]),
     "smm_device_malloc": (ctypes.c_int, [_vp, _c_i64, _pp]),
     "smm_device_free": (ctypes.c_int, [_vp, _vp]),
     "smm_memcpy_d2h": (ctypes.c_int, [_vp, _vp, _vp, _c_i64]),

@@ -6,6 +6,7 @@
 #include "smm_slab.hpp"
 #include "smm_ring.hpp"
 #include "smm_triple_sparse.hpp"
+#include "smm_masked.hpp"
 #include "../../include/smm_hip.h"
 
 #include <sys/mman.h>
@@ -92,6 +93,7 @@ struct smm_ctx {
     int slab_mode = 0, slab_ws = 0, slab_rw = 4;
     int narrow_idx = 1;      // 1: operands with < 65535 columns go through the symbolic phase as uint16 (column stream and lists)
     int64_t t3_max_t = (int64_t)1 << 27;   // sparse triple product: products of H[b] * Q (an upper bound of nnz(T_b)) per row block
+    int masked_mode = 0;                   // masked SpGEMM: 0 per-row cost model, 1 dot path (canonical A only), 2 row path
     int n_cu = 256;
     std::vector<PoolBlock> pool;          // free blocks
     std::map<void *, size_t> live;        // blocks handed out
@@ -739,6 +741,7 @@ struct smm_csr {
     int ring_npieces = 0; bool ring_spread = false; int64_t ring_bytes = 0;
     int64_t derived_bytes = 0;                   // HBM of every other cached copy (tile indices, payloads, ...)
     smm_csr *tr = nullptr;                       // H^T for the sparse triple product (pattern only: update_values leaves it)
+    smm_csr *trv = nullptr;                      // B^T with values for the masked SpGEMM's dot path (update_values drops it)
 };
 
 static int validate(smm_ctx *c, smm_csr *m)
@@ -832,6 +835,7 @@ extern "C" void smm_csr_destroy(smm_csr *m)
     (void)hipFree(m->ell_off); (void)hipFree(m->ell_col); (void)hipFree(m->ell_val);
     (void)hipFree(m->ring_off); (void)hipFree(m->ring_col); (void)hipFree(m->ring_val); (void)hipFree(m->ring_hdr);
     smm_csr_destroy(m->tr);
+    smm_csr_destroy(m->trv);
     delete m;
 }
 extern "C" int64_t smm_csr_rows(const smm_csr *m) { return m ? m->rows : -1; }
@@ -851,7 +855,8 @@ extern "C" int64_t smm_csr_device_bytes(const smm_csr *m)
     CTX_LOCK(m->ctx);
     int64_t own = 0;
     if (m->owned) own = (m->rows + 1) * (int64_t)sizeof(int) + (std::max<int64_t>(m->nnz, 1) + 2) * (int64_t)sizeof(int) + std::max<int64_t>(m->nnz, 1) * (int64_t)sizeof(double);
-    return own + m->derived_bytes + m->ell_bytes + m->ring_bytes + (m->tr ? smm_csr_device_bytes(m->tr) : 0);
+    return own + m->derived_bytes + m->ell_bytes + m->ring_bytes + (m->tr ? smm_csr_device_bytes(m->tr) : 0) +
+           (m->trv ? smm_csr_device_bytes(m->trv) : 0);
 }
 
 // Tile geometry: nct coarse tiles of wc = nw*wf columns; fine tile t covers [t*wf,(t+1)*wf).
@@ -1443,6 +1448,7 @@ static int ensure_slab(smm_ctx *c, smm_csr *b, const SlabGeom &g, smm_csr::SlabC
 // whatever product is still running there.
 static int refresh_value_copies(smm_ctx *c, smm_csr *m)
 {
+    if (m->trv) { smm_csr_destroy(m->trv); m->trv = nullptr; }     // (rebuilt by the next masked product that needs it)
     for (auto &e : m->packs) {
         Geom gs; gs.nw = 1; gs.nct = e.nct; gs.wc = e.wc; gs.wf = e.wc; gs.n_ft = e.nct;
         const int *seg = nullptr;
@@ -2747,7 +2753,10 @@ extern "C" int smm_result_download(smm_ctx *c, smm_result *r, int64_t *indptr, v
 }
 
 // One row block [b0, b1) of H (global rows): T_b = H[b] * Q, the pattern of its rows of S (k >= i, ascending), their values.
-static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, int flags, int64_t b0, int64_t b1, smm_result::Piece *out)
+// With a mask (canonical, n x n) the pattern is the mask's rows [b0, b1) filtered to k >= i: no H^T, no stage-2 symbolic
+// phase, no sort.
+static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, const smm_csr *mask, int flags, int64_t b0, int64_t b1,
+                               smm_result::Piece *out)
 {
     const int64_t nb = b1 - b0, n = h->rows, K = h->cols;
     const bool exact = (flags & SMM_EXACT) != 0;
@@ -2758,31 +2767,52 @@ static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, 
     int64_t tnnz = 0, snnz = 0;
     int64_t *tptr = nullptr; int *tidx = nullptr, *tptr32 = nullptr, *lists = nullptr; double *tval = nullptr, *dense = nullptr;
     int64_t *sptr = nullptr; int *sidx = nullptr; double *sval = nullptr;
+    int *mcnt = nullptr;
     auto drop = [&]() {
         smm_plan_destroy(p1); smm_plan_destroy(p2); smm_csr_destroy(tb);
         (void)hipStreamSynchronize(c->stream);
         pool_free(c, tptr); pool_free(c, tidx); pool_free(c, tval); pool_free(c, tptr32); pool_free(c, lists); pool_free(c, dense);
+        pool_free(c, mcnt);
     };
 #define BCHK(expr) do { int rc_ = (expr); if (rc_ != SMM_OK) { drop(); pool_free(c, sptr); pool_free(c, sidx); pool_free(c, sval); return rc_; } } while (0)
     // stage 1: T_b, the engine's SpGEMM (first-touch rows, SMM_EXACT values in the reference's order)
-    BCHK(smm_spgemm_symbolic(c, &hv, q, flags & SMM_EXACT, 0, &p1, &tnnz));
+    const bool zero = h->nnz == 0 || q->nnz == 0;       // (masked only: S is the mask's pattern filled with +0.0)
+    if (!zero) BCHK(smm_spgemm_symbolic(c, &hv, q, flags & SMM_EXACT, 0, &p1, &tnnz));
     BCHK(pool_get(c, (size_t)nb + 1, &tptr));
     BCHK(pool_get(c, (size_t)std::max<int64_t>(tnnz, 1) + 2, &tidx));
     BCHK(pool_get(c, (size_t)std::max<int64_t>(tnnz, 1), &tval));
-    BCHK(smm_spgemm_numeric(c, p1, tptr, tidx, tval));
+    if (!zero) BCHK(smm_spgemm_numeric(c, p1, tptr, tidx, tval));
+    else HIPCHK(hipMemsetAsync(tptr, 0, ((size_t)nb + 1) * sizeof(int64_t), c->stream));
     smm_plan_destroy(p1); p1 = nullptr;
     if (tnnz >= INT32_MAX) BCHK(fail(SMM_ERR_INVALID, "sparse triple product: one row of T has >= 2^31 entries"));
-    // stage 2, pattern: T_b (int32 row pointer, borrowed) times H^T, i <= k
-    BCHK(pool_get(c, (size_t)nb + 1, &tptr32));
-    LAUNCH(c, "smm_triple_sparse_narrow", smm_triple_sparse_narrow, std::min<int64_t>((nb + 256) / 256, 4096), 256, 0, nb, (const int64_t *)tptr, tptr32);
-    BCHK(smm_csr_from_device(c, nb, K, tnnz, tptr32, tidx, tval, &tb));
-    BCHK(smm_spgemm_symbolic(c, tb, ht, SMM_SYMMETRIC, b0, &p2, &snnz));
-    BCHK(pool_get(c, (size_t)nb + 1, &sptr));
-    BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sidx));
-    BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sval));
-    BCHK(smm_spgemm_numeric(c, p2, sptr, sidx, sval));        // (its values are T * H^T in T's order: overwritten below)
-    smm_plan_destroy(p2); p2 = nullptr;
-    BCHK(seg_sort(c, nb, sptr, sidx));
+    if (mask) {
+        // stage 2, pattern: the mask's rows filtered to k >= i (count, scan, copy)
+        BCHK(pool_get(c, (size_t)2 * nb + 2, &mcnt));
+        BCHK(pool_get(c, (size_t)nb + 1, &sptr));
+        const int g = (int)std::min<int64_t>((nb + 255) / 256, 4096);
+        LAUNCH(c, "smm_masked_tri_count", smm_masked_tri_count, g, 256, 0, (int)nb, b0, mask->ptr, mask->idx, mcnt, mcnt + nb + 1);
+        BCHK(scan_launch<int>(c, nb, mcnt, sptr));
+        HIPCHK(hipMemcpyAsync(&snnz, sptr + nb, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sidx));
+        BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sval));
+        if (snnz > 0)
+            LAUNCH(c, "smm_masked_tri_copy", smm_masked_tri_copy, std::min<int64_t>((nb + 3) / 4, 16384), 256, 0, (int)nb,
+                   (const int *)(mcnt + nb + 1), (const int *)mcnt, (const int64_t *)sptr, mask->idx, sidx);
+        LAUNCH_CHECK();
+    } else {
+        // stage 2, pattern: T_b (int32 row pointer, borrowed) times H^T, i <= k
+        BCHK(pool_get(c, (size_t)nb + 1, &tptr32));
+        LAUNCH(c, "smm_triple_sparse_narrow", smm_triple_sparse_narrow, std::min<int64_t>((nb + 256) / 256, 4096), 256, 0, nb, (const int64_t *)tptr, tptr32);
+        BCHK(smm_csr_from_device(c, nb, K, tnnz, tptr32, tidx, tval, &tb));
+        BCHK(smm_spgemm_symbolic(c, tb, ht, SMM_SYMMETRIC, b0, &p2, &snnz));
+        BCHK(pool_get(c, (size_t)nb + 1, &sptr));
+        BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sidx));
+        BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sval));
+        BCHK(smm_spgemm_numeric(c, p2, sptr, sidx, sval));        // (its values are T * H^T in T's order: overwritten below)
+        smm_plan_destroy(p2); p2 = nullptr;
+        BCHK(seg_sort(c, nb, sptr, sidx));
+    }
     // stage 2, values: rows binned by the length of T_i
     if (snnz > 0) {
         BCHK(pool_get(c, (size_t)3 * nb + 4, &lists));
@@ -2832,14 +2862,10 @@ static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, 
     return SMM_OK;
 }
 
-extern "C" int smm_triple_product_sparse(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t row_begin, int64_t row_end, smm_result **out)
+// mask == nullptr: smm_triple_product_sparse; else smm_triple_product_sparse_masked (mask validated, canonical, n x n)
+static int triple_sparse_impl(smm_ctx *c, smm_csr *h, smm_csr *q, const smm_csr *mask, int flags, int64_t row_begin, int64_t row_end,
+                              smm_result **out)
 {
-    if (!out) return fail(SMM_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
-    CTX_LOCK(c);
-    CHK(check_pair(c, h, q));
-    CHK(exact_guard(c, flags));
     const int64_t n = h->rows, K = h->cols;
     if (q->cols > K) return fail(SMM_ERR_INVALID, "Q has more columns (%lld) than H (%lld)", (long long)q->cols, (long long)K);
     if (row_begin < 0 || row_end > n || row_begin > row_end) return fail(SMM_ERR_INVALID, "bad row range");
@@ -2849,24 +2875,24 @@ extern "C" int smm_triple_product_sparse(smm_ctx *c, smm_csr *h, smm_csr *q, int
     const int64_t nr = row_end - row_begin;
     smm_result *r = new smm_result();
     r->ctx = c; r->rows = nr; r->cols = n;
-    if (nr == 0 || h->nnz == 0 || q->nnz == 0 || K == 0) { *out = r; return SMM_OK; }
+    if (nr == 0 || (mask ? mask->nnz == 0 : (h->nnz == 0 || q->nnz == 0 || K == 0))) { *out = r; return SMM_OK; }
     int rc = SMM_OK;
 #define RCHK(expr) do { rc = (expr); if (rc != SMM_OK) { smm_result_destroy(r); return rc; } } while (0)
-    if (!h->tr) RCHK(transpose_impl(c, h, &h->tr));
+    if (!mask && !h->tr) RCHK(transpose_impl(c, h, &h->tr));
     // row blocks: products of H[i] * Q (an upper bound of nnz(T_i)) summed up to the budget, at least one row per block
     std::vector<int64_t> prod((size_t)nr);
     {
         smm_csr hv = *h;
         hv.ptr = h->ptr + row_begin; hv.rows = nr; hv.owned = false; hv.segs.clear(); hv.locs.clear(); hv.slabs.clear(); hv.packs.clear();
         hv.ccs.clear(); hv.idx16 = nullptr; hv.idx_pad = nullptr; hv.tr = nullptr;
-        RCHK(smm_row_products(c, &hv, q, prod.data()));
+        if (h->nnz > 0 && q->nnz > 0) RCHK(smm_row_products(c, &hv, q, prod.data()));
     }
     int64_t b0 = row_begin;
     while (b0 < row_end) {
         int64_t b1 = b0, acc = 0;
         while (b1 < row_end && (b1 == b0 || acc + prod[(size_t)(b1 - row_begin)] <= c->t3_max_t)) acc += prod[(size_t)(b1++ - row_begin)];
         smm_result::Piece pc{0, 0, nullptr, nullptr, nullptr};
-        RCHK(triple_sparse_block(c, h, q, h->tr, flags, b0, b1, &pc));
+        RCHK(triple_sparse_block(c, h, q, h->tr, mask, flags, b0, b1, &pc));
         r->pieces.push_back(pc);
         r->nnz += pc.nnz;
         b0 = b1;
@@ -2896,6 +2922,178 @@ extern "C" int smm_triple_product_sparse(smm_ctx *c, smm_csr *h, smm_csr *q, int
 #undef RCHK
     *out = r;
     return SMM_OK;
+}
+
+extern "C" int smm_triple_product_sparse(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t row_begin, int64_t row_end, smm_result **out)
+{
+    if (!out) return fail(SMM_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(check_pair(c, h, q));
+    CHK(exact_guard(c, flags));
+    return triple_sparse_impl(c, h, q, nullptr, flags, row_begin, row_end, out);
+}
+
+// A mask operand: same context, the expected shape, canonical (rows strictly ascending).
+static int check_mask(smm_ctx *c, smm_csr *mask, int64_t rows, int64_t cols, const char *where)
+{
+    if (!mask) return fail(SMM_ERR_INVALID, "%s: mask is NULL", where);
+    if (mask->ctx != c) return fail(SMM_ERR_INVALID, "%s: mask belongs to another context", where);
+    if (mask->rows != rows || mask->cols != cols)
+        return fail(SMM_ERR_INVALID, "%s: mask is %lld x %lld, expected %lld x %lld", where, (long long)mask->rows, (long long)mask->cols,
+                    (long long)rows, (long long)cols);
+    CHK(validate(c, mask));
+    if (mask->vflags & (CSR_UNSORTED | CSR_HAS_EQUAL))
+        return fail(SMM_ERR_INVALID, "%s: the mask is not canonical (rows must hold strictly ascending columns)", where);
+    return SMM_OK;
+}
+
+extern "C" int smm_triple_product_sparse_masked(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *mask, int flags, int64_t row_begin,
+                                                int64_t row_end, smm_result **out)
+{
+    if (!out) return fail(SMM_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(check_pair(c, h, q));
+    CHK(check_mask(c, mask, h->rows, h->rows, "smm_triple_product_sparse_masked"));
+    CHK(exact_guard(c, flags));
+    return triple_sparse_impl(c, h, q, mask, flags, row_begin, row_end, out);
+}
+
+// ------------------------------------------------------------------------------ masked SpGEMM
+extern "C" int smm_ctx_tune_masked(smm_ctx *c, int mode)
+{
+    if (!c || mode < 0 || mode > 2) return fail(SMM_ERR_INVALID, "bad argument (mode: 0 auto, 1 dot, 2 row)");
+    CTX_LOCK(c);
+    c->masked_mode = mode;
+    return SMM_OK;
+}
+
+// nnz(mask) values of (A * B) on the mask's pattern into d_out (validated operands, canonical mask of A.rows x B.cols).
+static int masked_impl(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int flags, double *d_out)
+{
+    const int64_t m = a->rows, nm = mask->nnz;
+    if (nm == 0) return SMM_OK;
+    if (a->nnz == 0 || b->nnz == 0) {                 // the mask's pattern filled with +0.0
+        HIPCHK(hipMemsetAsync(d_out, 0, (size_t)nm * sizeof(double), c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return SMM_OK;
+    }
+    const bool exact = (flags & SMM_EXACT) != 0;
+    const bool a_canonical = !(a->vflags & (CSR_UNSORTED | CSR_HAS_EQUAL));
+    const bool dot = a_canonical && c->masked_mode != 2;
+    if (dot && !b->trv) CHK(transpose_impl(c, b, &b->trv));
+    int *cls = nullptr, *lists = nullptr, *map = nullptr;
+    auto drop = [&]() { (void)hipStreamSynchronize(c->stream); pool_free(c, cls); pool_free(c, lists); pool_free(c, map); };
+#define MCHK(expr) do { int rc_ = (expr); if (rc_ != SMM_OK) { drop(); return rc_; } } while (0)
+#define MHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { drop(); return fail(SMM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
+    MCHK(pool_get(c, (size_t)m + 8, &cls));
+    MCHK(pool_get(c, (size_t)MK_NCLS * m, &lists));
+    int *cnt = cls + m;
+    MHIP(hipMemsetAsync(cnt, 0, 8 * sizeof(int), c->stream));
+    LAUNCH(c, "smm_masked_cost", smm_masked_cost, std::min<int64_t>((m + 3) / 4, 16384), 256, 0, (int)m, mask->ptr, mask->idx, a->ptr, a->idx,
+           b->ptr, (int)b->rows, dot ? (const int *)b->trv->ptr : nullptr, (int)b->cols, c->masked_mode, cls);
+    LAUNCH(c, "smm_masked_bin", smm_masked_bin, std::min<int64_t>((m + 255) / 256, 4096), 256, 0, (int)m, (const int *)cls, lists, cnt);
+    MHIP(hipGetLastError());
+    int hc[8] = {0};
+    MHIP(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+    MHIP(hipStreamSynchronize(c->stream));
+    MaskedArgs A{};
+    A.m = (int)m;
+    A.a_ptr = a->ptr; A.a_idx = a->idx; A.a_val = a->val; A.K = (int)a->cols;
+    A.b_ptr = b->ptr; A.b_idx = b->idx; A.b_val = b->val; A.n = (int)b->cols;
+    if (dot) { A.t_ptr = b->trv->ptr; A.t_idx = b->trv->idx; A.t_val = b->trv->val; }
+    A.m_ptr = mask->ptr; A.m_idx = mask->idx; A.out = d_out;
+    A.bdup = (b->vflags & (CSR_UNSORTED | CSR_HAS_EQUAL)) ? 1 : 0;
+    A.err = c->d_err;
+    // dot path: lanes per mask entry, the mean length of a row of B^T rounded up to a power of two in [4, 64]
+    int dot_g = 4;
+    while (dot_g < WAVE && (int64_t)dot_g * b->cols < b->nnz) dot_g *= 2;
+    auto wg_kernel = [&](const void *kern, size_t lds) -> hipError_t {
+        return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    };
+    // global classes: one zeroed row of `width` ints per workgroup, at most 256 MB of them in flight
+    auto global_grid = [&](int nrows, int64_t width) {
+        return std::max<int64_t>(1, std::min<int64_t>({(int64_t)nrows, (int64_t)c->n_cu, ((int64_t)1 << 26) / std::max<int64_t>(width, 1)}));
+    };
+    for (int cl = 0; cl < MK_NCLS; ++cl) {
+        if (hc[cl] <= 0) continue;
+        A.rowlist = lists + (size_t)cl * m; A.nrows = hc[cl];
+        if (cl == MK_DOT_WAVE) {               // one wave per row, four rows per workgroup
+            const size_t lds = (size_t)4 * 512 * 2 * sizeof(int);
+            const int64_t grid = std::min<int64_t>((hc[cl] + 3) / 4, (int64_t)c->n_cu * 16);
+            LAUNCH(c, "smm_masked_dot", (smm_masked_dot_hash<512, 9, 64, 4>), grid, 256, lds, A, dot_g);
+        } else if (cl == MK_DOT_WG) {          // one workgroup per row
+            const size_t lds = (size_t)8192 * 2 * sizeof(int);
+            auto kern = smm_masked_dot_hash<8192, 13, 256, 1>;
+            MHIP(wg_kernel((const void *)kern, lds));
+            LAUNCH(c, "smm_masked_dot", kern, std::min<int64_t>(hc[cl], (int64_t)c->n_cu * 2), 256, lds, A, dot_g);
+        } else if (cl == MK_ROW_WAVE) {
+            const size_t lds = (size_t)4 * 512 * (sizeof(double) + sizeof(int) + 1);
+            const int64_t grid = std::min<int64_t>((hc[cl] + 3) / 4, (int64_t)c->n_cu * 16);
+            if (exact) LAUNCH(c, "smm_masked_row", (smm_masked_row_hash<512, 9, 64, 4, true>), grid, 256, lds, A);
+            else       LAUNCH(c, "smm_masked_row", (smm_masked_row_hash<512, 9, 64, 4, false>), grid, 256, lds, A);
+        } else if (cl == MK_ROW_WG) {
+            const size_t lds = (size_t)8192 * (sizeof(double) + sizeof(int) + 1);
+            auto kern = exact ? smm_masked_row_hash<8192, 13, 256, 1, true> : smm_masked_row_hash<8192, 13, 256, 1, false>;
+            MHIP(wg_kernel((const void *)kern, lds));
+            LAUNCH(c, "smm_masked_row", kern, std::min<int64_t>(hc[cl], (int64_t)c->n_cu), 256, lds, A);
+        } else {                               // MK_DOT_GLOBAL / MK_ROW_GLOBAL
+            const int64_t width = cl == MK_DOT_GLOBAL ? a->cols : b->cols;
+            const int64_t grid = global_grid(hc[cl], width);
+            pool_free(c, map); map = nullptr;
+            MCHK(pool_get(c, (size_t)grid * (size_t)width, &map));
+            MHIP(hipMemsetAsync(map, 0, (size_t)grid * (size_t)width * sizeof(int), c->stream));
+            A.map = map;
+            if (cl == MK_DOT_GLOBAL) {
+                LAUNCH(c, "smm_masked_dot", smm_masked_dot_global, grid, 256, 0, A, dot_g);
+            } else {
+                if (exact) LAUNCH(c, "smm_masked_row", smm_masked_row_global<true>, grid, 256, 0, A);
+                else       LAUNCH(c, "smm_masked_row", smm_masked_row_global<false>, grid, 256, 0, A);
+            }
+        }
+        MHIP(hipGetLastError());
+    }
+#undef MCHK
+#undef MHIP
+    drop();
+    return take_plan_error(c, "smm_spgemm_masked");
+}
+
+static int masked_args(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int flags)
+{
+    if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "smm_spgemm_masked: only SMM_EXACT is a flag of this call");
+    CHK(check_pair(c, a, b));
+    CHK(check_mask(c, mask, a->rows, b->cols, "smm_spgemm_masked"));
+    CHK(exact_guard(c, flags));
+    return SMM_OK;
+}
+
+extern "C" int smm_spgemm_masked(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int flags, double *d_c_data)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(masked_args(c, a, b, mask, flags));
+    if (mask->nnz > 0 && !d_c_data) return fail(SMM_ERR_INVALID, "d_c_data is NULL but nnz(mask) > 0");
+    return masked_impl(c, a, b, mask, flags, d_c_data);
+}
+
+extern "C" int smm_spgemm_masked_host(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int flags, double *c_data)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(masked_args(c, a, b, mask, flags));
+    if (mask->nnz == 0) return SMM_OK;
+    if (!c_data) return fail(SMM_ERR_INVALID, "c_data is NULL but nnz(mask) > 0");
+    double *d = nullptr;
+    CHK(pool_get(c, (size_t)mask->nnz, &d));
+    int rc = masked_impl(c, a, b, mask, flags, d);
+    if (rc == SMM_OK) rc = download(c, c_data, d, (size_t)mask->nnz * sizeof(double));
+    (void)hipStreamSynchronize(c->stream);
+    pool_free(c, d);
+    return rc;
 }
 
 // ------------------------------------------------------------------------------ memory helpers

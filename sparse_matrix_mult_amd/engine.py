@@ -303,18 +303,24 @@ class Context:
         """Row-block budget of the sparse triple product: entries of T = H[b] * Q per block (0 = default 2^27)."""
         check(self.lib, self.lib.smm_ctx_tune_triple_sparse(self.handle, int(max_t_nnz)))
 
-    def _triple_sparse(self, h, q, full, row_begin, row_end, exact):
+    def _triple_sparse(self, h, q, full, row_begin, row_end, exact, mask=None):
         row_end = h.rows if row_end is None else row_end
         r = ctypes.c_void_p()
-        check(self.lib, self.lib.smm_triple_product_sparse(self.handle, h.handle, q.handle, _flags(False, exact, full),
-                                                           int(row_begin), int(row_end), ctypes.byref(r)))
+        if mask is None:
+            check(self.lib, self.lib.smm_triple_product_sparse(self.handle, h.handle, q.handle, _flags(False, exact, full),
+                                                               int(row_begin), int(row_end), ctypes.byref(r)))
+        else:
+            check(self.lib, self.lib.smm_triple_product_sparse_masked(self.handle, h.handle, q.handle, mask.handle,
+                                                                      _flags(False, exact, full), int(row_begin), int(row_end),
+                                                                      ctypes.byref(r)))
         return r, row_end - row_begin, int(self.lib.smm_result_nnz(r))
 
-    def triple_sparse_host(self, h, q, full=False, row_begin=0, row_end=None, exact=False, index_dtype=None):
+    def triple_sparse_host(self, h, q, full=False, row_begin=0, row_end=None, exact=False, index_dtype=None, mask=None):
         """Rows [row_begin, row_end) of S = H Q H^T as CSR (smm_triple_product_sparse): columns k >= i in ascending
         order (full=True: the whole symmetric matrix).  (indptr int64, indices int32 -- int64 when nnz >= 2^31 or
-        index_dtype says so --, data float64) numpy arrays."""
-        r, rows, nnz = self._triple_sparse(h, q, full, row_begin, row_end, exact)
+        index_dtype says so --, data float64) numpy arrays.  mask (a canonical n x n DeviceCSR): S on the positions of
+        the mask with k >= i only (smm_triple_product_sparse_masked)."""
+        r, rows, nnz = self._triple_sparse(h, q, full, row_begin, row_end, exact, mask)
         try:
             wide = nnz > np.iinfo(np.int32).max if index_dtype is None else np.dtype(index_dtype) == np.int64
             indptr = np.empty(rows + 1, dtype=np.int64)
@@ -325,10 +331,10 @@ class Context:
         finally:
             self.lib.smm_result_destroy(r)
 
-    def triple_sparse_torch(self, h, q, full=False, row_begin=0, row_end=None, exact=False):
+    def triple_sparse_torch(self, h, q, full=False, row_begin=0, row_end=None, exact=False, mask=None):
         """triple_sparse_host with the result left in HBM: (indptr int64, indices int32, data float64) torch tensors."""
         import torch
-        r, rows, nnz = self._triple_sparse(h, q, full, row_begin, row_end, exact)
+        r, rows, nnz = self._triple_sparse(h, q, full, row_begin, row_end, exact, mask)
         try:
             dev = torch.device("cuda", self.device)
             indptr = torch.empty(rows + 1, dtype=torch.int64, device=dev)
@@ -339,6 +345,25 @@ class Context:
             return indptr, indices, data
         finally:
             self.lib.smm_result_destroy(r)
+
+    # ------------------------------------------------------------------ A B on a given pattern
+    def tune_masked(self, mode=0):
+        """Path of the masked SpGEMM: 0 per-row cost model (default), 1 dot path, 2 row path (A that is not canonical
+        always takes the row path)."""
+        check(self.lib, self.lib.smm_ctx_tune_masked(self.handle, int(mode)))
+
+    def spgemm_masked_host(self, a, b, mask, exact=False):
+        """Values of A B at the positions of mask (a canonical DeviceCSR, values ignored), in the mask's order: a
+        float64 numpy array of nnz(mask) (smm_spgemm_masked_host).  Positions no product reaches hold +0.0."""
+        out = np.empty(mask.nnz, dtype=np.float64)
+        check(self.lib, self.lib.smm_spgemm_masked_host(self.handle, a.handle, b.handle, mask.handle, _flags(False, exact),
+                                                        _ptr(out)))
+        return out
+
+    def spgemm_masked_into(self, a, b, mask, d_ptr, exact=False):
+        """spgemm_masked_host into caller-owned HBM (nnz(mask) float64 at d_ptr)."""
+        check(self.lib, self.lib.smm_spgemm_masked(self.handle, a.handle, b.handle, mask.handle, _flags(False, exact),
+                                                   ctypes.c_void_p(d_ptr or 0)))
 
 
 class DeviceCSR:

@@ -614,7 +614,7 @@ def sparse_matrix_multiply(matrix_a, matrix_b, output_format='sparse', symmetric
     return result
 
 
-def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False):
+def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False, mask=None):
     """S = H @ Q @ H.T with a SPARSE result, computed on the GPU without any n x n or n x K array.
 
     matrix_h : n x K, matrix_q : K x K (scipy CSR, anything csr_matrix() accepts, or a PinnedOperand).
@@ -625,6 +625,10 @@ def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False):
     set_exact(True) the values are bit-identical to sparse_matrix_multiply(H, Q, use_triple_product=True) at the
     stored positions; otherwise within 1e-10 relative.  For an S that is nearly full the dense triple product is
     the faster tool.
+
+    mask (n x n; scipy CSR, anything csr_matrix() accepts, or a PinnedOperand): S only at the positions of the mask
+    with k >= i (its values are ignored; positions without a structural contribution hold +0.0), without building the
+    structural pattern.  compute_full_matrix=True mirrors that upper part; mask entries below the diagonal are ignored.
     """
     matrix_h = _as_csr(matrix_h)
     matrix_q = _as_csr(matrix_q)
@@ -634,6 +638,8 @@ def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False):
         raise ValueError("Matrix dimensions are incompatible for multiplication.")
     n = matrix_h.shape[0]
     out_shape = (n, n)
+    if mask is not None:
+        return _triple_masked(matrix_h, matrix_q, _as_csr(mask), out_shape, bool(compute_full_matrix))
     if matrix_h.nnz == 0 or matrix_q.nnz == 0:
         if _result_device:
             return _device_zeros(default_context(), out_shape, True)
@@ -668,3 +674,148 @@ def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False):
             raise
         clear_cache()                                            # the resident operands / plans were in the way
         return product()
+
+
+# ------------------------------------------------------------------ products on a given pattern
+def _check_mask_shape(mask, shape, what):
+    if tuple(mask.shape) != tuple(shape):
+        raise ValueError(f"{what}: the mask is {mask.shape[0]} x {mask.shape[1]}, expected {shape[0]} x {shape[1]}")
+
+
+def _canonical_mask(mask):
+    """The mask with strictly ascending rows.  A scipy mask that is not canonical is canonicalised on a host copy
+    (duplicates merged, columns sorted; explicitly stored zeros stay positions); a PinnedOperand must be canonical."""
+    if isinstance(mask, PinnedOperand):
+        if mask.nnz and not mask._handle.is_canonical():
+            raise ValueError("the mask PinnedOperand is not canonical (rows must hold strictly ascending columns): "
+                             "pin mask.sorted_indices() after sum_duplicates()")
+        return mask
+    if not mask.has_canonical_format:
+        mask = mask.copy()
+        mask.sum_duplicates()
+    return mask
+
+
+def _mask_pattern(mask):
+    """(indptr, indices) of a canonical mask as int32 host arrays."""
+    if isinstance(mask, PinnedOperand):
+        if not mask.nnz:
+            return np.zeros(mask.shape[0] + 1, dtype=np.int32), np.empty(0, dtype=np.int32)
+        indptr, indices, _ = mask._handle.to_host()
+        return indptr, indices
+    nnz = int(mask.indptr[-1])
+    return mask.indptr.astype(np.int32), mask.indices[:nnz].astype(np.int32)
+
+
+def _pattern_result(ctx, indptr, indices, data, shape):
+    """A result on a host pattern: scipy CSR, or a DeviceCSRResult under set_result_device(True) (data may be a
+    torch tensor already)."""
+    if _result_device:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        if not torch.is_tensor(data):
+            data = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+        return DeviceCSRResult(torch.from_numpy(indptr.astype(np.int64)).to(dev), torch.from_numpy(indices).to(dev), data, shape)
+    return _result_csr(indptr, indices, data, shape)
+
+
+def _with_leases(ctx, mats, body):
+    """body(*leases) with every operand of `mats` leased (the operand cache applies to each), retried once after
+    clear_cache() when the device ran out of memory while resident operands / plans were in the way."""
+    def product():
+        cached = _cache_entries > 0
+        keys = [_operand_key(m) if cached and not isinstance(m, PinnedOperand) else None for m in mats]
+        leases = []
+        try:
+            for i, m in enumerate(mats):
+                protect = tuple(k[0] for k in keys[i + 1:] if k is not None)
+                leases.append(_acquire(ctx, m, keys[i], protect=protect))
+            return body(*leases)
+        finally:
+            for lease in reversed(leases):
+                lease.release()
+
+    try:
+        return product()
+    except SmmError as e:
+        if e.code != SMM_ERR_ALLOC or not (_cache or _plans):
+            raise
+        clear_cache()
+        return product()
+
+
+def masked_matrix_multiply(matrix_a, matrix_b, mask):
+    """C = (A @ B) evaluated only at the positions of `mask` (GraphBLAS masked mxm / SDDMM with sparse operands).
+
+    matrix_a : m x K, matrix_b : K x n, mask : m x n (scipy CSR, anything csr_matrix() accepts, or a PinnedOperand).
+    C's pattern is exactly the mask's (canonicalised: columns strictly ascending); the mask's values are ignored and
+    its explicitly stored zeros are positions.  A position where no product A[i,k] * B[k,j] exists holds +0.0 and is
+    stored (C.eliminate_zeros() drops such entries).  Under set_exact(True) every value that
+    sparse_matrix_multiply(A, B) stores is reproduced bit for bit; otherwise within 1e-10 relative.  A pair (k, j)
+    that row i of A does not store is never multiplied.  Returns a scipy CSR (a DeviceCSRResult under
+    set_result_device(True)).  Nothing is printed.
+    """
+    matrix_a = _as_csr(matrix_a)
+    matrix_b = _as_csr(matrix_b)
+    mask = _as_csr(mask)
+    if matrix_a.shape[1] != matrix_b.shape[0]:
+        raise ValueError("Matrix dimensions are incompatible for multiplication.")
+    out_shape = (matrix_a.shape[0], matrix_b.shape[1])
+    _check_mask_shape(mask, out_shape, "masked_matrix_multiply")
+    if mask.nnz == 0:
+        if _result_device:
+            return _device_zeros(default_context(), out_shape, True)
+        return csr_matrix(out_shape)
+    if matrix_a.nnz == 0 or matrix_b.nnz == 0:
+        ctx = default_context() if (_result_device or isinstance(mask, PinnedOperand)) else None
+        mask = _canonical_mask(mask)
+        indptr, indices = _mask_pattern(mask)
+        return _pattern_result(ctx, indptr, indices, np.zeros(len(indices), dtype=np.float64), out_shape)
+    ctx = default_context()
+    mask = _canonical_mask(mask)
+
+    def body(la, lb, lm):
+        indptr, indices = _mask_pattern(mask)
+        if _result_device:
+            import torch
+            dev = torch.device("cuda", ctx.device)
+            torch.cuda.current_stream(dev).synchronize()
+            data = torch.empty(lm.handle.nnz, dtype=torch.float64, device=dev)
+            ctx.spgemm_masked_into(la.handle, lb.handle, lm.handle, data.data_ptr(), exact=_exact)
+            ctx.synchronize()
+            return _pattern_result(ctx, indptr, indices, data, out_shape)
+        return _result_csr(indptr, indices, ctx.spgemm_masked_host(la.handle, lb.handle, lm.handle, exact=_exact), out_shape)
+
+    return _with_leases(ctx, (matrix_a, matrix_b, mask), body)
+
+
+def _triple_masked(matrix_h, matrix_q, mask, out_shape, full):
+    _check_mask_shape(mask, out_shape, "sparse_triple_product")
+    if mask.nnz == 0:
+        if _result_device:
+            return _device_zeros(default_context(), out_shape, True)
+        return csr_matrix(out_shape)
+    if matrix_h.nnz == 0 or matrix_q.nnz == 0:
+        # the mask's upper part (mirrored when full) filled with +0.0, on the host
+        ctx = default_context() if (_result_device or isinstance(mask, PinnedOperand)) else None
+        indptr, indices = _mask_pattern(_canonical_mask(mask))
+        rows = np.repeat(np.arange(out_shape[0], dtype=np.int64), np.diff(indptr))
+        keep = indices >= rows
+        up = csr_matrix((np.ones(int(keep.sum())), (rows[keep], indices[keep])), shape=out_shape)
+        if full:
+            up = (up + up.T).tocsr()
+        up.sort_indices()
+        return _pattern_result(ctx, up.indptr.astype(np.int32), up.indices.astype(np.int32), np.zeros(up.nnz), out_shape)
+    ctx = default_context()
+    mask = _canonical_mask(mask)
+
+    def body(lh, lq, lm):
+        if _result_device:
+            import torch
+            torch.cuda.current_stream(torch.device("cuda", ctx.device)).synchronize()
+            out = DeviceCSRResult(*ctx.triple_sparse_torch(lh.handle, lq.handle, full=full, exact=_exact, mask=lm.handle), out_shape)
+            ctx.synchronize()
+            return out
+        return _result_csr(*ctx.triple_sparse_host(lh.handle, lq.handle, full=full, exact=_exact, mask=lm.handle), out_shape)
+
+    return _with_leases(ctx, (matrix_h, matrix_q, mask), body)
