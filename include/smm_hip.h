@@ -87,9 +87,12 @@ int  smm_ctx_synchronize(smm_ctx *ctx);
 int  smm_ctx_set_check(smm_ctx *ctx, int enable);
 /* The context keeps freed scratch (the lists and tables of destroyed plans, result staging) in a pool for reuse.
  * smm_ctx_release_pool returns the pool's free blocks to the device (matrix_ops.clear_cache() calls it);
- * smm_ctx_pool_bytes says how much is held.  Every allocation that fails flushes the pool and retries once by itself. */
+ * smm_ctx_pool_bytes says how much is held.  Every allocation that fails flushes the pool and retries once by itself.
+ * smm_ctx_live_bytes is the total of the pool blocks handed out: those of open plans and results only, once every
+ * call has returned -- whether it succeeded or failed. */
 int     smm_ctx_release_pool(smm_ctx *ctx);
 int64_t smm_ctx_pool_bytes(smm_ctx *ctx);
+int64_t smm_ctx_live_bytes(smm_ctx *ctx);
 /* TEST HOOK: the nth device allocation from now fails -- its first attempt only (the library's own flush-and-retry
  * must make the call succeed), or with hard != 0 both attempts (the call returns SMM_ERR_ALLOC).  smm_ctx_alloc_retries
  * counts the allocations that needed the retry. */

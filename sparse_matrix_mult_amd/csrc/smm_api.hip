@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -179,6 +180,37 @@ template <typename T> static int pool_get(smm_ctx *c, size_t count, T **out)
     return rc;
 }
 
+// Owner of one pool block: reset() and the destructor hand it back to the pool.  Neither synchronises, and neither
+// needs to: the context has one stream, so the pool hands a block out again only to work queued behind everything
+// that used it, and pool_flush returns blocks to the device through hipFree, which waits for the device.
+template <typename T> struct PoolBuf {
+    smm_ctx *c;
+    T *p = nullptr;
+    explicit PoolBuf(smm_ctx *ctx) : c(ctx) {}
+    PoolBuf(PoolBuf &&o) noexcept : c(o.c), p(o.release()) {}
+    PoolBuf &operator=(PoolBuf &&o) noexcept { if (this != &o) { reset(); c = o.c; p = o.release(); } return *this; }
+    ~PoolBuf() { reset(); }
+    int alloc(size_t count) { reset(); return pool_get(c, count, &p); }
+    void reset() { pool_free(c, p); p = nullptr; }
+    T *release() { T *q = p; p = nullptr; return q; }
+    operator T *() const { return p; }
+};
+// Owner of a dev_malloc'd array until it is committed to an operand or a cache entry (release()).
+template <typename T> struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.release()) {}
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { (void)hipFree(p); p = o.release(); } return *this; }
+    ~DevBuf() { (void)hipFree(p); }
+    hipError_t alloc(smm_ctx *c, size_t count) { return dev_malloc(c, (void **)&p, count * sizeof(T)); }
+    T *release() { T *q = p; p = nullptr; return q; }
+    operator T *() const { return p; }
+};
+// unique_ptr deleter that calls one of the ABI's destroy functions (plans and results under construction)
+template <auto Destroy> struct Destroyer {
+    template <typename T> void operator()(T *x) const { Destroy(x); }
+};
+
 struct LaunchTimer {
     smm_ctx *c; const char *name; hipEvent_t t0 = nullptr, t1 = nullptr;
     LaunchTimer(smm_ctx *ctx, const char *n) : c(ctx), name(n)
@@ -326,6 +358,14 @@ extern "C" int64_t smm_ctx_pool_bytes(smm_ctx *c)
     CTX_LOCK(c);
     int64_t t = 0;
     for (auto &b : c->pool) t += (int64_t)b.bytes;
+    return t;
+}
+extern "C" int64_t smm_ctx_live_bytes(smm_ctx *c)
+{
+    if (!c) return -1;
+    CTX_LOCK(c);
+    int64_t t = 0;
+    for (auto &kv : c->live) t += (int64_t)kv.second;
     return t;
 }
 extern "C" int smm_ctx_inject_alloc_failure(smm_ctx *c, int nth, int hard)
@@ -744,6 +784,17 @@ struct smm_csr {
     smm_csr *trv = nullptr;                      // B^T with values for the masked SpGEMM's dot path (update_values drops it)
 };
 
+// Rows [r0, r0 + nr) of a validated h as a borrowed operand without any of h's caches.  The row pointer is not rebased:
+// kernels use ptr[row] and ptr[row + 1] only as absolute positions in idx / val.
+static smm_csr csr_row_view(const smm_csr *h, int64_t r0, int64_t nr)
+{
+    smm_csr v;
+    v.ctx = h->ctx; v.rows = nr; v.cols = h->cols; v.nnz = h->nnz;
+    v.ptr = h->ptr + r0; v.idx = h->idx; v.val = h->val;
+    v.validated = h->validated; v.vflags = h->vflags;
+    return v;
+}
+
 static int validate(smm_ctx *c, smm_csr *m)
 {
     if (m->validated) return (m->vflags & CSR_BAD) ? fail(SMM_ERR_INVALID, "malformed CSR operand") : SMM_OK;
@@ -780,13 +831,10 @@ extern "C" int smm_csr_from_host(smm_ctx *c, int64_t rows, int64_t cols, int64_t
     CHK(csr_common(c, rows, cols, nnz));
     CTX_LOCK(c);
     if (!indptr || (nnz > 0 && (!indices || !data))) return fail(SMM_ERR_INVALID, "NULL CSR array");
-    int *dp = nullptr, *di = nullptr; double *dv = nullptr;
-    if (dev_malloc(c, (void **)&dp, (rows + 1) * sizeof(int)) != hipSuccess ||
-        dev_malloc(c, (void **)&di, (std::max<int64_t>(nnz, 1) + 2) * sizeof(int)) != hipSuccess ||     // + slack: the wide symbolic walk reads columns in pairs
-        dev_malloc(c, (void **)&dv, std::max<int64_t>(nnz, 1) * sizeof(double)) != hipSuccess) {
-        (void)hipFree(dp); (void)hipFree(di); (void)hipFree(dv);
+    DevBuf<int> dp, di; DevBuf<double> dv;
+    if (dp.alloc(c, rows + 1) != hipSuccess || di.alloc(c, std::max<int64_t>(nnz, 1) + 2) != hipSuccess ||     // + slack: the wide symbolic walk reads columns in pairs
+        dv.alloc(c, std::max<int64_t>(nnz, 1)) != hipSuccess)
         return fail(SMM_ERR_ALLOC, "hipMalloc of a CSR operand failed");
-    }
     HIPCHK(hipMemcpyAsync(dp, indptr, (rows + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     if (nnz > 0) {
         HIPCHK(hipMemcpyAsync(di, indices, nnz * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -795,7 +843,7 @@ extern "C" int smm_csr_from_host(smm_ctx *c, int64_t rows, int64_t cols, int64_t
     HIPCHK(hipStreamSynchronize(c->stream));
     smm_csr *m = new smm_csr();
     m->ctx = c; m->rows = rows; m->cols = cols; m->nnz = nnz;
-    m->ptr = dp; m->idx = di; m->val = dv; m->owned = true;
+    m->ptr = dp.release(); m->idx = di.release(); m->val = dv.release(); m->owned = true;
     int rc = validate(c, m);
     if (rc != SMM_OK) { smm_csr_destroy(m); return rc; }
     *out = m;
@@ -899,17 +947,15 @@ static int ensure_seg(smm_ctx *c, smm_csr *b, const Geom &g, const int **out)
     for (auto &e : b->segs)
         if (e.wf == g.wf && e.n_ft == g.n_ft) { *out = e.seg; return SMM_OK; }
     const int64_t total = b->rows * (int64_t)(g.n_ft + 1);
-    int *seg = nullptr;
-    if (dev_malloc(c, (void **)&seg, std::max<int64_t>(total, 1) * sizeof(int)) != hipSuccess)
-        return fail(SMM_ERR_ALLOC, "hipMalloc of the tile index failed");
+    DevBuf<int> seg;
+    if (seg.alloc(c, std::max<int64_t>(total, 1)) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the tile index failed");
     if (total > 0) {
         LAUNCH(c, "smm_segptr", smm_segptr, (total + 255) / 256, 256, 0, (int)b->rows, g.n_ft, g.wf, b->ptr, b->idx, seg);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { (void)hipFree(seg); return fail(SMM_ERR_HIP, "smm_segptr: %s", hipGetErrorString(e)); }
+        LAUNCH_CHECK();
     }
-    b->segs.push_back({g.wf, g.n_ft, seg});
-    b->derived_bytes += std::max<int64_t>(total, 1) * (int64_t)sizeof(int);
     *out = seg;
+    b->segs.push_back({g.wf, g.n_ft, seg.release()});
+    b->derived_bytes += std::max<int64_t>(total, 1) * (int64_t)sizeof(int);
     return SMM_OK;
 }
 
@@ -918,13 +964,13 @@ static int ensure_idx16(smm_ctx *c, smm_csr *b)
     if (b->idx16) return SMM_OK;
     if (b->cols >= 65535) return fail(SMM_ERR_INVALID, "16-bit column copy needs < 65535 columns");
     // + 2 entries of slack: the wide symbolic walk reads columns in pairs
-    if (dev_malloc(c, (void **)&b->idx16, (std::max<int64_t>(b->nnz, 1) + 2) * sizeof(unsigned short)) != hipSuccess)
-        return fail(SMM_ERR_ALLOC, "hipMalloc of the 16-bit column copy failed");
+    DevBuf<unsigned short> idx16;
+    if (idx16.alloc(c, std::max<int64_t>(b->nnz, 1) + 2) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the 16-bit column copy failed");
     if (b->nnz > 0) {
-        LAUNCH(c, "smm_idx16", smm_idx16, std::min<int64_t>((b->nnz + 255) / 256, 65536), 256, 0, (int)b->nnz, b->idx, b->idx16);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { (void)hipFree(b->idx16); b->idx16 = nullptr; return fail(SMM_ERR_HIP, "smm_idx16: %s", hipGetErrorString(e)); }
+        LAUNCH(c, "smm_idx16", smm_idx16, std::min<int64_t>((b->nnz + 255) / 256, 65536), 256, 0, (int)b->nnz, b->idx, idx16);
+        LAUNCH_CHECK();
     }
+    b->idx16 = idx16.release();
     b->derived_bytes += (std::max<int64_t>(b->nnz, 1) + 2) * (int64_t)sizeof(unsigned short);
     return SMM_OK;
 }
@@ -937,12 +983,11 @@ static int idx_with_slack(smm_ctx *c, smm_csr *b, const int **out)
     if (b->owned) { *out = b->idx; return SMM_OK; }
     if (!b->idx_pad) {
         const size_t n = (size_t)std::max<int64_t>(b->nnz, 1) + 2;
-        if (dev_malloc(c, (void **)&b->idx_pad, n * sizeof(int)) != hipSuccess)
-            return fail(SMM_ERR_ALLOC, "hipMalloc of the padded column copy failed");
-        hipError_t e = hipMemsetAsync(b->idx_pad + (n - 2), 0, 2 * sizeof(int), c->stream);
-        if (e == hipSuccess && b->nnz > 0)
-            e = hipMemcpyAsync(b->idx_pad, b->idx, (size_t)b->nnz * sizeof(int), hipMemcpyDeviceToDevice, c->stream);
-        if (e != hipSuccess) { (void)hipFree(b->idx_pad); b->idx_pad = nullptr; return fail(SMM_ERR_HIP, "padded column copy: %s", hipGetErrorString(e)); }
+        DevBuf<int> pad;
+        if (pad.alloc(c, n) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the padded column copy failed");
+        HIPCHK(hipMemsetAsync(pad + (n - 2), 0, 2 * sizeof(int), c->stream));
+        if (b->nnz > 0) HIPCHK(hipMemcpyAsync(pad, b->idx, (size_t)b->nnz * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+        b->idx_pad = pad.release();
         b->derived_bytes += (int64_t)(n * sizeof(int));
     }
     *out = b->idx_pad;
@@ -954,17 +999,15 @@ static int ensure_loc(smm_ctx *c, smm_csr *b, const Geom &g, const short **out)
     for (auto &e : b->locs)
         if (e.wc == g.wc) { *out = e.loc; return SMM_OK; }
     if (g.wc > 32767) return fail(SMM_ERR_INVALID, "coarse tile wider than 32767 columns");
-    short *loc = nullptr;
-    if (dev_malloc(c, (void **)&loc, std::max<int64_t>(b->nnz, 1) * sizeof(short)) != hipSuccess)
-        return fail(SMM_ERR_ALLOC, "hipMalloc of the tile-local column array failed");
+    DevBuf<short> loc;
+    if (loc.alloc(c, std::max<int64_t>(b->nnz, 1)) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the tile-local column array failed");
     if (b->nnz > 0) {
         LAUNCH(c, "smm_loc16", smm_loc16, std::min<int64_t>((b->nnz + 255) / 256, 65536), 256, 0, (int)b->nnz, g.wc, b->idx, loc);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { (void)hipFree(loc); return fail(SMM_ERR_HIP, "smm_loc16: %s", hipGetErrorString(e)); }
+        LAUNCH_CHECK();
     }
-    b->locs.push_back({g.wc, loc});
-    b->derived_bytes += std::max<int64_t>(b->nnz, 1) * (int64_t)sizeof(short);
     *out = loc;
+    b->locs.push_back({g.wc, loc.release()});
+    b->derived_bytes += std::max<int64_t>(b->nnz, 1) * (int64_t)sizeof(short);
     return SMM_OK;
 }
 
@@ -984,31 +1027,30 @@ static int ensure_ell(smm_ctx *c, smm_csr *h, int nchunks, int chunk, bool sprea
     const int nslices = (n + WAVE - 1) / WAVE;
     const int64_t items = (int64_t)nchunks * nslices;
     if (items >= 0x7fffffff) return fail(SMM_ERR_INVALID, "H too large for the sliced-ELL index (%lld blocks)", (long long)items);
-    int64_t *cnt = nullptr;
-    CHK(pool_get(c, (size_t)items, &cnt));
-    if (dev_malloc(c, (void **)&h->ell_off, (size_t)(items + 1) * sizeof(int64_t)) != hipSuccess) {
-        pool_free(c, cnt);
-        return fail(SMM_ERR_ALLOC, "hipMalloc of the ELL index failed");
-    }
+    PoolBuf<int64_t> cnt(c);
+    DevBuf<int64_t> off;
+    CHK(cnt.alloc((size_t)items));
+    if (off.alloc(c, (size_t)items + 1) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the ELL index failed");
     EllArgs E{};
     E.n = n; E.nchunks = nchunks; E.chunk = chunk; E.nslices = nslices;
     E.h_ptr = h->ptr; E.h_idx = h->idx; E.h_val = h->val; E.hseg = hseg;
-    E.cnt = cnt; E.off = h->ell_off;
+    E.cnt = cnt; E.off = off;
     const int grid = (int)((items + 3) / 4);
     LAUNCH(c, "smm_ell_count", smm_ell_count, grid, 256, 0, E);
-    LAUNCH(c, "smm_scan", smm_scan<int64_t>, 1, 1024, 0, (int)items, (const int64_t *)cnt, h->ell_off);
+    LAUNCH(c, "smm_scan", smm_scan<int64_t>, 1, 1024, 0, (int)items, (const int64_t *)cnt, off);
     int64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, h->ell_off + items, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&total, off + items, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    pool_free(c, cnt);
+    cnt.reset();
     // + one wave of slack: stage 2 requests step 0 of a block before it knows the block is empty
-    if (dev_malloc(c, (void **)&h->ell_col, (total + WAVE) * sizeof(short)) != hipSuccess ||
-        dev_malloc(c, (void **)&h->ell_val, (total + WAVE) * sizeof(double)) != hipSuccess)
+    DevBuf<short> col; DevBuf<double> val;
+    if (col.alloc(c, total + WAVE) != hipSuccess || val.alloc(c, total + WAVE) != hipSuccess)
         return fail(SMM_ERR_ALLOC, "hipMalloc of the ELL payload (%lld entries) failed", (long long)total);
-    E.col = h->ell_col; E.val = h->ell_val;
+    E.col = col; E.val = val;
     if (spread) LAUNCH(c, "smm_ell_fill", smm_ell_fill<1>, grid, 256, 0, E);
     else LAUNCH(c, "smm_ell_fill", smm_ell_fill<2>, grid, 256, 0, E);
     LAUNCH_CHECK();
+    h->ell_off = off.release(); h->ell_col = col.release(); h->ell_val = val.release();
     h->ell_chunk = chunk; h->ell_nchunks = nchunks; h->ell_spread = spread;
     h->ell_bytes = (items + 1) * (int64_t)sizeof(int64_t) + (total + WAVE) * (int64_t)(sizeof(short) + sizeof(double));
     return SMM_OK;
@@ -1033,29 +1075,28 @@ static int ensure_ring(smm_ctx *c, smm_csr *h, bool spread)
     const int n = (int)h->rows;
     const int nkg = (n + 16 * WAVE - 1) / (16 * WAVE);
     const int64_t streams = (int64_t)nkg * 16;
-    int64_t *cnt = nullptr;
-    CHK(pool_get(c, (size_t)streams, &cnt));
-    if (dev_malloc(c, (void **)&h->ring_off, (size_t)(streams + 1) * sizeof(int64_t)) != hipSuccess) {
-        pool_free(c, cnt);
-        return fail(SMM_ERR_ALLOC, "hipMalloc of the ring stream index failed");
-    }
+    PoolBuf<int64_t> cnt(c);
+    DevBuf<int64_t> off;
+    CHK(cnt.alloc((size_t)streams));
+    if (off.alloc(c, (size_t)streams + 1) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the ring stream index failed");
     RingBuildArgs B{};
     B.n = n; B.K = (int)h->cols; B.npieces = npieces; B.nkg = nkg;
     B.h_ptr = h->ptr; B.h_idx = h->idx; B.h_val = h->val;
-    B.cnt = cnt; B.off = h->ring_off; B.err = c->d_err;
+    B.cnt = cnt; B.off = off; B.err = c->d_err;
     if (spread) LAUNCH(c, "smm_ring_build", (smm_ring_build<8, false>), nkg, 1024, 0, B);
     else LAUNCH(c, "smm_ring_build", (smm_ring_build<1, false>), nkg, 1024, 0, B);
-    LAUNCH(c, "smm_scan", smm_scan<int64_t>, 1, 1024, 0, (int)streams, (const int64_t *)cnt, h->ring_off);
+    LAUNCH(c, "smm_scan", smm_scan<int64_t>, 1, 1024, 0, (int)streams, (const int64_t *)cnt, off);
     int64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, h->ring_off + streams, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&total, off + streams, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    pool_free(c, cnt);
-    if (dev_malloc(c, (void **)&h->ring_col, (size_t)(total + 1) * WAVE * sizeof(short)) != hipSuccess ||
-        dev_malloc(c, (void **)&h->ring_val, (size_t)(total + 1) * WAVE * sizeof(double)) != hipSuccess ||
-        dev_malloc(c, (void **)&h->ring_hdr, (size_t)(total + streams + 64) * sizeof(unsigned)) != hipSuccess)
+    cnt.reset();
+    DevBuf<short> col; DevBuf<double> val; DevBuf<unsigned> hdr;
+    if (col.alloc(c, (size_t)(total + 1) * WAVE) != hipSuccess || val.alloc(c, (size_t)(total + 1) * WAVE) != hipSuccess ||
+        hdr.alloc(c, (size_t)(total + streams + 64)) != hipSuccess)
         return fail(SMM_ERR_ALLOC, "hipMalloc of the ring streams (%lld steps) failed", (long long)total);
-    B.col = h->ring_col; B.val = h->ring_val; B.hdr = h->ring_hdr;
+    B.col = col; B.val = val; B.hdr = hdr;
     CHK(ring_fill(c, h, B, spread));
+    h->ring_off = off.release(); h->ring_col = col.release(); h->ring_val = val.release(); h->ring_hdr = hdr.release();
     h->ring_npieces = npieces; h->ring_spread = spread;
     h->ring_bytes = (streams + 1) * (int64_t)sizeof(int64_t) + (total + 1) * WAVE * (int64_t)(sizeof(short) + sizeof(double)) +
                     (total + streams + 64) * (int64_t)sizeof(unsigned);
@@ -1082,15 +1123,14 @@ extern "C" int smm_row_products(smm_ctx *c, const smm_csr *a, const smm_csr *b, 
     CHK(check_pair(c, (smm_csr *)a, (smm_csr *)b));
     if (!products_host) return fail(SMM_ERR_INVALID, "products_host is NULL");
     if (a->rows == 0) return SMM_OK;
-    int64_t *d = nullptr;
-    CHK(pool_get(c, (size_t)a->rows, &d));
+    PoolBuf<int64_t> d(c);
+    CHK(d.alloc((size_t)a->rows));
     const int grid = (int)std::min<int64_t>((a->rows + 3) / 4, 16384);
     LAUNCH(c, "smm_row_work", smm_row_work, grid, 256, 0, (int)a->rows, (int)b->cols, (int64_t)0, 0, a->ptr, a->idx,
            b->ptr, d, (int64_t *)nullptr);
     LAUNCH_CHECK();
     HIPCHK(hipMemcpyAsync(products_host, d, a->rows * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    pool_free(c, d);
     return SMM_OK;
 }
 
@@ -1126,8 +1166,8 @@ static int launch_numeric_t(smm_ctx *c, NumericArgs &args)
         grid = std::min<int64_t>(grid, per_cu * c->n_cu);
     }
 #ifdef SMM_STAMPS
-    unsigned long long *d_st = nullptr;
-    CHK(pool_get(c, 4, &d_st));
+    PoolBuf<unsigned long long> d_st(c);
+    CHK(d_st.alloc(4));
     (void)hipMemsetAsync(d_st, 0, 32, c->stream);
     args.stamps = d_st;
 #endif
@@ -1141,7 +1181,7 @@ static int launch_numeric_t(smm_ctx *c, NumericArgs &args)
         const double tot = (double)(h[0] + h[1] + h[2]);
         fprintf(stderr, "[SMM_STAMPS] units=%lld NW=%d wc=%d nct=%d exact=%d  init %.1f%%  accumulate %.1f%%  epilogue %.1f%%  (sum %.3g cycles)\n",
                 (long long)grid, NW, args.wc, args.nct, (int)EXACT, 100 * h[0] / tot, 100 * h[1] / tot, 100 * h[2] / tot, tot);
-        pool_free(c, d_st);
+        d_st.reset();
     }
 #endif
     if (e != hipSuccess) return fail(SMM_ERR_HIP, "smm_numeric launch: %s", hipGetErrorString(e));
@@ -1226,6 +1266,7 @@ extern "C" void smm_plan_destroy(smm_plan *p)
     pool_free(c, p->d_scnt); pool_free(c, p->d_dst0); pool_free(c, p->d_runs2); pool_free(c, p->d_tflag);
     delete p;
 }
+using PlanPtr = std::unique_ptr<smm_plan, Destroyer<smm_plan_destroy>>;
 extern "C" int64_t smm_plan_nnz(const smm_plan *p) { return p ? p->nnz : -1; }
 extern "C" int64_t smm_plan_device_bytes(const smm_plan *p)
 {
@@ -1252,14 +1293,12 @@ static int scan_launch(smm_ctx *c, int64_t n, const T *in, int64_t *out)
         return SMM_OK;
     }
     const int tiles = (int)((n + SCAN_TILE - 1) / SCAN_TILE);
-    int64_t *sums = nullptr;
-    CHK(pool_get(c, (size_t)2 * tiles + 1, &sums));
+    PoolBuf<int64_t> sums(c);
+    CHK(sums.alloc((size_t)2 * tiles + 1));
     LAUNCH(c, "smm_scan", smm_scan_tile_sums<T>, tiles, 1024, 0, (int)n, in, sums);
     LAUNCH(c, "smm_scan", smm_scan<int64_t>, 1, 1024, 0, tiles, (const int64_t *)sums, sums + tiles);
     LAUNCH(c, "smm_scan", smm_scan_tiles<T>, tiles, 1024, 0, (int)n, in, (const int64_t *)(sums + tiles), out);
-    hipError_t e = hipGetLastError();
-    pool_free(c, sums);         // stream-ordered reuse: the pool hands it out again only to work queued behind these launches
-    if (e != hipSuccess) return fail(SMM_ERR_HIP, "scan: %s", hipGetErrorString(e));
+    LAUNCH_CHECK();
     return SMM_OK;
 }
 
@@ -1275,41 +1314,33 @@ static int ensure_pack(smm_ctx *c, smm_csr *b, const Geom &g, smm_csr::PackCache
     CHK(ensure_seg(c, b, gs, &seg));
     const int64_t cells = (int64_t)g.nct * b->rows;
     if (cells + 1 >= INT32_MAX) return fail(SMM_ERR_INVALID, "too many (tile, row) pieces");
-    int *units = nullptr; int64_t *off64 = nullptr;
-    CHK(pool_get(c, (size_t)std::max<int64_t>(cells, 1), &units));
-    int rc = pool_get(c, (size_t)cells + 1, &off64);
-    if (rc != SMM_OK) { pool_free(c, units); return rc; }
+    PoolBuf<int> units(c);
+    PoolBuf<int64_t> off64(c);
+    CHK(units.alloc((size_t)std::max<int64_t>(cells, 1)));
+    CHK(off64.alloc((size_t)cells + 1));
     int *d_maxlen = (int *)((char *)c->d_flags + 244);
     (void)hipMemsetAsync(d_maxlen, 0, sizeof(int), c->stream);
     if (cells > 0) LAUNCH(c, "smm_pack_count", smm_pack_count, (cells + 255) / 256, 256, 0, (int)b->rows, g.nct, seg, units, d_maxlen);
-    rc = scan_launch<int>(c, cells, units, off64);
+    CHK(scan_launch<int>(c, cells, units, off64));
     int64_t total = 0;
     int maxlen = 0;
-    if (rc == SMM_OK) {
-        hipError_t e = hipMemcpyAsync(&total, off64 + cells, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&maxlen, d_maxlen, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(SMM_ERR_HIP, "pack build: %s", hipGetErrorString(e));
-    }
-    if (rc == SMM_OK && total >= INT32_MAX) rc = fail(SMM_ERR_INVALID, "operand too large for the packed payload");
-    smm_csr::PackCache e{g.wc, g.nct, nullptr, nullptr, maxlen};
+    HIPCHK(hipMemcpyAsync(&total, off64 + cells, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&maxlen, d_maxlen, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (total >= INT32_MAX) return fail(SMM_ERR_INVALID, "operand too large for the packed payload");
     // (+ 4 units of slack: the piece walk's last lane reads up to three 8-byte units past a very short last piece)
-    if (rc == SMM_OK &&
-        (dev_malloc(c, (void **)&e.desc, (size_t)std::max<int64_t>(cells, 1) * sizeof(int2)) != hipSuccess ||
-         dev_malloc(c, (void **)&e.pay, (size_t)(std::max<int64_t>(total, 1) + 4) * sizeof(double)) != hipSuccess)) {
-        (void)hipFree(e.desc); (void)hipFree(e.pay);
-        rc = fail(SMM_ERR_ALLOC, "hipMalloc of the packed payload failed");
-    }
-    if (rc == SMM_OK && cells > 0) {
-        LAUNCH(c, "smm_pack_desc", smm_pack_desc, (cells + 255) / 256, 256, 0, (int)b->rows, g.nct, seg, (const int64_t *)off64, e.desc);
+    DevBuf<int2> desc; DevBuf<double> pay;
+    if (desc.alloc(c, (size_t)std::max<int64_t>(cells, 1)) != hipSuccess || pay.alloc(c, (size_t)(std::max<int64_t>(total, 1) + 4)) != hipSuccess)
+        return fail(SMM_ERR_ALLOC, "hipMalloc of the packed payload failed");
+    if (cells > 0) {
+        LAUNCH(c, "smm_pack_desc", smm_pack_desc, (cells + 255) / 256, 256, 0, (int)b->rows, g.nct, seg, (const int64_t *)off64, desc);
         LAUNCH(c, "smm_pack_fill", smm_pack_fill, std::min<int64_t>((b->rows + 3) / 4, 65536), 256, 0, (int)b->rows, g.nct, g.wc, b->ptr,
-               b->idx, b->val, seg, (const int2 *)e.desc, e.pay);
-        hipError_t he = hipGetLastError();
-        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);        // units / off64 go back to the pool
-        if (he != hipSuccess) { (void)hipFree(e.desc); (void)hipFree(e.pay); rc = fail(SMM_ERR_HIP, "pack build: %s", hipGetErrorString(he)); }
+               b->idx, b->val, seg, (const int2 *)desc, pay);
+        LAUNCH_CHECK();
+        HIPCHK(hipStreamSynchronize(c->stream));        // units / off64 go back to the pool
     }
-    pool_free(c, units); pool_free(c, off64);
-    if (rc != SMM_OK) return rc;
+    units.reset(); off64.reset();
+    smm_csr::PackCache e{g.wc, g.nct, desc.release(), pay.release(), maxlen};
     b->packs.push_back(e);
     b->derived_bytes += std::max<int64_t>(cells, 1) * (int64_t)sizeof(int2) + (std::max<int64_t>(total, 1) + 4) * (int64_t)sizeof(double);
     *out = e;
@@ -1328,43 +1359,33 @@ static int ensure_ccs(smm_ctx *c, smm_csr *b, int ws, int n_slabs, smm_csr::CcsC
     CHK(ensure_seg(c, b, gs, &seg));
     const int64_t cells = (int64_t)n_slabs * b->rows;
     if (cells + n_slabs + 1 >= INT32_MAX) return fail(SMM_ERR_INVALID, "too many (slab, row) pieces");
-    int *chunks = nullptr; int64_t *off64 = nullptr;
-    CHK(pool_get(c, (size_t)std::max<int64_t>(cells, 1), &chunks));
-    int rc = pool_get(c, (size_t)cells + 1, &off64);
-    if (rc != SMM_OK) { pool_free(c, chunks); return rc; }
+    PoolBuf<int> chunks(c);
+    PoolBuf<int64_t> off64(c);
+    CHK(chunks.alloc((size_t)std::max<int64_t>(cells, 1)));
+    CHK(off64.alloc((size_t)cells + 1));
     if (cells > 0) LAUNCH(c, "smm_ccs_count", smm_ccs_count, (cells + 255) / 256, 256, 0, (int)b->rows, n_slabs, seg, chunks);
-    rc = scan_launch<int>(c, cells, chunks, off64);
+    CHK(scan_launch<int>(c, cells, chunks, off64));
     int64_t total = 0;
-    if (rc == SMM_OK) {
-        hipError_t e = hipMemcpyAsync(&total, off64 + cells, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(SMM_ERR_HIP, "chunked stream build: %s", hipGetErrorString(e));
-    }
-    if (rc == SMM_OK && total + 1 >= (INT32_MAX / CCS_CHUNK)) rc = fail(SMM_ERR_INVALID, "operand too large for the chunked column stream");
-    smm_csr::CcsCache e{ws, n_slabs, (ws + 31) / 32, (int)total, nullptr, nullptr, 0.0};
-    unsigned long long *d_stat = nullptr;
-    if (rc == SMM_OK) rc = pool_get(c, 2, &d_stat);
-    if (rc == SMM_OK && hipMemsetAsync(d_stat, 0, 2 * sizeof(unsigned long long), c->stream) != hipSuccess) rc = fail(SMM_ERR_HIP, "memset");
+    HIPCHK(hipMemcpyAsync(&total, off64 + cells, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (total + 1 >= (INT32_MAX / CCS_CHUNK)) return fail(SMM_ERR_INVALID, "operand too large for the chunked column stream");
+    PoolBuf<unsigned long long> d_stat(c);
+    CHK(d_stat.alloc(2));
+    HIPCHK(hipMemsetAsync(d_stat, 0, 2 * sizeof(unsigned long long), c->stream));
     const int64_t ptr_entries = (int64_t)n_slabs * (b->rows + 1);
-    if (rc == SMM_OK &&
-        (dev_malloc(c, (void **)&e.cptr, (size_t)ptr_entries * sizeof(int)) != hipSuccess ||
-         dev_malloc(c, (void **)&e.stream, (size_t)(total + 1) * CCS_CHUNK * sizeof(unsigned short)) != hipSuccess)) {
-        (void)hipFree(e.cptr); (void)hipFree(e.stream);
-        rc = fail(SMM_ERR_ALLOC, "hipMalloc of the chunked column stream failed");
-    }
-    if (rc == SMM_OK) {
-        LAUNCH(c, "smm_ccs_ptr", smm_ccs_ptr, (ptr_entries + 255) / 256, 256, 0, (int)b->rows, n_slabs, (const int64_t *)off64, e.cptr);
-        LAUNCH(c, "smm_ccs_fill", smm_ccs_fill, std::min<int64_t>(std::max<int64_t>((cells + 3) / 4, 1), 65536), 256, 0, (int)b->rows, n_slabs, ws,
-               e.bm_words, b->idx, seg, (const int *)e.cptr, e.stream, d_stat);
-        hipError_t he = hipGetLastError();
-        unsigned long long stat[2] = {0, 0};
-        if (he == hipSuccess) he = hipMemcpyAsync(stat, d_stat, sizeof(stat), hipMemcpyDeviceToHost, c->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);        // chunks / off64 go back to the pool
-        e.same_word = stat[1] ? (double)stat[0] / (double)stat[1] : 0.0;
-        if (he != hipSuccess) { (void)hipFree(e.cptr); (void)hipFree(e.stream); rc = fail(SMM_ERR_HIP, "chunked stream build: %s", hipGetErrorString(he)); }
-    }
-    pool_free(c, chunks); pool_free(c, off64); pool_free(c, d_stat);
-    if (rc != SMM_OK) return rc;
+    DevBuf<int> cptr; DevBuf<unsigned short> stream;
+    if (cptr.alloc(c, (size_t)ptr_entries) != hipSuccess || stream.alloc(c, (size_t)(total + 1) * CCS_CHUNK) != hipSuccess)
+        return fail(SMM_ERR_ALLOC, "hipMalloc of the chunked column stream failed");
+    const int bm_words = (ws + 31) / 32;
+    LAUNCH(c, "smm_ccs_ptr", smm_ccs_ptr, (ptr_entries + 255) / 256, 256, 0, (int)b->rows, n_slabs, (const int64_t *)off64, cptr);
+    LAUNCH(c, "smm_ccs_fill", smm_ccs_fill, std::min<int64_t>(std::max<int64_t>((cells + 3) / 4, 1), 65536), 256, 0, (int)b->rows, n_slabs, ws,
+           bm_words, b->idx, seg, (const int *)cptr, stream, d_stat);
+    LAUNCH_CHECK();
+    unsigned long long stat[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(stat, d_stat, sizeof(stat), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));        // chunks / off64 go back to the pool
+    chunks.reset(); off64.reset(); d_stat.reset();
+    smm_csr::CcsCache e{ws, n_slabs, bm_words, (int)total, cptr.release(), stream.release(), stat[1] ? (double)stat[0] / (double)stat[1] : 0.0};
     b->ccs.push_back(e);
     b->derived_bytes += ptr_entries * (int64_t)sizeof(int) + (total + 1) * CCS_CHUNK * (int64_t)sizeof(unsigned short);
     *out = e;
@@ -1410,31 +1431,24 @@ static int ensure_slab(smm_ctx *c, smm_csr *b, const SlabGeom &g, smm_csr::SlabC
     const int *seg = nullptr;
     CHK(ensure_seg(c, b, gs, &seg));
     const int64_t cells = (int64_t)g.n_slabs * b->rows;
-    int *cnt = nullptr; int64_t *off64 = nullptr;
-    CHK(pool_get(c, (size_t)std::max<int64_t>(cells, 1), &cnt));
-    int rc = pool_get(c, (size_t)cells + 1, &off64);
-    if (rc != SMM_OK) { pool_free(c, cnt); return rc; }
-    smm_csr::SlabCache e{g.ws, g.n_slabs, nullptr, nullptr, nullptr};
-    if (dev_malloc(c, (void **)&e.soff, (size_t)(cells + 1) * sizeof(int)) != hipSuccess ||
-        dev_malloc(c, (void **)&e.scol, (size_t)std::max<int64_t>(b->nnz, 1) * sizeof(short)) != hipSuccess ||
-        dev_malloc(c, (void **)&e.sval, (size_t)std::max<int64_t>(b->nnz, 1) * sizeof(double)) != hipSuccess) {
-        (void)hipFree(e.soff); (void)hipFree(e.scol); (void)hipFree(e.sval);
-        pool_free(c, cnt); pool_free(c, off64);
+    PoolBuf<int> cnt(c);
+    PoolBuf<int64_t> off64(c);
+    CHK(cnt.alloc((size_t)std::max<int64_t>(cells, 1)));
+    CHK(off64.alloc((size_t)cells + 1));
+    DevBuf<int> soff; DevBuf<short> scol; DevBuf<double> sval;
+    if (soff.alloc(c, (size_t)(cells + 1)) != hipSuccess || scol.alloc(c, (size_t)std::max<int64_t>(b->nnz, 1)) != hipSuccess ||
+        sval.alloc(c, (size_t)std::max<int64_t>(b->nnz, 1)) != hipSuccess)
         return fail(SMM_ERR_ALLOC, "hipMalloc of the slab-major copy of B failed");
-    }
     if (cells > 0) LAUNCH(c, "smm_slab_count", smm_slab_count, (cells + 255) / 256, 256, 0, (int)b->rows, g.n_slabs, seg, cnt);
-    rc = scan_launch<int>(c, cells, cnt, off64);
-    if (rc == SMM_OK) {
-        LAUNCH(c, "smm_narrow32", smm_narrow32, std::min<int64_t>((cells + 256) / 256, 65536), 256, 0, cells + 1, (const int64_t *)off64, e.soff);
-        if (b->rows > 0)
-            LAUNCH(c, "smm_slab_fill", smm_slab_fill, std::min<int64_t>((b->rows + 3) / 4, 65536), 256, 0, (int)b->rows, g.n_slabs, g.ws,
-                   b->ptr, b->idx, b->val, seg, (const int *)e.soff, e.scol, e.sval);
-        hipError_t he = hipGetLastError();
-        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);        // cnt / off64 go back to the pool
-        if (he != hipSuccess) rc = fail(SMM_ERR_HIP, "slab build: %s", hipGetErrorString(he));
-    }
-    pool_free(c, cnt); pool_free(c, off64);
-    if (rc != SMM_OK) { (void)hipFree(e.soff); (void)hipFree(e.scol); (void)hipFree(e.sval); return rc; }
+    CHK(scan_launch<int>(c, cells, cnt, off64));
+    LAUNCH(c, "smm_narrow32", smm_narrow32, std::min<int64_t>((cells + 256) / 256, 65536), 256, 0, cells + 1, (const int64_t *)off64, soff);
+    if (b->rows > 0)
+        LAUNCH(c, "smm_slab_fill", smm_slab_fill, std::min<int64_t>((b->rows + 3) / 4, 65536), 256, 0, (int)b->rows, g.n_slabs, g.ws,
+               b->ptr, b->idx, b->val, seg, (const int *)soff, scol, sval);
+    LAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));        // cnt / off64 go back to the pool
+    cnt.reset(); off64.reset();
+    smm_csr::SlabCache e{g.ws, g.n_slabs, soff.release(), scol.release(), sval.release()};
     b->slabs.push_back(e);
     b->derived_bytes += (cells + 1) * (int64_t)sizeof(int) + std::max<int64_t>(b->nnz, 1) * (int64_t)(sizeof(short) + sizeof(double));
     *out = e;
@@ -1693,238 +1707,227 @@ extern "C" int smm_plan_inject_fault(smm_ctx *c, smm_plan *p, int kind)
     return SMM_OK;
 }
 
-extern "C" int smm_spgemm_symbolic(smm_ctx *c, smm_csr *a, smm_csr *b, int flags, int64_t a_row_offset,
-                                   smm_plan **plan, int64_t *nnz_out)
+// ------------------------------------------------------------------------------ symbolic phase
+// The marker of the symbolic phase is a bitmap of B's columns (ncols/8 bytes per wave, in LDS when it fits): at 50 000
+// columns 24 waves fit a CU, at 1e6 columns one.  Rows with few products -- known after the row work -- therefore take an
+// LDS hash set instead, wherever that is the smaller marker:
+//   four classes: <= 256 / 512 / 1024 / 2048 products in 512 / 1024 / 2048 / 4096 slots (2 ... 16 KB per wave; round 4:
+//   there used to be two, and a band of half-width 8 -- 289 products, 33 columns per row -- ran 8 waves per CU in the
+//   4096-slot class: 11.6 ms; in the 1024-slot class 4.9 ms).
+// ... and TINY rows (<= 16 products from <= 16 entries of A, whatever B looks like) go four to a wave (smm_symbolic_tiny)
+constexpr int NHC = 4;
+constexpr int HS[NHC] = {512, 1024, 2048, 4096};
+constexpr int SB_REST = NHC, SB_TINY = NHC + 1, SB_TINY2 = NHC + 2, SB_N = NHC + 3;      // bins of the symbolic phase: hash classes, bitmap, tiny (16 / 32 lanes per row)
+
+// What the row work leaves for the walks.
+struct SymRows {
+    PoolBuf<int64_t> prod;       // products per row (the numeric binning at the end applies the same tiny-row predicate)
+    PoolBuf<int> slists;         // SB_N x m: the rows of each bin (binned only)
+    int sbin[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int hmax1 = 0;               // most products of a row in a hash class (0: no hash classes)
+    bool binned = false;
+    bool safe = false;           // B has unsorted rows or repeated columns
+    int64_t total_ub = 0;        // sum of the list capacities
+    explicit SymRows(smm_ctx *c) : prod(c), slists(c) {}
+};
+
+// Waves per workgroup (4, 2 or 1) that fit the most waves of wave_bytes of LDS each into a CU's 160 KB; returns how many
+// (at most 32).  *per_wg keeps its value when not even one wave fits.
+static int most_waves_per_cu(size_t wave_bytes, int *per_wg)
 {
-    if (!plan) return fail(SMM_ERR_INVALID, "plan is NULL");
-    *plan = nullptr;
-    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
-    CTX_LOCK(c);
-    CHK(check_pair(c, a, b));
-    if (a_row_offset < 0) return fail(SMM_ERR_INVALID, "negative a_row_offset");
-    CHK(exact_guard(c, flags));
-    smm_plan *p = new smm_plan();
-    p->ctx = c; p->a = a; p->b = b; p->flags = flags; p->row_offset = a_row_offset;
-    p->m = a->rows; p->ncols = b->cols;
-    p->b_sorted = !(b->vflags & CSR_UNSORTED);
-    p->g = make_geom(c, p->ncols, b, (flags & SMM_EXACT) != 0);
-    const bool sym = flags & SMM_SYMMETRIC;
-    const int64_t m = p->m;
-    int rc = SMM_OK;
-#define PCHK(expr) do { rc = (expr); if (rc != SMM_OK) { smm_plan_destroy(p); return rc; } } while (0)
-    PCHK(pool_get(c, (size_t)m + 1, &p->d_cptr));
-    if (m == 0 || a->nnz == 0 || b->nnz == 0 || p->ncols == 0) {
-        // sparse_sparse_sparse.cpp:181-185: zero operand -> rowPtr of zeros only
-        hipError_t e = hipMemsetAsync(p->d_cptr, 0, (m + 1) * sizeof(int64_t), c->stream);
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "memset: %s", hipGetErrorString(e)); }
-        p->nnz = 0;
-        if (nnz_out) *nnz_out = 0;
-        *plan = p;
-        return SMM_OK;
+    int best = 0;
+    for (int cand : {4, 2, 1}) {
+        const int waves = (int)std::min<size_t>(32, ((size_t)160 * 1024 / (cand * wave_bytes)) * cand);
+        if (waves > best) { best = waves; *per_wg = cand; }
     }
-    // capacities of the per-row ordered lists
-    int64_t *d_prod = nullptr, *d_ub = nullptr;
-    PCHK(pool_get(c, (size_t)m, &d_prod));
-    PCHK(pool_get(c, (size_t)m, &d_ub));
-    PCHK(pool_get(c, (size_t)m + 1, &p->d_ub_off));
-    const int wgrid = (int)std::min<int64_t>((m + 3) / 4, 16384);
+    return best;
+}
+
+// smm_symbolic_ccs over `units` (slab, row) units, or over the listed rows (n_slabs = 1), of the chunked column stream cc
+static int launch_ccs(smm_ctx *c, const smm_plan *p, const smm_csr::CcsCache &cc, int64_t units, int n_slabs, const int *rowlist,
+                      const int *nrows, int *cnt, int *counter)
+{
+    const size_t wave_bytes = (size_t)(cc.bm_words + WAVE) * sizeof(unsigned);
+    int cw = 4;
+    most_waves_per_cu(wave_bytes, &cw);
+    const size_t lds = wave_bytes * cw;
+    const int sgrid = (int)std::min<int64_t>((units + cw - 1) / cw, (int64_t)c->n_cu * 8 * (4 / cw));
+    const bool dr = c->sym_dense == 2 || (c->sym_dense == 1 && cc.same_word >= 0.8);
+    const bool batch = units >= (int64_t)64 * sgrid * cw && units < INT32_MAX - (1 << 24);        // many short units: 16 per counter round trip
+    auto kern = ccs_kernel((p->flags & SMM_SYMMETRIC) != 0, dr, batch);
+    if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    LAUNCH(c, "smm_symbolic", kern, sgrid, cw * 64, lds, (int)p->m, n_slabs, rowlist, nrows, p->row_offset, cc.ws, cc.bm_words,
+           (int)p->b->rows, (int64_t)p->a->nnz, cc.guard_chunk, p->a->ptr, p->a->idx, (const int *)cc.cptr, (const unsigned short *)cc.stream,
+           (const int64_t *)p->d_ub_off, (unsigned short *)p->d_tmp, p->d_P, cnt, counter);
+    LAUNCH_CHECK();
+    return SMM_OK;
+}
+
+// The rows of C binned for the numeric phase into p->d_lists (5 x m), the bin sizes into p->n_bin.  prod (products per
+// row) fills the tiny bins; without it they stay empty.
+static int bin_c_rows(smm_ctx *c, smm_plan *p, const BinSpec &spec, const int64_t *prod)
+{
+    const int64_t m = p->m;
+    CHK(pool_get(c, (size_t)5 * m, &p->d_lists));
+    int *d_counts = (int *)((char *)c->d_flags + 320);
+    HIPCHK(hipMemsetAsync(d_counts, 0, 8 * sizeof(int), c->stream));
+    LAUNCH(c, "smm_bin_rows", smm_bin_rows<int>, std::min<int64_t>((m + 1023) / 1024, 2048), 1024, 0, (int)m, spec,
+           (const int *)p->d_rowcnt, p->d_lists, d_counts, prod ? c->tiny_max : 0, prod, prod ? p->a->ptr : nullptr);
+    HIPCHK(hipMemcpyAsync(p->n_bin, d_counts, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SMM_OK;
+}
+
+// Row work and bins: the capacities of the per-row ordered lists and their offsets (p->d_ub_off), the products per row,
+// the rows of every bin of the symbolic phase.
+static int sym_row_work(smm_ctx *c, smm_plan *p, SymRows &r)
+{
+    const smm_csr *a = p->a, *b = p->b;
+    const int64_t m = p->m;
+    const int sym = (p->flags & SMM_SYMMETRIC) ? 1 : 0;
+    PoolBuf<int64_t> ub(c);
+    CHK(r.prod.alloc((size_t)m));
+    CHK(ub.alloc((size_t)m));
+    CHK(pool_get(c, (size_t)m + 1, &p->d_ub_off));
     if (a->nnz <= 8 * m) {       // short rows on average: a row per lane instead of a row per wave; rows beyond 32 entries on a list
-        int *d_long = nullptr;
-        PCHK(pool_get(c, (size_t)(a->nnz / ROW_WORK_SHORT_MAX + 2), &d_long));      // [0]: count, [1 ...]: rows
-        hipError_t e = hipMemsetAsync(d_long, 0, sizeof(int), c->stream);
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "memset: %s", hipGetErrorString(e)); }
+        PoolBuf<int> d_long(c);
+        CHK(d_long.alloc((size_t)(a->nnz / ROW_WORK_SHORT_MAX + 2)));      // [0]: count, [1 ...]: rows
+        HIPCHK(hipMemsetAsync(d_long, 0, sizeof(int), c->stream));
         LAUNCH(c, "smm_row_work", smm_row_work_short, (int)std::min<int64_t>((m + 255) / 256, 65536), 256, 0, (int)m, (int)p->ncols,
-               p->row_offset, sym ? 1 : 0, a->ptr, a->idx, b->ptr, d_prod, d_ub, d_long + 1, d_long);
+               p->row_offset, sym, a->ptr, a->idx, b->ptr, r.prod.p, ub.p, d_long + 1, d_long.p);
         LAUNCH(c, "smm_row_work", smm_row_work_listed, c->n_cu * 8, 256, 0, (const int *)d_long, (const int *)(d_long + 1), (int)p->ncols,
-               p->row_offset, sym ? 1 : 0, a->ptr, a->idx, b->ptr, d_prod, d_ub);
-        pool_free(c, d_long);           // stream-ordered: only work queued behind these launches can get it
+               p->row_offset, sym, a->ptr, a->idx, b->ptr, r.prod.p, ub.p);
     } else
-        LAUNCH(c, "smm_row_work", smm_row_work, wgrid, 256, 0, (int)m, (int)p->ncols, p->row_offset, sym ? 1 : 0, a->ptr,
-               a->idx, b->ptr, d_prod, d_ub);
-    PCHK(scan_launch<int64_t>(c, m, d_ub, p->d_ub_off));
-    // The marker of the symbolic phase is a bitmap of B's columns (ncols/8 bytes per wave, in LDS when
-    // it fits): at 50 000 columns 24 waves fit a CU, at 1e6 columns one.  Rows with few products --
-    // known now -- therefore take an LDS hash set instead, wherever that is the smaller marker:
-    //   four classes: <= 256 / 512 / 1024 / 2048 products in 512 / 1024 / 2048 / 4096 slots (2 ... 16 KB per wave; round 4:
-    //   there used to be two, and a band of half-width 8 -- 289 products, 33 columns per row -- ran 8 waves per CU in the
-    //   4096-slot class: 11.6 ms; in the 1024-slot class 4.9 ms).
+        LAUNCH(c, "smm_row_work", smm_row_work, (int)std::min<int64_t>((m + 3) / 4, 16384), 256, 0, (int)m, (int)p->ncols, p->row_offset, sym,
+               a->ptr, a->idx, b->ptr, r.prod.p, ub.p);
+    CHK(scan_launch<int64_t>(c, m, ub, p->d_ub_off));
     const int bm_words = (int)((p->ncols + 31) / 32);
     const size_t bm_bytes = (size_t)(bm_words + 1) * sizeof(unsigned);      // + the guard word
-    const bool ldsbm = bm_bytes <= 128 * 1024;
-    const bool safe = (b->vflags & (CSR_HAS_EQUAL | CSR_UNSORTED)) != 0;
-    constexpr int NHC = 4;
-    constexpr int HS[NHC] = {512, 1024, 2048, 4096};
+    r.safe = (b->vflags & (CSR_HAS_EQUAL | CSR_UNSORTED)) != 0;
     int hmax[NHC];
-    for (int i = 0; i < NHC; ++i) hmax[i] = (!safe && bm_bytes > (size_t)HS[i] * 4) ? HS[i] / 2 : (i ? hmax[i - 1] : 0);
-    const int hmax1 = hmax[NHC - 1];
-    constexpr int SB_REST = NHC, SB_TINY = NHC + 1, SB_TINY2 = NHC + 2, SB_N = NHC + 3;      // bins of the symbolic phase: hash classes, bitmap, tiny (16 / 32 lanes per row)
-    // ... and TINY rows (<= 16 products from <= 16 entries of A, whatever B looks like) go four to a wave (smm_symbolic_tiny)
-    const int tiny_max = c->tiny_max;
-    const bool binned = hmax1 > 0 || tiny_max > 0;
-    int sbin[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    sbin[SB_REST] = (int)m;
-    int *d_slists = nullptr;
+    for (int i = 0; i < NHC; ++i) hmax[i] = (!r.safe && bm_bytes > (size_t)HS[i] * 4) ? HS[i] / 2 : (i ? hmax[i - 1] : 0);
+    r.hmax1 = hmax[NHC - 1];
+    r.binned = r.hmax1 > 0 || c->tiny_max > 0;
+    r.sbin[SB_REST] = (int)m;
     int *d_scounts = (int *)((char *)c->d_flags + 256);
-    if (binned) {
-        PCHK(pool_get(c, (size_t)SB_N * m, &d_slists));
-        hipError_t e = hipMemsetAsync(d_scounts, 0, 8 * sizeof(int), c->stream);
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "memset: %s", hipGetErrorString(e)); }
+    if (r.binned) {
+        CHK(r.slists.alloc((size_t)SB_N * m));
+        HIPCHK(hipMemsetAsync(d_scounts, 0, 8 * sizeof(int), c->stream));
         BinSpec spec{NHC, {hmax[0], hmax[1], hmax[2], hmax[3], 0, 0}, SB_TINY, SB_TINY2};
         LAUNCH(c, "smm_bin_rows", smm_bin_rows<int64_t>, std::min<int64_t>((m + 1023) / 1024, 2048), 1024, 0, (int)m, spec,
-               (const int64_t *)d_ub, d_slists, d_scounts, tiny_max, (const int64_t *)d_prod, a->ptr);
+               (const int64_t *)ub, r.slists.p, d_scounts, c->tiny_max, (const int64_t *)r.prod, a->ptr);
     }
-    int64_t total_ub = 0;
-    {
-        hipError_t e = hipMemcpyAsync(&total_ub, p->d_ub_off + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && binned)
-            e = hipMemcpyAsync(sbin, d_scounts, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "row work: %s", hipGetErrorString(e)); }
-    }
-    pool_free(c, d_ub);             // (d_prod lives on: the numeric binning at the end applies the same tiny-row predicate)
-    // Column slabs (round 3): B wider than one slab of the chunked stream (or than smm_ctx_tune_symbolic allows), sorted,
-    // without repeated columns, and most rows beyond the hash-set classes -> every (slab, row) is walked on its own.
-    {
-        const int ws_cap = c->sym_max_ws > 0 ? c->sym_max_ws : CCS_MAX_WS;
-        const bool wide = p->ncols > ws_cap && p->g.wc <= ws_cap && p->g.wc <= 32767;
-        const bool dominant = c->sym_max_ws > 0 || hmax1 == 0 || 2 * (int64_t)sbin[SB_REST] >= m;
-        if (c->sym_ccs && c->narrow_idx && wide && dominant && !safe && p->b_sorted && c->slab_mode != 2) {
-            if (d_slists) pool_free(c, d_slists);
-            pool_free(c, d_prod);
-            // tiles per slab: as many as fit the slab limit (<= 8), but not so many that the marker bitmap leaves fewer
-            // than 28 waves per CU (configs[4] share: 3 tiles = 60 000 columns = 21 waves 12.4 ms, 2 tiles = 31 waves 11.7 ms)
-            int tps = std::max(1, std::min(8, ws_cap / p->g.wc));
-            if (c->sym_max_ws == 0)
-                while (tps > 1 && (160 * 1024) / ((((tps * p->g.wc + 31) / 32) + WAVE) * 4) < 28) --tps;
-            p->tps = tps; p->ws = tps * p->g.wc; p->n_slabs = (p->g.nct + tps - 1) / tps;
-            p->list16 = true;
-            const int ns = p->n_slabs;
-            smm_csr::CcsCache cc{};
-            PCHK(ensure_ccs(c, b, p->ws, ns, &cc));
-            Geom gs; gs.nw = 1; gs.nct = ns; gs.wc = p->ws; gs.wf = p->ws; gs.n_ft = ns;
-            const int *sseg = nullptr;
-            PCHK(ensure_seg(c, b, gs, &sseg));
-            // capacities and offsets of the (slab, row) lists
-            int64_t *d_ubs = nullptr;
-            PCHK(pool_get(c, (size_t)ns * m, &d_ubs));
-            pool_free(c, p->d_ub_off); p->d_ub_off = nullptr;
-            PCHK(pool_get(c, (size_t)ns * m + 1, &p->d_ub_off));
-            LAUNCH(c, "smm_row_work", smm_ccs_row_work, wgrid, 256, 0, (int)m, ns, p->ws, (int)p->ncols, (int)b->rows, p->row_offset,
-                   sym ? 1 : 0, a->ptr, a->idx, sseg, d_ubs);
-            PCHK(scan_launch<int64_t>(c, (int64_t)ns * m, d_ubs, p->d_ub_off));
-            {
-                hipError_t e = hipMemcpyAsync(&total_ub, p->d_ub_off + (int64_t)ns * m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "slab row work: %s", hipGetErrorString(e)); }
-            }
-            pool_free(c, d_ubs);
-            p->total_cap = total_ub;
-            {
-                // (+ slack: a list longer than its capacity -- a defect the plan checker reports -- and a sub-run table that
-                // points past a list must still stay inside this allocation)
-                char *tmp = nullptr;
-                PCHK(pool_get(c, ((size_t)std::max<int64_t>(total_ub, 1) + LIST_SLACK) * 2, &tmp));
-                p->d_tmp = tmp;
-            }
-            PCHK(pool_get(c, (size_t)a->nnz * ns, &p->d_P));
-            PCHK(pool_get(c, (size_t)ns * m, &p->d_scnt));
-            PCHK(pool_get(c, (size_t)m, &p->d_rowcnt));
-            int *d_unitctr = (int *)((char *)c->d_flags + 208);
-            {
-                hipError_t e = hipMemsetAsync(d_unitctr, 0, sizeof(int), c->stream);
-                if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "memset: %s", hipGetErrorString(e)); }
-            }
-            {
-                const size_t wave_bytes = (size_t)(cc.bm_words + WAVE) * sizeof(unsigned);
-                int cw = 4, best = 0;
-                for (int cand : {4, 2, 1}) {
-                    const int waves = (int)std::min<size_t>(32, ((size_t)160 * 1024 / (cand * wave_bytes)) * cand);
-                    if (waves > best) { best = waves; cw = cand; }
-                }
-                const size_t lds = wave_bytes * cw;
-                const int64_t units = (int64_t)ns * m;
-                if (units >= INT32_MAX) { smm_plan_destroy(p); return fail(SMM_ERR_INVALID, "too many (slab, row) units"); }
-                const int sgrid = (int)std::min<int64_t>((units + cw - 1) / cw, (int64_t)c->n_cu * 8 * (4 / cw));
-                const bool dr = c->sym_dense == 2 || (c->sym_dense == 1 && cc.same_word >= 0.8);
-                const bool batch = units >= (int64_t)64 * sgrid * cw && units < INT32_MAX - (1 << 24);          // many short units: 16 per counter round trip
-                auto kern = ccs_kernel(sym, dr, batch);
-                if (lds > 64 * 1024) {
-                    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
-                }
-                LAUNCH(c, "smm_symbolic", kern, sgrid, cw * 64, lds, (int)m, ns, (const int *)nullptr, (const int *)nullptr, p->row_offset, cc.ws,
-                       cc.bm_words, (int)b->rows, (int64_t)a->nnz, cc.guard_chunk, a->ptr, a->idx, (const int *)cc.cptr,
-                       (const unsigned short *)cc.stream, (const int64_t *)p->d_ub_off, (unsigned short *)p->d_tmp, p->d_P, p->d_scnt, d_unitctr);
-            }
-            LAUNCH(c, "smm_slab_rowcnt", smm_slab_rowcnt, std::min<int64_t>((m + 255) / 256, 4096), 256, 0, (int)m, ns, (const int *)p->d_scnt,
-                   p->d_rowcnt);
-            PCHK(scan_launch<int>(c, m, p->d_rowcnt, p->d_cptr));
-            {
-                hipError_t e = hipMemcpyAsync(&p->nnz, p->d_cptr + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (e == hipSuccess) e = hipGetLastError();
-                if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "symbolic phase (slabs): %s", hipGetErrorString(e)); }
-            }
-            if (p->nnz > 0) {
-                // every non-empty row goes to the tile kernel (the hash kernels read one list per row)
-                PCHK(pool_get(c, (size_t)5 * m, &p->d_lists));
-                int *d_counts = (int *)((char *)c->d_flags + 320);
-                hipError_t e = hipMemsetAsync(d_counts, 0, 8 * sizeof(int), c->stream);
-                BinSpec nspec{2, {0, 0, 0, 0, 0, 0}, 3, 4};
-                LAUNCH(c, "smm_bin_rows", smm_bin_rows<int>, std::min<int64_t>((m + 1023) / 1024, 2048), 1024, 0, (int)m, nspec,
-                       (const int *)p->d_rowcnt, p->d_lists, d_counts);
-                if (e == hipSuccess) e = hipMemcpyAsync(p->n_bin, d_counts, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "row binning: %s", hipGetErrorString(e)); }
-            }
-            if (p->n_bin[2] > 0) {
-                if (flags & SMM_EXACT) {
-                    PCHK(ensure_seg(c, b, p->g, &p->seg));
-                    PCHK(ensure_loc(c, b, p->g, &p->loc));
-                } else {
-                    PCHK(ensure_pack(c, b, p->g, &p->pack));
-                }
-                PCHK(pool_get(c, (size_t)a->nnz, &p->d_dst0));
-                PCHK(pool_get(c, (size_t)a->nnz * p->g.nct, &p->d_runs2));
-                PCHK(pool_get(c, (size_t)m * p->g.nct, &p->d_tflag));
-                const int nd = p->n_bin[2];
-                LAUNCH(c, "smm_runs", smm_runs_slab, std::min<int64_t>((nd + 3) / 4, 65536), 256, 0, nd, (int)m, ns, tps, p->g.nct, p->g.wc,
-                       (int64_t)a->nnz, (const int *)(p->d_lists + 2 * m), a->ptr, (const int64_t *)p->d_ub_off, (const int *)p->d_scnt,
-                       (const unsigned *)p->d_P, (const unsigned short *)p->d_tmp, p->d_dst0, p->d_runs2, p->d_tflag, c->d_err);
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "smm_runs_slab: %s", hipGetErrorString(e)); }
-            }
-            if (c->check) PCHK(plan_check(c, p));
-            if (nnz_out) *nnz_out = p->nnz;
-            *plan = p;
-            return SMM_OK;
-        }
-    }
-    p->list16 = c->narrow_idx && p->ncols < 65535 && b->cols < 65535;
-    if (p->list16) PCHK(ensure_idx16(c, b));
-    p->total_cap = total_ub;
-    {
-        char *tmp = nullptr;
-        PCHK(pool_get(c, ((size_t)std::max<int64_t>(total_ub, 1) + std::max<size_t>(LIST_SLACK, (size_t)p->ncols)) * (p->list16 ? 2 : 4), &tmp));
-        p->d_tmp = tmp;
-    }
-    PCHK(pool_get(c, (size_t)a->nnz, &p->d_P));
-    PCHK(pool_get(c, (size_t)m, &p->d_rowcnt));
-    if (binned) {               // rows without products are in no bin: their count stays 0
-        hipError_t e = hipMemsetAsync(p->d_rowcnt, 0, (size_t)m * sizeof(int), c->stream);
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "memset: %s", hipGetErrorString(e)); }
-    }
+    HIPCHK(hipMemcpyAsync(&r.total_ub, p->d_ub_off + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (r.binned) HIPCHK(hipMemcpyAsync(r.sbin, d_scounts, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SMM_OK;
+}
 
+// Column slabs (round 3): B wider than one slab of the chunked stream (or than smm_ctx_tune_symbolic allows), sorted,
+// without repeated columns, and most rows beyond the hash-set classes -> every (slab, row) is walked on its own.
+static bool use_slab_walk(const smm_ctx *c, const smm_plan *p, const SymRows &r)
+{
+    const int ws_cap = c->sym_max_ws > 0 ? c->sym_max_ws : CCS_MAX_WS;
+    const bool wide = p->ncols > ws_cap && p->g.wc <= ws_cap && p->g.wc <= 32767;
+    const bool dominant = c->sym_max_ws > 0 || r.hmax1 == 0 || 2 * (int64_t)r.sbin[SB_REST] >= p->m;
+    return c->sym_ccs && c->narrow_idx && wide && dominant && !r.safe && p->b_sorted && c->slab_mode != 2;
+}
+
+// The column-slab walk: the (slab, row) lists over the chunked column stream, C's row pointer, every non-empty row binned
+// for the tile kernel, and the slab sub-run table (smm_runs_slab).
+static int sym_slab_walk(smm_ctx *c, smm_plan *p, SymRows &r)
+{
+    r.slists.reset();
+    r.prod.reset();
+    smm_csr *a = p->a, *b = p->b;
+    const int64_t m = p->m;
+    const int ws_cap = c->sym_max_ws > 0 ? c->sym_max_ws : CCS_MAX_WS;
+    // tiles per slab: as many as fit the slab limit (<= 8), but not so many that the marker bitmap leaves fewer
+    // than 28 waves per CU (configs[4] share: 3 tiles = 60 000 columns = 21 waves 12.4 ms, 2 tiles = 31 waves 11.7 ms)
+    int tps = std::max(1, std::min(8, ws_cap / p->g.wc));
+    if (c->sym_max_ws == 0)
+        while (tps > 1 && (160 * 1024) / ((((tps * p->g.wc + 31) / 32) + WAVE) * 4) < 28) --tps;
+    p->tps = tps; p->ws = tps * p->g.wc; p->n_slabs = (p->g.nct + tps - 1) / tps;
+    p->list16 = true;
+    const int ns = p->n_slabs;
+    smm_csr::CcsCache cc{};
+    CHK(ensure_ccs(c, b, p->ws, ns, &cc));
+    Geom gs; gs.nw = 1; gs.nct = ns; gs.wc = p->ws; gs.wf = p->ws; gs.n_ft = ns;
+    const int *sseg = nullptr;
+    CHK(ensure_seg(c, b, gs, &sseg));
+    // capacities and offsets of the (slab, row) lists
+    PoolBuf<int64_t> ubs(c);
+    CHK(ubs.alloc((size_t)ns * m));
+    pool_free(c, p->d_ub_off); p->d_ub_off = nullptr;
+    CHK(pool_get(c, (size_t)ns * m + 1, &p->d_ub_off));
+    LAUNCH(c, "smm_row_work", smm_ccs_row_work, (int)std::min<int64_t>((m + 3) / 4, 16384), 256, 0, (int)m, ns, p->ws, (int)p->ncols,
+           (int)b->rows, p->row_offset, (p->flags & SMM_SYMMETRIC) ? 1 : 0, a->ptr, a->idx, sseg, ubs.p);
+    CHK(scan_launch<int64_t>(c, (int64_t)ns * m, ubs, p->d_ub_off));
+    HIPCHK(hipMemcpyAsync(&p->total_cap, p->d_ub_off + (int64_t)ns * m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    ubs.reset();
+    // (+ slack: a list longer than its capacity -- a defect the plan checker reports -- and a sub-run table that
+    // points past a list must still stay inside this allocation)
+    CHK(pool_alloc(c, ((size_t)std::max<int64_t>(p->total_cap, 1) + LIST_SLACK) * 2, &p->d_tmp));
+    CHK(pool_get(c, (size_t)a->nnz * ns, &p->d_P));
+    CHK(pool_get(c, (size_t)ns * m, &p->d_scnt));
+    CHK(pool_get(c, (size_t)m, &p->d_rowcnt));
+    int *d_unitctr = (int *)((char *)c->d_flags + 208);
+    HIPCHK(hipMemsetAsync(d_unitctr, 0, sizeof(int), c->stream));
+    if ((int64_t)ns * m >= INT32_MAX) return fail(SMM_ERR_INVALID, "too many (slab, row) units");
+    CHK(launch_ccs(c, p, cc, (int64_t)ns * m, ns, nullptr, nullptr, p->d_scnt, d_unitctr));
+    LAUNCH(c, "smm_slab_rowcnt", smm_slab_rowcnt, std::min<int64_t>((m + 255) / 256, 4096), 256, 0, (int)m, ns, (const int *)p->d_scnt,
+           p->d_rowcnt);
+    CHK(scan_launch<int>(c, m, p->d_rowcnt, p->d_cptr));
+    HIPCHK(hipMemcpyAsync(&p->nnz, p->d_cptr + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    LAUNCH_CHECK();
+    // every non-empty row goes to the tile kernel (the hash kernels read one list per row)
+    if (p->nnz > 0) CHK(bin_c_rows(c, p, BinSpec{2, {0, 0, 0, 0, 0, 0}, 3, 4}, nullptr));
+    if (p->n_bin[2] > 0) {
+        if (p->flags & SMM_EXACT) {
+            CHK(ensure_seg(c, b, p->g, &p->seg));
+            CHK(ensure_loc(c, b, p->g, &p->loc));
+        } else {
+            CHK(ensure_pack(c, b, p->g, &p->pack));
+        }
+        CHK(pool_get(c, (size_t)a->nnz, &p->d_dst0));
+        CHK(pool_get(c, (size_t)a->nnz * p->g.nct, &p->d_runs2));
+        CHK(pool_get(c, (size_t)m * p->g.nct, &p->d_tflag));
+        const int nd = p->n_bin[2];
+        LAUNCH(c, "smm_runs", smm_runs_slab, std::min<int64_t>((nd + 3) / 4, 65536), 256, 0, nd, (int)m, ns, tps, p->g.nct, p->g.wc,
+               (int64_t)a->nnz, (const int *)(p->d_lists + 2 * m), a->ptr, (const int64_t *)p->d_ub_off, (const int *)p->d_scnt,
+               (const unsigned *)p->d_P, (const unsigned short *)p->d_tmp, p->d_dst0, p->d_runs2, p->d_tflag, c->d_err);
+        LAUNCH_CHECK();
+    }
+    return SMM_OK;
+}
+
+// The row walk: tiny rows, the hash classes, then the bitmap walk (or the walk over the chunked column stream) for the
+// rest; C's row pointer.
+static int sym_row_walk(smm_ctx *c, smm_plan *p, SymRows &r)
+{
+    smm_csr *a = p->a, *b = p->b;
+    const int64_t m = p->m;
+    const bool sym = (p->flags & SMM_SYMMETRIC) != 0;
+    const bool safe = r.safe;
+    p->list16 = c->narrow_idx && p->ncols < 65535 && b->cols < 65535;
+    if (p->list16) CHK(ensure_idx16(c, b));
+    p->total_cap = r.total_ub;
+    CHK(pool_alloc(c, ((size_t)std::max<int64_t>(r.total_ub, 1) + std::max<size_t>(LIST_SLACK, (size_t)p->ncols)) * (p->list16 ? 2 : 4),
+                   &p->d_tmp));
+    CHK(pool_get(c, (size_t)a->nnz, &p->d_P));
+    CHK(pool_get(c, (size_t)m, &p->d_rowcnt));
+    if (r.binned) HIPCHK(hipMemsetAsync(p->d_rowcnt, 0, (size_t)m * sizeof(int), c->stream));   // rows without products are in no bin: their count stays 0
     // the kernels hand rows out through these counters (one per launch)
     int *d_rowctr = (int *)((char *)c->d_flags + 288);
-    {
-        hipError_t e = hipMemsetAsync(d_rowctr, 0, 8 * sizeof(int), c->stream);
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "memset: %s", hipGetErrorString(e)); }
-    }
+    HIPCHK(hipMemsetAsync(d_rowctr, 0, 8 * sizeof(int), c->stream));
+    int *d_scounts = (int *)((char *)c->d_flags + 256);
+    const int *d_slists = r.slists;
     // tiny rows: four (<= 16 products) or two (<= 32) to a wave, no marker at all
     for (int tc = 0; tc < 2; ++tc) {
         const int bin = tc == 0 ? SB_TINY : SB_TINY2;
-        const int nt = sbin[bin];
+        const int nt = r.sbin[bin];
         if (nt == 0) continue;
         const int per_wg = tc == 0 ? 16 : 8;                         // rows per 256-thread workgroup
         const int tgrid = (int)std::min<int64_t>(((int64_t)nt + per_wg - 1) / per_wg, (int64_t)c->n_cu * 32);
@@ -1937,131 +1940,129 @@ extern "C" int smm_spgemm_symbolic(smm_ctx *c, smm_csr *a, smm_csr *b, int flags
         else           { if (sym) { TINY_G_CASE(true, int) } else { TINY_G_CASE(false, int) } }
 #undef TINY_G_CASE
 #undef TINY_CASE
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "smm_symbolic_tiny: %s", hipGetErrorString(e)); }
+        LAUNCH_CHECK();
     }
     // hash classes: one wave per row, four rows per workgroup
     for (int cls = 0; cls < NHC; ++cls) {
-        if (hmax1 == 0 || sbin[cls] == 0) continue;
+        if (r.hmax1 == 0 || r.sbin[cls] == 0) continue;
         const int hs = HS[cls];
-        const int hgrid = (int)std::min<int64_t>((sbin[cls] + 3) / 4, (int64_t)c->n_cu * 16);
-        if (sym) PCHK((launch_symbolic_t<true, false, MARK_LDS_HASH>(c, p, hs, nullptr, hgrid, 4, d_slists + (size_t)cls * m, d_scounts + cls, d_rowctr + cls)));
-        else     PCHK((launch_symbolic_t<false, false, MARK_LDS_HASH>(c, p, hs, nullptr, hgrid, 4, d_slists + (size_t)cls * m, d_scounts + cls, d_rowctr + cls)));
+        const int hgrid = (int)std::min<int64_t>((r.sbin[cls] + 3) / 4, (int64_t)c->n_cu * 16);
+        if (sym) CHK((launch_symbolic_t<true, false, MARK_LDS_HASH>(c, p, hs, nullptr, hgrid, 4, d_slists + (size_t)cls * m, d_scounts + cls, d_rowctr + cls)));
+        else     CHK((launch_symbolic_t<false, false, MARK_LDS_HASH>(c, p, hs, nullptr, hgrid, 4, d_slists + (size_t)cls * m, d_scounts + cls, d_rowctr + cls)));
     }
     // bitmap kernels for the rest: one wave per row; waves per workgroup are chosen so that as many
     // waves as possible fit a CU's 160 KB
-    const int64_t nbm = binned ? sbin[SB_REST] : m;
-    const int *bm_rows = binned ? d_slists + (size_t)SB_REST * m : nullptr;
-    const int *bm_count = binned ? d_scounts + SB_REST : nullptr;
+    const int bm_words = (int)((p->ncols + 31) / 32);
+    const size_t bm_bytes = (size_t)(bm_words + 1) * sizeof(unsigned);      // + the guard word
+    const bool ldsbm = bm_bytes <= 128 * 1024;
+    const int64_t nbm = r.binned ? r.sbin[SB_REST] : m;
+    const int *bm_rows = r.binned ? d_slists + (size_t)SB_REST * m : nullptr;
+    const int *bm_count = r.binned ? d_scounts + SB_REST : nullptr;
     int wpb = 4, waves_per_cu = 8;
-    if (ldsbm) {
-        int best = 0;
-        for (int cand : {4, 2, 1}) {
-            const int waves = (int)std::min<size_t>(32, ((size_t)160 * 1024 / (cand * bm_bytes)) * cand);
-            if (waves > best) { best = waves; wpb = cand; }
-        }
-        waves_per_cu = best;
-    }
+    if (ldsbm) waves_per_cu = most_waves_per_cu(bm_bytes, &wpb);
     // few waves per CU (wide bitmaps): a round is one memory round trip whatever it carries -> 32 loads in flight
     const bool deep = !safe && waves_per_cu <= 8;
-    unsigned *gbm = nullptr;
+    PoolBuf<unsigned> gbm(c);
     // Round 3: sorted B without repeated columns and 16-bit lists -> the walk over the chunk-padded stream
     const bool use_ccs = c->sym_ccs && p->list16 && !safe && p->ncols <= CCS_MAX_WS && nbm > 0;
     if (use_ccs) {
         smm_csr::CcsCache cc{};
-        PCHK(ensure_ccs(c, b, (int)p->ncols, 1, &cc));
-        const size_t wave_bytes = (size_t)(cc.bm_words + WAVE) * sizeof(unsigned);
-        int cw = 4, best = 0;
-        for (int cand : {4, 2, 1}) {
-            const int waves = (int)std::min<size_t>(32, ((size_t)160 * 1024 / (cand * wave_bytes)) * cand);
-            if (waves > best) { best = waves; cw = cand; }
-        }
-        const size_t lds = wave_bytes * cw;
-        const int sgrid = (int)std::min<int64_t>((nbm + cw - 1) / cw, (int64_t)c->n_cu * 8 * (4 / cw));
-        const bool dr = c->sym_dense == 2 || (c->sym_dense == 1 && cc.same_word >= 0.8);
-        const bool batch = nbm >= (int64_t)64 * sgrid * cw && nbm < INT32_MAX - (1 << 24);                // many short rows: 16 per counter round trip
-        auto kern = ccs_kernel(sym, dr, batch);
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
-        }
-        LAUNCH(c, "smm_symbolic", kern, sgrid, cw * 64, lds, (int)m, 1, bm_rows, bm_count, p->row_offset, cc.ws, cc.bm_words, (int)b->rows,
-               (int64_t)a->nnz, cc.guard_chunk, a->ptr, a->idx, (const int *)cc.cptr, (const unsigned short *)cc.stream,
-               (const int64_t *)p->d_ub_off, (unsigned short *)p->d_tmp, p->d_P, p->d_rowcnt, d_rowctr + SB_REST);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "smm_symbolic_ccs: %s", hipGetErrorString(e)); }
+        CHK(ensure_ccs(c, b, (int)p->ncols, 1, &cc));
+        CHK(launch_ccs(c, p, cc, nbm, 1, bm_rows, bm_count, p->d_rowcnt, d_rowctr + SB_REST));
     } else if (nbm > 0) {
         int sgrid = (int)std::min<int64_t>((nbm + wpb - 1) / wpb, (int64_t)c->n_cu * 8 * (4 / wpb));
-        if (!ldsbm) PCHK(pool_get(c, (size_t)sgrid * wpb * (bm_words + 1), &gbm));
+        if (!ldsbm) CHK(gbm.alloc((size_t)sgrid * wpb * (bm_words + 1)));
         const int mark = ldsbm ? MARK_LDS_BITMAP : MARK_GLOBAL_BITMAP;
         // (round 4) many short rows: 16 per counter round trip (one atomic per row on one word is 11 ns of L2 time each)
         const int rbatch = nbm >= (int64_t)64 * sgrid * wpb && nbm < INT32_MAX - (1 << 24) ? 16 : 1;
-#define SYM_CASE(S, F, L) if (sym == S && safe == F && mark == L && !deep) PCHK((launch_symbolic_t<S, F, L>(c, p, bm_words, gbm, sgrid, wpb, bm_rows, bm_count, d_rowctr + SB_REST, rbatch)));
+#define SYM_CASE(S, F, L) if (sym == S && safe == F && mark == L && !deep) CHK((launch_symbolic_t<S, F, L>(c, p, bm_words, gbm, sgrid, wpb, bm_rows, bm_count, d_rowctr + SB_REST, rbatch)));
         SYM_CASE(false, false, MARK_LDS_BITMAP) SYM_CASE(false, true, MARK_LDS_BITMAP) SYM_CASE(true, false, MARK_LDS_BITMAP)
         SYM_CASE(true, true, MARK_LDS_BITMAP) SYM_CASE(false, false, MARK_GLOBAL_BITMAP) SYM_CASE(false, true, MARK_GLOBAL_BITMAP)
         SYM_CASE(true, false, MARK_GLOBAL_BITMAP) SYM_CASE(true, true, MARK_GLOBAL_BITMAP)
-#define SYM_DEEP(S, L) if (sym == S && mark == L && deep) PCHK((launch_symbolic_t<S, false, L, 32>(c, p, bm_words, gbm, sgrid, wpb, bm_rows, bm_count, d_rowctr + SB_REST, rbatch)));
+#define SYM_DEEP(S, L) if (sym == S && mark == L && deep) CHK((launch_symbolic_t<S, false, L, 32>(c, p, bm_words, gbm, sgrid, wpb, bm_rows, bm_count, d_rowctr + SB_REST, rbatch)));
         SYM_DEEP(false, MARK_LDS_BITMAP) SYM_DEEP(true, MARK_LDS_BITMAP) SYM_DEEP(false, MARK_GLOBAL_BITMAP) SYM_DEEP(true, MARK_GLOBAL_BITMAP)
 #undef SYM_DEEP
 #undef SYM_CASE
     }
-    PCHK(scan_launch<int>(c, m, p->d_rowcnt, p->d_cptr));
-    {
-        hipError_t e = hipMemcpyAsync(&p->nnz, p->d_cptr + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "symbolic phase: %s", hipGetErrorString(e)); }
+    CHK(scan_launch<int>(c, m, p->d_rowcnt, p->d_cptr));
+    HIPCHK(hipMemcpyAsync(&p->nnz, p->d_cptr + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    LAUNCH_CHECK();
+    gbm.reset();
+    r.slists.reset();
+    return SMM_OK;
+}
+
+// The rows of C binned (few nonzeros -> LDS hash kernels, the rest -> dense LDS tiles) and, for the dense-tile rows, the
+// slab path's choice, B's tile index or packed payload, and the sub-run table (smm_runs).
+static int sym_runs(smm_ctx *c, smm_plan *p, SymRows &r)
+{
+    smm_csr *a = p->a, *b = p->b;
+    const int64_t m = p->m;
+    if (p->nnz > 0) CHK(bin_c_rows(c, p, BinSpec{2, {c->hash_small, c->hash_medium, 0, 0, 0, 0}, 3, 4}, r.prod));
+    r.prod.reset();
+    if (!p->b_sorted || p->n_bin[2] == 0) return SMM_OK;
+    const double est_products = (double)a->nnz * ((double)b->nnz / (double)std::max<int64_t>(b->rows, 1)) * ((double)p->n_bin[2] / (double)m);
+    p->use_slab = slab_geometry(c, b, p->ncols, &p->sg) &&
+                  slab_pays(c, a, p->sg, (double)p->n_bin[2] * (double)p->ncols, est_products, (double)p->nnz,
+                            (double)b->nnz / (double)std::max<int64_t>(b->rows, 1), (double)p->ncols);
+    if (p->use_slab) CHK(ensure_slab(c, b, p->sg, &p->slab));
+    // (chosen by the heuristic, not forced: the tile kernel's index is built as well, so that the numeric
+    // phase can fall back to it when the slab path's dense scratch does not fit)
+    if (p->use_slab && c->slab_mode == 2) { /* forced: slab only */ }
+    else if (p->flags & SMM_EXACT) {
+        CHK(ensure_seg(c, b, p->g, &p->seg));
+        CHK(ensure_loc(c, b, p->g, &p->loc));
+    } else {
+        CHK(ensure_pack(c, b, p->g, &p->pack));
     }
-    if (gbm) pool_free(c, gbm);
-    if (d_slists) pool_free(c, d_slists);
-    if (p->nnz <= 0) pool_free(c, d_prod);
-    if (p->nnz > 0) {
-        // bin the rows of C: few nonzeros -> LDS hash kernels, the rest -> dense LDS tiles
-        PCHK(pool_get(c, (size_t)5 * m, &p->d_lists));
-        int *d_counts = (int *)((char *)c->d_flags + 320);
-        hipError_t e = hipMemsetAsync(d_counts, 0, 8 * sizeof(int), c->stream);
-        BinSpec nspec{2, {c->hash_small, c->hash_medium, 0, 0, 0, 0}, 3, 4};
-        LAUNCH(c, "smm_bin_rows", smm_bin_rows<int>, std::min<int64_t>((m + 1023) / 1024, 2048), 1024, 0, (int)m, nspec,
-               (const int *)p->d_rowcnt, p->d_lists, d_counts, tiny_max, (const int64_t *)d_prod, a->ptr);
-        if (e == hipSuccess) e = hipMemcpyAsync(p->n_bin, d_counts, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        pool_free(c, d_prod);
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "row binning: %s", hipGetErrorString(e)); }
-    }
-    if (p->b_sorted && p->n_bin[2] > 0) {
-        const double est_products = (double)a->nnz * ((double)b->nnz / (double)std::max<int64_t>(b->rows, 1)) *
-                                    ((double)p->n_bin[2] / (double)m);
-        p->use_slab = slab_geometry(c, b, p->ncols, &p->sg) &&
-                      slab_pays(c, a, p->sg, (double)p->n_bin[2] * (double)p->ncols, est_products, (double)p->nnz,
-                                (double)b->nnz / (double)std::max<int64_t>(b->rows, 1), (double)p->ncols);
-        if (p->use_slab) PCHK(ensure_slab(c, b, p->sg, &p->slab));
-        // (chosen by the heuristic, not forced: the tile kernel's index is built as well, so that the numeric
-        // phase can fall back to it when the slab path's dense scratch does not fit)
-        if (p->use_slab && c->slab_mode == 2) { /* forced: slab only */ }
-        else if (flags & SMM_EXACT) {
-            PCHK(ensure_seg(c, b, p->g, &p->seg));
-            PCHK(ensure_loc(c, b, p->g, &p->loc));
+    CHK(pool_get(c, (size_t)a->nnz * (p->g.nct + 1), &p->d_runs));
+    CHK(pool_get(c, (size_t)m, &p->d_tail));
+    const int nd = p->n_bin[2];
+    const int rgrid = (int)std::min<int64_t>((nd + 3) / 4, 65536);
+    const int tail_min = (p->flags & SMM_EXACT) ? TAIL_MIN_EXACT : TAIL_MIN_DEFAULT;
+    if (p->list16)
+        LAUNCH(c, "smm_runs", smm_runs<unsigned short>, rgrid, 256, 0, nd, p->g.nct, p->g.wc, (const int *)(p->d_lists + 2 * m), a->ptr,
+               p->d_ub_off, p->d_rowcnt, p->d_P, (const unsigned short *)p->d_tmp, p->d_runs, p->d_tail, c->d_err, tail_min);
+    else
+        LAUNCH(c, "smm_runs", smm_runs<int>, rgrid, 256, 0, nd, p->g.nct, p->g.wc, (const int *)(p->d_lists + 2 * m), a->ptr,
+               p->d_ub_off, p->d_rowcnt, p->d_P, (const int *)p->d_tmp, p->d_runs, p->d_tail, c->d_err, tail_min);
+    LAUNCH_CHECK();
+    return SMM_OK;
+}
+
+extern "C" int smm_spgemm_symbolic(smm_ctx *c, smm_csr *a, smm_csr *b, int flags, int64_t a_row_offset,
+                                   smm_plan **plan, int64_t *nnz_out)
+{
+    if (!plan) return fail(SMM_ERR_INVALID, "plan is NULL");
+    *plan = nullptr;
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(check_pair(c, a, b));
+    if (a_row_offset < 0) return fail(SMM_ERR_INVALID, "negative a_row_offset");
+    CHK(exact_guard(c, flags));
+    PlanPtr p(new smm_plan());
+    p->ctx = c; p->a = a; p->b = b; p->flags = flags; p->row_offset = a_row_offset;
+    p->m = a->rows; p->ncols = b->cols;
+    p->b_sorted = !(b->vflags & CSR_UNSORTED);
+    p->g = make_geom(c, p->ncols, b, (flags & SMM_EXACT) != 0);
+    CHK(pool_get(c, (size_t)p->m + 1, &p->d_cptr));
+    if (p->m == 0 || a->nnz == 0 || b->nnz == 0 || p->ncols == 0) {
+        // sparse_sparse_sparse.cpp:181-185: zero operand -> rowPtr of zeros only
+        HIPCHK(hipMemsetAsync(p->d_cptr, 0, (p->m + 1) * sizeof(int64_t), c->stream));
+    } else {
+        SymRows r(c);
+        CHK(sym_row_work(c, p.get(), r));
+        if (use_slab_walk(c, p.get(), r)) {
+            CHK(sym_slab_walk(c, p.get(), r));
         } else {
-            PCHK(ensure_pack(c, b, p->g, &p->pack));
+            CHK(sym_row_walk(c, p.get(), r));
+            CHK(sym_runs(c, p.get(), r));
         }
-        PCHK(pool_get(c, (size_t)a->nnz * (p->g.nct + 1), &p->d_runs));
-        PCHK(pool_get(c, (size_t)m, &p->d_tail));
-        const int nd = p->n_bin[2];
-        const int rgrid = (int)std::min<int64_t>((nd + 3) / 4, 65536);
-        const int tail_min = (flags & SMM_EXACT) ? TAIL_MIN_EXACT : TAIL_MIN_DEFAULT;
-        if (p->list16)
-            LAUNCH(c, "smm_runs", smm_runs<unsigned short>, rgrid, 256, 0, nd, p->g.nct, p->g.wc, (const int *)(p->d_lists + 2 * m), a->ptr,
-                   p->d_ub_off, p->d_rowcnt, p->d_P, (const unsigned short *)p->d_tmp, p->d_runs, p->d_tail, c->d_err, tail_min);
-        else
-            LAUNCH(c, "smm_runs", smm_runs<int>, rgrid, 256, 0, nd, p->g.nct, p->g.wc, (const int *)(p->d_lists + 2 * m), a->ptr,
-                   p->d_ub_off, p->d_rowcnt, p->d_P, (const int *)p->d_tmp, p->d_runs, p->d_tail, c->d_err, tail_min);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { smm_plan_destroy(p); return fail(SMM_ERR_HIP, "smm_runs: %s", hipGetErrorString(e)); }
+        if (c->check) CHK(plan_check(c, p.get()));
     }
-    if (c->check) PCHK(plan_check(c, p));
-#undef PCHK
     if (nnz_out) *nnz_out = p->nnz;
-    *plan = p;
+    *plan = p.release();
     return SMM_OK;
 }
 
@@ -2140,23 +2141,18 @@ extern "C" int smm_spgemm_numeric(smm_ctx *c, smm_plan *p, int64_t *d_c_indptr, 
         A.runs2 = p->d_runs2; A.tflag = p->d_tflag; A.n_slabs = p->n_slabs; A.tps = p->tps; A.ws = p->ws; A.mtot = (int)m; A.nnzA = p->a->nnz;
         if (p->use_slab) {
             // values in column order into a dense scratch (one row per row of the bin), then the emission
-            double *scratch = nullptr;
-            int rc = pool_get(c, (size_t)nd * (size_t)p->ncols, &scratch);
+            PoolBuf<double> scratch(c);
+            const int rc = scratch.alloc((size_t)nd * (size_t)p->ncols);
             if (rc != SMM_OK) {
                 if (!(p->pack.pay || p->seg)) return rc;         // slab path forced: no tile index to fall back to
-                CHK(launch_numeric<OUT_SPARSE>(c, A, sym, p->g.nw, exact));
-                return SMM_OK;
+                return launch_numeric<OUT_SPARSE>(c, A, sym, p->g.nw, exact);
             }
-            rc = launch_slab<true>(c, p->a, p->b, p->slab, p->sg.rw, nd, dense_rows, sym, p->row_offset, scratch, p->ncols);
-            if (rc == SMM_OK) {
-                A.c_dense = scratch; A.ldc = p->ncols;
-                A.dummy_idx = (const int *)((const char *)c->d_flags + 64);
-                A.dummy_val = (const double *)((const char *)c->d_flags + 128);
-                A.err = c->d_err;
-                rc = sym ? launch_numeric_t<OUT_SPARSE, true, 16, false, true>(c, A) : launch_numeric_t<OUT_SPARSE, false, 16, false, true>(c, A);
-            }
-            pool_free(c, scratch);          // stream-ordered: only work queued behind the emission can get it
-            return rc;
+            CHK(launch_slab<true>(c, p->a, p->b, p->slab, p->sg.rw, nd, dense_rows, sym, p->row_offset, scratch, p->ncols));
+            A.c_dense = scratch; A.ldc = p->ncols;
+            A.dummy_idx = (const int *)((const char *)c->d_flags + 64);
+            A.dummy_val = (const double *)((const char *)c->d_flags + 128);
+            A.err = c->d_err;
+            return sym ? launch_numeric_t<OUT_SPARSE, true, 16, false, true>(c, A) : launch_numeric_t<OUT_SPARSE, false, 16, false, true>(c, A);
         }
         CHK(launch_numeric<OUT_SPARSE>(c, A, sym, p->g.nw, exact));
     } else {
@@ -2165,9 +2161,9 @@ extern "C" int smm_spgemm_numeric(smm_ctx *c, smm_plan *p, int64_t *d_c_indptr, 
                p->list16 ? 1 : 0, d_c_indices);
         LAUNCH_CHECK();
         const int grid = (int)std::min<int64_t>((nd + 3) / 4, (int64_t)c->n_cu * 2);
-        int *slot = nullptr;
+        PoolBuf<int> slot(c);
         // SMM_EXACT: the ordered variant (read-modify-write in the reference's order instead of atomics; a second map per wave)
-        CHK(pool_get(c, (size_t)grid * 4 * (size_t)p->ncols * (exact ? 2 : 1), &slot));
+        CHK(slot.alloc((size_t)grid * 4 * (size_t)p->ncols * (exact ? 2 : 1)));
 #define GEN_CASE(S, O)                                                                                                        \
         if (sym == S && exact == O)                                                                                           \
             LAUNCH(c, "smm_numeric_general", (smm_numeric_general<S, O>), grid, 256, 0, nd, (int)p->ncols, p->row_offset,      \
@@ -2177,7 +2173,6 @@ extern "C" int smm_spgemm_numeric(smm_ctx *c, smm_plan *p, int64_t *d_c_indptr, 
 #undef GEN_CASE
         LAUNCH_CHECK();
         HIPCHK(hipStreamSynchronize(c->stream));
-        pool_free(c, slot);
     }
     return SMM_OK;
 }
@@ -2206,20 +2201,21 @@ static int numeric_host(smm_ctx *c, smm_plan *p, int64_t *c_indptr, void *c_indi
     if (!c || !p || !c_indptr) return fail(SMM_ERR_INVALID, "NULL argument");
     CTX_LOCK(c);
     HIPCHK(hipSetDevice(c->device));
-    int64_t *dp = nullptr; int *di = nullptr; double *dv = nullptr;
+    PoolBuf<int64_t> dp(c); PoolBuf<int> di(c); PoolBuf<double> dv(c);
     const int64_t nnz = p->nnz;
-    CHK(pool_get(c, (size_t)p->m + 1, &dp));
-    int rc = pool_get(c, (size_t)std::max<int64_t>(nnz, 1), &di);
-    if (rc == SMM_OK) rc = pool_get(c, (size_t)std::max<int64_t>(nnz, 1), &dv);
-    if (rc == SMM_OK) rc = smm_spgemm_numeric(c, p, dp, di, dv);
-    if (rc == SMM_OK && nnz > 0 && (!c_indices || !c_data)) rc = fail(SMM_ERR_INVALID, "output arrays are NULL but nnz > 0");
-    if (rc == SMM_OK) rc = download(c, c_indptr, dp, (size_t)(p->m + 1) * sizeof(int64_t));
-    if (rc == SMM_OK && nnz > 0) rc = download(c, c_indices, di, (size_t)nnz * sizeof(int), wide);
-    if (rc == SMM_OK && nnz > 0) rc = download(c, c_data, dv, (size_t)nnz * sizeof(double));
+    CHK(dp.alloc((size_t)p->m + 1));
+    CHK(di.alloc((size_t)std::max<int64_t>(nnz, 1)));
+    CHK(dv.alloc((size_t)std::max<int64_t>(nnz, 1)));
+    CHK(smm_spgemm_numeric(c, p, dp, di, dv));
+    if (nnz > 0 && (!c_indices || !c_data)) return fail(SMM_ERR_INVALID, "output arrays are NULL but nnz > 0");
+    CHK(download(c, c_indptr, dp, (size_t)(p->m + 1) * sizeof(int64_t)));
+    if (nnz > 0) {
+        CHK(download(c, c_indices, di, (size_t)nnz * sizeof(int), wide));
+        CHK(download(c, c_data, dv, (size_t)nnz * sizeof(double)));
+    }
     (void)hipStreamSynchronize(c->stream);
-    pool_free(c, dp); pool_free(c, di); pool_free(c, dv);
-    if (rc == SMM_OK) rc = take_plan_error(c, "smm_spgemm_numeric");       // what the kernels' clamps recorded, if anything
-    return rc;
+    dp.reset(); di.reset(); dv.reset();
+    return take_plan_error(c, "smm_spgemm_numeric");       // what the kernels' clamps recorded, if anything
 }
 
 // ------------------------------------------------------------------------------ CSR x CSR -> dense
@@ -2266,17 +2262,16 @@ static int dense_into(smm_ctx *c, smm_csr *a, smm_csr *b, int flags, int64_t row
     } else {
         const bool ordered = (flags & SMM_EXACT) != 0;
         const int grid = (int)std::min<int64_t>((m + 3) / 4, ordered ? (int64_t)c->n_cu * 2 : 65536);
-        int *owner = nullptr;
-        if (ordered) CHK(pool_get(c, (size_t)grid * 4 * (size_t)n, &owner));
+        PoolBuf<int> owner(c);
+        if (ordered) CHK(owner.alloc((size_t)grid * 4 * (size_t)n));
 #define GEN_CASE(S, O)                                                                                                        \
         if (sym == S && ordered == O)                                                                                         \
             LAUNCH(c, "smm_dense_general", (smm_dense_general<S, O>), grid, 256, 0, (int)m, (int)n, row_offset, a->ptr, a->idx, \
                    a->val, b->ptr, b->idx, b->val, d_c, ldc, owner);
         GEN_CASE(false, false) GEN_CASE(true, false) GEN_CASE(false, true) GEN_CASE(true, true)
 #undef GEN_CASE
-        hipError_t e = hipGetLastError();
-        if (owner) { if (e == hipSuccess) e = hipStreamSynchronize(c->stream); pool_free(c, owner); }
-        if (e != hipSuccess) return fail(SMM_ERR_HIP, "smm_dense_general: %s", hipGetErrorString(e));
+        LAUNCH_CHECK();
+        if (owner) HIPCHK(hipStreamSynchronize(c->stream));
     }
     return SMM_OK;
 }
@@ -2316,13 +2311,12 @@ extern "C" int smm_spgemm_dense_host(smm_ctx *c, smm_csr *a, smm_csr *b, int fla
     const int64_t total = a->rows * b->cols;
     if (total == 0) return SMM_OK;
     if (!out) return fail(SMM_ERR_INVALID, "c is NULL");
-    double *d = nullptr;
-    CHK(pool_get(c, (size_t)total, &d));
-    int rc = smm_spgemm_dense(c, a, b, flags, a_row_offset, d);
-    if (rc == SMM_OK) rc = download(c, out, d, (size_t)total * sizeof(double));
+    PoolBuf<double> d(c);
+    CHK(d.alloc((size_t)total));
+    CHK(smm_spgemm_dense(c, a, b, flags, a_row_offset, d));
+    CHK(download(c, out, d, (size_t)total * sizeof(double)));
     (void)hipStreamSynchronize(c->stream);
-    pool_free(c, d);
-    return rc;
+    return SMM_OK;
 }
 
 // ------------------------------------------------------------------------------ CSR mirror epilogue
@@ -2336,27 +2330,22 @@ extern "C" int smm_csr_mirror_symbolic(smm_ctx *c, int64_t n, const int64_t *d_i
     HIPCHK(hipSetDevice(c->device));
     *nnz_full = 0;
     if (n == 0) { HIPCHK(hipMemsetAsync(d_full_indptr, 0, sizeof(int64_t), c->stream)); return SMM_OK; }
-    int *mcnt = nullptr; int64_t *flen = nullptr;
-    CHK(pool_get(c, (size_t)n + 1, &mcnt));                       // [n] = longest mirrored segment
-    int rc = pool_get(c, (size_t)n, &flen);
-    if (rc != SMM_OK) { pool_free(c, mcnt); return rc; }
-    hipError_t e = hipMemsetAsync(mcnt, 0, ((size_t)n + 1) * sizeof(int), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_flags, 0, sizeof(unsigned), c->stream);
+    PoolBuf<int> mcnt(c);
+    PoolBuf<int64_t> flen(c);
+    CHK(mcnt.alloc((size_t)n + 1));                       // [n] = longest mirrored segment
+    CHK(flen.alloc((size_t)n));
+    HIPCHK(hipMemsetAsync(mcnt, 0, ((size_t)n + 1) * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_flags, 0, sizeof(unsigned), c->stream));
     const int grid = (int)std::min<int64_t>((n + 3) / 4, 16384);
     LAUNCH(c, "smm_mirror_count", smm_mirror_count, grid, 256, 0, (int)n, d_indptr, d_indices, mcnt, c->d_flags);
     LAUNCH(c, "smm_mirror_rowlen", smm_mirror_rowlen, std::min<int64_t>((n + 255) / 256, 4096), 256, 0, (int)n, d_indptr, (const int *)mcnt,
            flen, mcnt + n);
-    rc = scan_launch<int64_t>(c, n, flen, d_full_indptr);
+    CHK(scan_launch<int64_t>(c, n, flen, d_full_indptr));
     unsigned bad = 0; int maxseg = 0;
-    if (rc == SMM_OK) {
-        if (e == hipSuccess) e = hipMemcpyAsync(nnz_full, d_full_indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, c->d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&maxseg, mcnt + n, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(SMM_ERR_HIP, "CSR mirror: %s", hipGetErrorString(e));
-    }
-    pool_free(c, mcnt); pool_free(c, flen);
-    if (rc != SMM_OK) return rc;
+    HIPCHK(hipMemcpyAsync(nnz_full, d_full_indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&bad, c->d_flags, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&maxseg, mcnt + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     if (bad) return fail(SMM_ERR_INVALID, "CSR mirror: the input holds entries left of the diagonal or outside the n x n square");
     (void)maxseg;                 // (any length: segments beyond the LDS sort are placed by rank, smm_mirror_rank)
     return SMM_OK;
@@ -2370,41 +2359,35 @@ extern "C" int smm_csr_mirror_fill(smm_ctx *c, int64_t n, const int64_t *d_indpt
     CTX_LOCK(c);
     HIPCHK(hipSetDevice(c->device));
     if (!d_indices || !d_data || !d_full_indices || !d_full_data) return fail(SMM_ERR_INVALID, "NULL CSR array");
-    int *mcnt = nullptr, *cursor = nullptr;
-    CHK(pool_get(c, (size_t)n, &mcnt));
-    int rc = pool_get(c, (size_t)n, &cursor);
-    if (rc != SMM_OK) { pool_free(c, mcnt); return rc; }
-    hipError_t e = hipMemsetAsync(mcnt, 0, (size_t)n * sizeof(int), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, (size_t)n * sizeof(int), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_flags, 0, sizeof(unsigned), c->stream);
+    PoolBuf<int> mcnt(c), cursor(c);
+    CHK(mcnt.alloc((size_t)n));
+    CHK(cursor.alloc((size_t)n));
+    HIPCHK(hipMemsetAsync(mcnt, 0, (size_t)n * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(cursor, 0, (size_t)n * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_flags, 0, sizeof(unsigned), c->stream));
     const int grid = (int)std::min<int64_t>((n + 3) / 4, 16384);
     LAUNCH(c, "smm_mirror_count", smm_mirror_count, grid, 256, 0, (int)n, d_indptr, d_indices, mcnt, c->d_flags);
     // rows that receive more mirrored entries than the LDS sort holds: their entries are staged and placed by rank
-    int64_t *big = nullptr, *toff = nullptr; int *tidx = nullptr; double *tval = nullptr;
+    PoolBuf<int64_t> big(c), toff(c);
+    PoolBuf<int> tidx(c);
+    PoolBuf<double> tval(c);
     int64_t total_big = 0;
-    auto drop = [&]() { pool_free(c, mcnt); pool_free(c, cursor); pool_free(c, big); pool_free(c, toff); pool_free(c, tidx); pool_free(c, tval); };
-    rc = pool_get(c, (size_t)n, &big);
-    if (rc == SMM_OK) rc = pool_get(c, (size_t)n + 1, &toff);
-    if (rc == SMM_OK) {
-        LAUNCH(c, "smm_mirror_big", smm_mirror_big, std::min<int64_t>((n + 255) / 256, 4096), 256, 0, (int)n, (const int *)mcnt, big);
-        rc = scan_launch<int64_t>(c, n, big, toff);
+    CHK(big.alloc((size_t)n));
+    CHK(toff.alloc((size_t)n + 1));
+    LAUNCH(c, "smm_mirror_big", smm_mirror_big, std::min<int64_t>((n + 255) / 256, 4096), 256, 0, (int)n, (const int *)mcnt, big);
+    CHK(scan_launch<int64_t>(c, n, big, toff));
+    HIPCHK(hipMemcpyAsync(&total_big, toff + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (total_big > 0) {
+        CHK(tidx.alloc((size_t)total_big));
+        CHK(tval.alloc((size_t)total_big));
     }
-    if (rc == SMM_OK) {
-        if (e == hipSuccess) e = hipMemcpyAsync(&total_big, toff + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(SMM_ERR_HIP, "CSR mirror: %s", hipGetErrorString(e));
-    }
-    if (rc == SMM_OK && total_big > 0) {
-        rc = pool_get(c, (size_t)total_big, &tidx);
-        if (rc == SMM_OK) rc = pool_get(c, (size_t)total_big, &tval);
-    }
-    if (rc != SMM_OK) { drop(); return rc; }
     LAUNCH(c, "smm_mirror_fill", smm_mirror_fill, grid, 256, 0, (int)n, d_indptr, d_indices, d_data, d_full_indptr, (const int *)mcnt, cursor,
            d_full_indices, d_full_data, total_big > 0 ? (const int64_t *)toff : (const int64_t *)nullptr, tidx, tval);
     if (total_big > 0) {
         auto rk = smm_mirror_rank;
         const size_t rlds = (size_t)2 * RANK_WORDS * sizeof(unsigned);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)rk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds);
+        HIPCHK(hipFuncSetAttribute((const void *)rk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
         LAUNCH(c, "smm_mirror_rank", rk, std::min<int64_t>(n, (int64_t)c->n_cu * 4), 1024, rlds, (int)n, d_full_indptr, (const int *)mcnt,
                (const int64_t *)toff, (const int *)tidx, (const double *)tval, d_full_indices, d_full_data);
     }
@@ -2412,14 +2395,12 @@ extern "C" int smm_csr_mirror_fill(smm_ctx *c, int64_t n, const int64_t *d_indpt
     {
         auto kern = smm_mirror_sort<true>;
         const size_t lds = (size_t)MIRROR_MAX_SEG * (sizeof(double) + sizeof(int));
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         LAUNCH(c, "smm_mirror_sort", kern, std::min<int64_t>(n, (int64_t)c->n_cu * 4), 256, lds, (int)n, d_full_indptr, (const int *)mcnt,
                d_full_indices, d_full_data);
     }
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);     // mcnt / cursor / the staging array return to the pool
-    drop();
-    if (e != hipSuccess) return fail(SMM_ERR_HIP, "CSR mirror: %s", hipGetErrorString(e));
+    LAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));     // mcnt / cursor / the staging array return to the pool
     return SMM_OK;
 }
 
@@ -2449,14 +2430,11 @@ extern "C" int smm_triple_product(smm_ctx *c, smm_csr *h, smm_csr *q, int flags,
         return SMM_OK;
     }
     // stage 1: T = H[row_begin:row_end, :] * Q, dense nr x K (sparse_sparse_dense.cpp:187-198)
-    double *T = nullptr;
-    CHK(pool_get(c, (size_t)nr * K, &T));
+    PoolBuf<double> T(c);
+    CHK(T.alloc((size_t)nr * K));
     if (q->cols < K) HIPCHK(hipMemsetAsync(T, 0, (size_t)nr * K * sizeof(double), c->stream));
-    smm_csr hv = *h;                       // row-range view of H (borrowed arrays)
-    hv.ptr = h->ptr + row_begin; hv.rows = nr; hv.owned = false; hv.segs.clear(); hv.locs.clear(); hv.slabs.clear(); hv.packs.clear(); hv.ccs.clear(); hv.idx16 = nullptr; hv.idx_pad = nullptr;
-    // indptr of the view is not rebased: kernels only use ptr[row], ptr[row+1] as absolute positions.
-    int rc = dense_into(c, &hv, q, flags & SMM_EXACT, 0, T, K);
-    if (rc != SMM_OK) { pool_free(c, T); return rc; }
+    smm_csr hv = csr_row_view(h, row_begin, nr);
+    CHK(dense_into(c, &hv, q, flags & SMM_EXACT, 0, T, K));
     // stage 2
     if (h->vflags & CSR_UNSORTED) {
         // H with unsorted rows (legal CSR, e.g. an unsorted scipy product): the chunked ELL walk needs
@@ -2468,10 +2446,9 @@ extern "C" int smm_triple_product(smm_ctx *c, smm_csr *h, smm_csr *q, int flags,
                                full ? 1 : 0, h->ptr, h->idx, h->val, (const double *)T, d_c, n);
         }
         if (full) LAUNCH(c, "smm_triple_mirror", smm_triple_mirror, (n * n + 255) / 256, 256, 0, (int)n, d_c, n);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        pool_free(c, T);
-        if (e != hipSuccess) return fail(SMM_ERR_HIP, "triple product: %s", hipGetErrorString(e));
+        LAUNCH_CHECK();
+        HIPCHK(hipStreamSynchronize(c->stream));
+        T.reset();
         if (mirror) CHK(mirror_upper(c, n, d_c, n));
         return SMM_OK;
     }
@@ -2483,8 +2460,7 @@ extern "C" int smm_triple_product(smm_ctx *c, smm_csr *h, smm_csr *q, int flags,
     if (c->s2_ring && NW == 16 && (K + RING_PW - 1) / RING_PW < 65535) {
         // round 4: ring of column pieces, progress words instead of barriers (smm_ring.hpp)
         const bool exact_r = (flags & SMM_EXACT) != 0;
-        rc = ensure_ring(c, h, !exact_r);
-        if (rc != SMM_OK) { pool_free(c, T); return rc; }
+        CHK(ensure_ring(c, h, !exact_r));
         RingArgs A{};
         A.n = (int)n; A.K = (int)K; A.npieces = h->ring_npieces; A.nslices = (int)((n + WAVE - 1) / WAVE);
         A.nib = (int)((nr + R - 1) / R);
@@ -2495,17 +2471,15 @@ extern "C" int smm_triple_product(smm_ctx *c, smm_csr *h, smm_csr *q, int flags,
         A.nkg = (int)nkg;
         A.gk = (int)std::min<int64_t>(std::max(c->s2_group, 1), nkg);
         const int64_t grid2 = ((nkg + A.gk - 1) / A.gk) * A.gk * (((int64_t)A.nib + 7) / 8) * 8;
-        if (grid2 > 0x7fffffff) { pool_free(c, T); return fail(SMM_ERR_INVALID, "triple product too large for one launch"); }
+        if (grid2 > 0x7fffffff) return fail(SMM_ERR_INVALID, "triple product too large for one launch");
         const size_t lds = (size_t)RING_NB * RING_PW * (R + 2) * sizeof(double);
         auto kern = exact_r ? smm_triple_stage2_ring<R, 16, false> : smm_triple_stage2_ring<R, 16, true>;
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { pool_free(c, T); return fail(SMM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
+        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         LAUNCH(c, "smm_triple_stage2", kern, grid2, 16 * 64, lds, A);
         if (full) LAUNCH(c, "smm_triple_mirror", smm_triple_mirror, (n * n + 255) / 256, 256, 0, (int)n, d_c, n);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // T returns to the pool below
-        pool_free(c, T);
-        if (e != hipSuccess) return fail(SMM_ERR_HIP, "triple product: %s", hipGetErrorString(e));
+        LAUNCH_CHECK();
+        HIPCHK(hipStreamSynchronize(c->stream));   // T returns to the pool
+        T.reset();
 #ifdef SMM_RING_STAMPS
         {
             unsigned long long st[6];
@@ -2523,8 +2497,7 @@ extern "C" int smm_triple_product(smm_ctx *c, smm_csr *h, smm_csr *q, int flags,
     const int nchunks = (int)((K + chunk_cap - 1) / chunk_cap);
     const int chunk = (int)((K + nchunks - 1) / nchunks);
     const bool exact = (flags & SMM_EXACT) != 0;
-    rc = ensure_ell(c, h, nchunks, chunk, !exact);
-    if (rc != SMM_OK) { pool_free(c, T); return rc; }
+    CHK(ensure_ell(c, h, nchunks, chunk, !exact));
     TripleArgs A{};
     A.n = (int)n; A.K = (int)K; A.nchunks = nchunks; A.chunk = chunk; A.nslices = (int)((n + WAVE - 1) / WAVE);
     A.nib = (int)((nr + R - 1) / R);
@@ -2534,17 +2507,14 @@ extern "C" int smm_triple_product(smm_ctx *c, smm_csr *h, smm_csr *q, int flags,
     const size_t lds = (size_t)(R + 2) * chunk * sizeof(double);
     const int64_t nkg = (n + NW * WAVE - 1) / (NW * WAVE);
     auto kern = exact ? smm_triple_stage2<R, NW, chunk_cap, false> : smm_triple_stage2<R, NW, chunk_cap, true>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { pool_free(c, T); return fail(SMM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e)); }
-    }
+    if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     A.nkg = (int)nkg;
     A.gk = (int)std::min<int64_t>(std::max(c->s2_group, 1), nkg);
     const int64_t grid2 = ((nkg + A.gk - 1) / A.gk) * A.gk * (((int64_t)A.nib + 7) / 8) * 8;
-    if (grid2 > 0x7fffffff) { pool_free(c, T); return fail(SMM_ERR_INVALID, "triple product too large for one launch"); }
+    if (grid2 > 0x7fffffff) return fail(SMM_ERR_INVALID, "triple product too large for one launch");
 #ifdef SMM_S2_STAMPS
-    unsigned long long *d_st = nullptr;
-    if (pool_get(c, 8, &d_st) == SMM_OK) { (void)hipMemsetAsync(d_st, 0, 64, c->stream); A.stamps = d_st; }
+    PoolBuf<unsigned long long> d_st(c);
+    if (d_st.alloc(8) == SMM_OK) { (void)hipMemsetAsync(d_st, 0, 64, c->stream); A.stamps = d_st; }
 #endif
     LAUNCH(c, "smm_triple_stage2", kern, grid2, NW * 64, lds, A);
 #ifdef SMM_S2_STAMPS
@@ -2555,14 +2525,13 @@ extern "C" int smm_triple_product(smm_ctx *c, smm_csr *h, smm_csr *q, int flags,
         double tot = 0; for (int i = 0; i < 6; ++i) tot += (double)hst[i];
         fprintf(stderr, "[SMM_S2_STAMPS] wave-cycles %.4g: preload issue %.1f%%  barrier 1 %.1f%%  tile write %.1f%%  barrier 2 %.1f%%  tile load issue %.1f%%  steps %.1f%%\n",
                 tot, 100 * hst[0] / tot, 100 * hst[1] / tot, 100 * hst[2] / tot, 100 * hst[3] / tot, 100 * hst[4] / tot, 100 * hst[5] / tot);
-        pool_free(c, d_st);
+        d_st.reset();
     }
 #endif
     if (full) LAUNCH(c, "smm_triple_mirror", smm_triple_mirror, (n * n + 255) / 256, 256, 0, (int)n, d_c, n);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // T returns to the pool below
-    pool_free(c, T);
-    if (e != hipSuccess) return fail(SMM_ERR_HIP, "triple product: %s", hipGetErrorString(e));
+    LAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));   // T returns to the pool
+    T.reset();
     if (mirror) CHK(mirror_upper(c, n, d_c, n));
     return SMM_OK;
 }
@@ -2575,13 +2544,12 @@ extern "C" int smm_triple_product_host(smm_ctx *c, smm_csr *h, smm_csr *q, int f
     const int64_t n = h->rows, nr = row_end - row_begin;
     if (nr <= 0 || n == 0) return smm_triple_product(c, h, q, flags, row_begin, row_end, nullptr);
     if (!out) return fail(SMM_ERR_INVALID, "c is NULL");
-    double *d = nullptr;
-    CHK(pool_get(c, (size_t)nr * n, &d));
-    int rc = smm_triple_product(c, h, q, flags, row_begin, row_end, d);
-    if (rc == SMM_OK) rc = download(c, out, d, (size_t)nr * (size_t)n * sizeof(double));
+    PoolBuf<double> d(c);
+    CHK(d.alloc((size_t)nr * n));
+    CHK(smm_triple_product(c, h, q, flags, row_begin, row_end, d));
+    CHK(download(c, out, d, (size_t)nr * (size_t)n * sizeof(double)));
     (void)hipStreamSynchronize(c->stream);
-    pool_free(c, d);
-    return rc;
+    return SMM_OK;
 }
 
 // ------------------------------------------------------------------------------ device CSR transpose
@@ -2601,42 +2569,33 @@ static int transpose_impl(smm_ctx *c, const smm_csr *a, smm_csr **out)
 {
     *out = nullptr;
     const int64_t rows = a->cols, cols = a->rows, nnz = a->nnz;
-    int *dp = nullptr, *di = nullptr; double *dv = nullptr;
-    if (dev_malloc(c, (void **)&dp, (rows + 1) * sizeof(int)) != hipSuccess ||
-        dev_malloc(c, (void **)&di, (std::max<int64_t>(nnz, 1) + 2) * sizeof(int)) != hipSuccess ||     // (slack as smm_csr_from_host)
-        dev_malloc(c, (void **)&dv, std::max<int64_t>(nnz, 1) * sizeof(double)) != hipSuccess) {
-        (void)hipFree(dp); (void)hipFree(di); (void)hipFree(dv);
+    DevBuf<int> dp, di; DevBuf<double> dv;
+    if (dp.alloc(c, rows + 1) != hipSuccess || di.alloc(c, std::max<int64_t>(nnz, 1) + 2) != hipSuccess ||     // (slack as smm_csr_from_host)
+        dv.alloc(c, std::max<int64_t>(nnz, 1)) != hipSuccess)
         return fail(SMM_ERR_ALLOC, "hipMalloc of the transposed operand failed");
-    }
-    smm_csr *m = new smm_csr();
-    m->ctx = c; m->rows = rows; m->cols = cols; m->nnz = nnz;
-    m->ptr = dp; m->idx = di; m->val = dv; m->owned = true;
-    int *cnt = nullptr, *key = nullptr; int64_t *off = nullptr;
-    auto drop = [&]() { pool_free(c, cnt); pool_free(c, key); pool_free(c, off); };
-    int rc = pool_get(c, (size_t)rows + 1, &cnt);
-    if (rc == SMM_OK) rc = pool_get(c, (size_t)rows + 1, &off);
-    if (rc == SMM_OK) rc = pool_get(c, (size_t)std::max<int64_t>(nnz, 1), &key);
-    hipError_t e = rc == SMM_OK ? hipMemsetAsync(cnt, 0, ((size_t)rows + 1) * sizeof(int), c->stream) : hipSuccess;
-    const int grid = (int)std::min<int64_t>(std::max<int64_t>((nnz + 255) / 256, 1), (int64_t)c->n_cu * 16);
-    if (rc == SMM_OK && e == hipSuccess) {
+    {
+        PoolBuf<int> cnt(c), key(c);
+        PoolBuf<int64_t> off(c);
+        CHK(cnt.alloc((size_t)rows + 1));
+        CHK(off.alloc((size_t)rows + 1));
+        CHK(key.alloc((size_t)std::max<int64_t>(nnz, 1)));
+        HIPCHK(hipMemsetAsync(cnt, 0, ((size_t)rows + 1) * sizeof(int), c->stream));
+        const int grid = (int)std::min<int64_t>(std::max<int64_t>((nnz + 255) / 256, 1), (int64_t)c->n_cu * 16);
         LAUNCH(c, "smm_transpose_count", smm_transpose_count, grid, 256, 0, nnz, a->idx, (int)rows, cnt);
-        rc = scan_launch<int>(c, rows, cnt, off);
-    }
-    if (rc == SMM_OK && e == hipSuccess) {
-        e = hipMemsetAsync(cnt, 0, ((size_t)rows + 1) * sizeof(int), c->stream);       // (cursor of the scatter)
+        CHK(scan_launch<int>(c, rows, cnt, off));
+        HIPCHK(hipMemsetAsync(cnt, 0, ((size_t)rows + 1) * sizeof(int), c->stream));       // (cursor of the scatter)
         LAUNCH(c, "smm_transpose_scatter", smm_transpose_scatter, grid, 256, 0, nnz, a->idx, (int)rows, (const int64_t *)off, cnt, key);
-        rc = seg_sort(c, rows, off, key);
-    }
-    if (rc == SMM_OK && e == hipSuccess) {
+        CHK(seg_sort(c, rows, off, key));
         const int ggrid = (int)std::min<int64_t>(std::max<int64_t>(std::max(nnz, rows + 1) / 256 + 1, 1), (int64_t)c->n_cu * 16);
         LAUNCH(c, "smm_transpose_gather", smm_transpose_gather, ggrid, 256, 0, nnz, (int)a->rows, a->ptr, a->val, (const int *)key, (int)rows,
                (const int64_t *)off, dp, di, dv);
-        e = hipGetLastError();
+        LAUNCH_CHECK();
+        HIPCHK(hipStreamSynchronize(c->stream));
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    drop();
-    if (rc == SMM_OK && e != hipSuccess) rc = fail(SMM_ERR_HIP, "smm_csr_transpose: %s", hipGetErrorString(e));
-    if (rc == SMM_OK) rc = validate(c, m);          // (flags of the new operand: sorted rows, repeated columns where A repeats rows)
+    smm_csr *m = new smm_csr();
+    m->ctx = c; m->rows = rows; m->cols = cols; m->nnz = nnz;
+    m->ptr = dp.release(); m->idx = di.release(); m->val = dv.release(); m->owned = true;
+    const int rc = validate(c, m);          // (flags of the new operand: sorted rows, repeated columns where A repeats rows)
     if (rc != SMM_OK) { smm_csr_destroy(m); return rc; }
     *out = m;
     return SMM_OK;
@@ -2760,62 +2719,58 @@ static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, 
 {
     const int64_t nb = b1 - b0, n = h->rows, K = h->cols;
     const bool exact = (flags & SMM_EXACT) != 0;
-    smm_csr hv = *h;                       // row-range view of H (borrowed arrays, indptr not rebased: see smm_triple_product)
-    hv.ptr = h->ptr + b0; hv.rows = nb; hv.owned = false; hv.segs.clear(); hv.locs.clear(); hv.slabs.clear(); hv.packs.clear(); hv.ccs.clear();
-    hv.idx16 = nullptr; hv.idx_pad = nullptr; hv.tr = nullptr;
-    smm_plan *p1 = nullptr, *p2 = nullptr; smm_csr *tb = nullptr;
+    smm_csr hv = csr_row_view(h, b0, nb);
+    PlanPtr p1, p2;
+    std::unique_ptr<smm_csr, Destroyer<smm_csr_destroy>> tb;
     int64_t tnnz = 0, snnz = 0;
-    int64_t *tptr = nullptr; int *tidx = nullptr, *tptr32 = nullptr, *lists = nullptr; double *tval = nullptr, *dense = nullptr;
-    int64_t *sptr = nullptr; int *sidx = nullptr; double *sval = nullptr;
-    int *mcnt = nullptr;
-    auto drop = [&]() {
-        smm_plan_destroy(p1); smm_plan_destroy(p2); smm_csr_destroy(tb);
-        (void)hipStreamSynchronize(c->stream);
-        pool_free(c, tptr); pool_free(c, tidx); pool_free(c, tval); pool_free(c, tptr32); pool_free(c, lists); pool_free(c, dense);
-        pool_free(c, mcnt);
-    };
-#define BCHK(expr) do { int rc_ = (expr); if (rc_ != SMM_OK) { drop(); pool_free(c, sptr); pool_free(c, sidx); pool_free(c, sval); return rc_; } } while (0)
+    PoolBuf<int64_t> tptr(c), sptr(c);
+    PoolBuf<int> tidx(c), tptr32(c), lists(c), mcnt(c), sidx(c);
+    PoolBuf<double> tval(c), dense(c), sval(c);
     // stage 1: T_b, the engine's SpGEMM (first-touch rows, SMM_EXACT values in the reference's order)
     const bool zero = h->nnz == 0 || q->nnz == 0;       // (masked only: S is the mask's pattern filled with +0.0)
-    if (!zero) BCHK(smm_spgemm_symbolic(c, &hv, q, flags & SMM_EXACT, 0, &p1, &tnnz));
-    BCHK(pool_get(c, (size_t)nb + 1, &tptr));
-    BCHK(pool_get(c, (size_t)std::max<int64_t>(tnnz, 1) + 2, &tidx));
-    BCHK(pool_get(c, (size_t)std::max<int64_t>(tnnz, 1), &tval));
-    if (!zero) BCHK(smm_spgemm_numeric(c, p1, tptr, tidx, tval));
+    smm_plan *pp = nullptr;
+    if (!zero) { CHK(smm_spgemm_symbolic(c, &hv, q, flags & SMM_EXACT, 0, &pp, &tnnz)); p1.reset(pp); }
+    CHK(tptr.alloc((size_t)nb + 1));
+    CHK(tidx.alloc((size_t)std::max<int64_t>(tnnz, 1) + 2));
+    CHK(tval.alloc((size_t)std::max<int64_t>(tnnz, 1)));
+    if (!zero) CHK(smm_spgemm_numeric(c, p1.get(), tptr, tidx, tval));
     else HIPCHK(hipMemsetAsync(tptr, 0, ((size_t)nb + 1) * sizeof(int64_t), c->stream));
-    smm_plan_destroy(p1); p1 = nullptr;
-    if (tnnz >= INT32_MAX) BCHK(fail(SMM_ERR_INVALID, "sparse triple product: one row of T has >= 2^31 entries"));
+    p1.reset();
+    if (tnnz >= INT32_MAX) return fail(SMM_ERR_INVALID, "sparse triple product: one row of T has >= 2^31 entries");
     if (mask) {
         // stage 2, pattern: the mask's rows filtered to k >= i (count, scan, copy)
-        BCHK(pool_get(c, (size_t)2 * nb + 2, &mcnt));
-        BCHK(pool_get(c, (size_t)nb + 1, &sptr));
+        CHK(mcnt.alloc((size_t)2 * nb + 2));
+        CHK(sptr.alloc((size_t)nb + 1));
         const int g = (int)std::min<int64_t>((nb + 255) / 256, 4096);
         LAUNCH(c, "smm_masked_tri_count", smm_masked_tri_count, g, 256, 0, (int)nb, b0, mask->ptr, mask->idx, mcnt, mcnt + nb + 1);
-        BCHK(scan_launch<int>(c, nb, mcnt, sptr));
+        CHK(scan_launch<int>(c, nb, mcnt, sptr));
         HIPCHK(hipMemcpyAsync(&snnz, sptr + nb, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sidx));
-        BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sval));
+        CHK(sidx.alloc((size_t)std::max<int64_t>(snnz, 1)));
+        CHK(sval.alloc((size_t)std::max<int64_t>(snnz, 1)));
         if (snnz > 0)
             LAUNCH(c, "smm_masked_tri_copy", smm_masked_tri_copy, std::min<int64_t>((nb + 3) / 4, 16384), 256, 0, (int)nb,
                    (const int *)(mcnt + nb + 1), (const int *)mcnt, (const int64_t *)sptr, mask->idx, sidx);
         LAUNCH_CHECK();
     } else {
         // stage 2, pattern: T_b (int32 row pointer, borrowed) times H^T, i <= k
-        BCHK(pool_get(c, (size_t)nb + 1, &tptr32));
+        CHK(tptr32.alloc((size_t)nb + 1));
         LAUNCH(c, "smm_triple_sparse_narrow", smm_triple_sparse_narrow, std::min<int64_t>((nb + 256) / 256, 4096), 256, 0, nb, (const int64_t *)tptr, tptr32);
-        BCHK(smm_csr_from_device(c, nb, K, tnnz, tptr32, tidx, tval, &tb));
-        BCHK(smm_spgemm_symbolic(c, tb, ht, SMM_SYMMETRIC, b0, &p2, &snnz));
-        BCHK(pool_get(c, (size_t)nb + 1, &sptr));
-        BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sidx));
-        BCHK(pool_get(c, (size_t)std::max<int64_t>(snnz, 1), &sval));
-        BCHK(smm_spgemm_numeric(c, p2, sptr, sidx, sval));        // (its values are T * H^T in T's order: overwritten below)
-        smm_plan_destroy(p2); p2 = nullptr;
-        BCHK(seg_sort(c, nb, sptr, sidx));
+        smm_csr *t = nullptr;
+        CHK(smm_csr_from_device(c, nb, K, tnnz, tptr32, tidx, tval, &t));
+        tb.reset(t);
+        CHK(smm_spgemm_symbolic(c, tb.get(), ht, SMM_SYMMETRIC, b0, &pp, &snnz));
+        p2.reset(pp);
+        CHK(sptr.alloc((size_t)nb + 1));
+        CHK(sidx.alloc((size_t)std::max<int64_t>(snnz, 1)));
+        CHK(sval.alloc((size_t)std::max<int64_t>(snnz, 1)));
+        CHK(smm_spgemm_numeric(c, p2.get(), sptr, sidx, sval));        // (its values are T * H^T in T's order: overwritten below)
+        p2.reset();
+        CHK(seg_sort(c, nb, sptr, sidx));
     }
     // stage 2, values: rows binned by the length of T_i
     if (snnz > 0) {
-        BCHK(pool_get(c, (size_t)3 * nb + 4, &lists));
+        CHK(lists.alloc((size_t)3 * nb + 4));
         int *cnt = lists + 3 * nb;
         HIPCHK(hipMemsetAsync(cnt, 0, 4 * sizeof(int), c->stream));
         LAUNCH(c, "smm_triple_sparse_bin", smm_triple_sparse_bin, std::min<int64_t>((nb + 255) / 256, 4096), 256, 0, (int)nb,
@@ -2848,7 +2803,7 @@ static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, 
         if (hc[2] > 0) {            // a zeroed global row of K doubles per workgroup, a bounded number in flight
             A.rowlist = lists + 2 * nb; A.nrows = hc[2];
             const int64_t grid = std::max<int64_t>(1, std::min<int64_t>({(int64_t)hc[2], (int64_t)c->n_cu, ((int64_t)1 << 28) / (8 * K)}));
-            BCHK(pool_get(c, (size_t)grid * (size_t)K, &dense));
+            CHK(dense.alloc((size_t)grid * (size_t)K));
             HIPCHK(hipMemsetAsync(dense, 0, (size_t)grid * (size_t)K * sizeof(double), c->stream));
             A.dense = dense;
             if (exact) LAUNCH(c, "smm_triple_sparse_s2", smm_triple_sparse_s2_global<false>, grid, 256, 0, A);
@@ -2856,9 +2811,9 @@ static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, 
             LAUNCH_CHECK();
         }
     }
-#undef BCHK
-    drop();
-    out->rows = nb; out->nnz = snnz; out->ptr = sptr; out->idx = sidx; out->val = sval;
+    tb.reset();
+    (void)hipStreamSynchronize(c->stream);      // the temporaries go back to the pool
+    out->rows = nb; out->nnz = snnz; out->ptr = sptr.release(); out->idx = sidx.release(); out->val = sval.release();
     return SMM_OK;
 }
 
@@ -2873,54 +2828,49 @@ static int triple_sparse_impl(smm_ctx *c, smm_csr *h, smm_csr *q, const smm_csr 
     const bool full = (flags & SMM_FULL_MATRIX) != 0;
     if (full && (row_begin != 0 || row_end != n)) return fail(SMM_ERR_INVALID, "SMM_FULL_MATRIX needs the whole row range [0,n)");
     const int64_t nr = row_end - row_begin;
-    smm_result *r = new smm_result();
+    std::unique_ptr<smm_result, Destroyer<smm_result_destroy>> r(new smm_result());
     r->ctx = c; r->rows = nr; r->cols = n;
-    if (nr == 0 || (mask ? mask->nnz == 0 : (h->nnz == 0 || q->nnz == 0 || K == 0))) { *out = r; return SMM_OK; }
-    int rc = SMM_OK;
-#define RCHK(expr) do { rc = (expr); if (rc != SMM_OK) { smm_result_destroy(r); return rc; } } while (0)
-    if (!mask && !h->tr) RCHK(transpose_impl(c, h, &h->tr));
+    if (nr == 0 || (mask ? mask->nnz == 0 : (h->nnz == 0 || q->nnz == 0 || K == 0))) { *out = r.release(); return SMM_OK; }
+    if (!mask && !h->tr) CHK(transpose_impl(c, h, &h->tr));
     // row blocks: products of H[i] * Q (an upper bound of nnz(T_i)) summed up to the budget, at least one row per block
     std::vector<int64_t> prod((size_t)nr);
-    {
-        smm_csr hv = *h;
-        hv.ptr = h->ptr + row_begin; hv.rows = nr; hv.owned = false; hv.segs.clear(); hv.locs.clear(); hv.slabs.clear(); hv.packs.clear();
-        hv.ccs.clear(); hv.idx16 = nullptr; hv.idx_pad = nullptr; hv.tr = nullptr;
-        if (h->nnz > 0 && q->nnz > 0) RCHK(smm_row_products(c, &hv, q, prod.data()));
+    if (h->nnz > 0 && q->nnz > 0) {
+        smm_csr hv = csr_row_view(h, row_begin, nr);
+        CHK(smm_row_products(c, &hv, q, prod.data()));
     }
     int64_t b0 = row_begin;
     while (b0 < row_end) {
         int64_t b1 = b0, acc = 0;
         while (b1 < row_end && (b1 == b0 || acc + prod[(size_t)(b1 - row_begin)] <= c->t3_max_t)) acc += prod[(size_t)(b1++ - row_begin)];
         smm_result::Piece pc{0, 0, nullptr, nullptr, nullptr};
-        RCHK(triple_sparse_block(c, h, q, h->tr, mask, flags, b0, b1, &pc));
+        CHK(triple_sparse_block(c, h, q, h->tr, mask, flags, b0, b1, &pc));
         r->pieces.push_back(pc);
         r->nnz += pc.nnz;
         b0 = b1;
     }
-    RCHK(take_plan_error(c, "smm_triple_product_sparse"));
+    CHK(take_plan_error(c, "smm_triple_product_sparse"));
     if (full) {
         // the upper triangle joined into one CSR, mirrored on the device (rows stay ascending: mirrored part first, then k >= i)
-        smm_result::Piece up{n, r->nnz, nullptr, nullptr, nullptr}, fp{n, 0, nullptr, nullptr, nullptr};
-        auto drop2 = [&]() { (void)hipStreamSynchronize(c->stream); for (auto *pp : {&up, &fp}) { pool_free(c, pp->ptr); pool_free(c, pp->idx); pool_free(c, pp->val); } };
-#define FCHK(expr) do { rc = (expr); if (rc != SMM_OK) { drop2(); smm_result_destroy(r); return rc; } } while (0)
-        FCHK(pool_get(c, (size_t)n + 1, &up.ptr));
-        FCHK(pool_get(c, (size_t)std::max<int64_t>(up.nnz, 1), &up.idx));
-        FCHK(pool_get(c, (size_t)std::max<int64_t>(up.nnz, 1), &up.val));
-        FCHK(result_join(c, r, up.ptr, up.idx, up.val));
-        FCHK(pool_get(c, (size_t)n + 1, &fp.ptr));
-        FCHK(smm_csr_mirror_symbolic(c, n, up.ptr, up.idx, fp.ptr, &fp.nnz));
-        FCHK(pool_get(c, (size_t)std::max<int64_t>(fp.nnz, 1), &fp.idx));
-        FCHK(pool_get(c, (size_t)std::max<int64_t>(fp.nnz, 1), &fp.val));
-        FCHK(smm_csr_mirror_fill(c, n, up.ptr, up.idx, up.val, fp.ptr, fp.idx, fp.val));
-#undef FCHK
+        PoolBuf<int64_t> up_ptr(c), fp_ptr(c);
+        PoolBuf<int> up_idx(c), fp_idx(c);
+        PoolBuf<double> up_val(c), fp_val(c);
+        int64_t fnnz = 0;
+        CHK(up_ptr.alloc((size_t)n + 1));
+        CHK(up_idx.alloc((size_t)std::max<int64_t>(r->nnz, 1)));
+        CHK(up_val.alloc((size_t)std::max<int64_t>(r->nnz, 1)));
+        CHK(result_join(c, r.get(), up_ptr, up_idx, up_val));
+        CHK(fp_ptr.alloc((size_t)n + 1));
+        CHK(smm_csr_mirror_symbolic(c, n, up_ptr, up_idx, fp_ptr, &fnnz));
+        CHK(fp_idx.alloc((size_t)std::max<int64_t>(fnnz, 1)));
+        CHK(fp_val.alloc((size_t)std::max<int64_t>(fnnz, 1)));
+        CHK(smm_csr_mirror_fill(c, n, up_ptr, up_idx, up_val, fp_ptr, fp_idx, fp_val));
         (void)hipStreamSynchronize(c->stream);
         for (auto &p : r->pieces) { pool_free(c, p.ptr); pool_free(c, p.idx); pool_free(c, p.val); }
-        pool_free(c, up.ptr); pool_free(c, up.idx); pool_free(c, up.val);
-        r->pieces.assign(1, fp);
-        r->nnz = fp.nnz;
+        up_ptr.reset(); up_idx.reset(); up_val.reset();
+        r->pieces.assign(1, smm_result::Piece{n, fnnz, fp_ptr.release(), fp_idx.release(), fp_val.release()});
+        r->nnz = fnnz;
     }
-#undef RCHK
-    *out = r;
+    *out = r.release();
     return SMM_OK;
 }
 
@@ -2985,21 +2935,18 @@ static int masked_impl(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int fl
     const bool a_canonical = !(a->vflags & (CSR_UNSORTED | CSR_HAS_EQUAL));
     const bool dot = a_canonical && c->masked_mode != 2;
     if (dot && !b->trv) CHK(transpose_impl(c, b, &b->trv));
-    int *cls = nullptr, *lists = nullptr, *map = nullptr;
-    auto drop = [&]() { (void)hipStreamSynchronize(c->stream); pool_free(c, cls); pool_free(c, lists); pool_free(c, map); };
-#define MCHK(expr) do { int rc_ = (expr); if (rc_ != SMM_OK) { drop(); return rc_; } } while (0)
-#define MHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { drop(); return fail(SMM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
-    MCHK(pool_get(c, (size_t)m + 8, &cls));
-    MCHK(pool_get(c, (size_t)MK_NCLS * m, &lists));
+    PoolBuf<int> cls(c), lists(c), map(c);
+    CHK(cls.alloc((size_t)m + 8));
+    CHK(lists.alloc((size_t)MK_NCLS * m));
     int *cnt = cls + m;
-    MHIP(hipMemsetAsync(cnt, 0, 8 * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(cnt, 0, 8 * sizeof(int), c->stream));
     LAUNCH(c, "smm_masked_cost", smm_masked_cost, std::min<int64_t>((m + 3) / 4, 16384), 256, 0, (int)m, mask->ptr, mask->idx, a->ptr, a->idx,
            b->ptr, (int)b->rows, dot ? (const int *)b->trv->ptr : nullptr, (int)b->cols, c->masked_mode, cls);
     LAUNCH(c, "smm_masked_bin", smm_masked_bin, std::min<int64_t>((m + 255) / 256, 4096), 256, 0, (int)m, (const int *)cls, lists, cnt);
-    MHIP(hipGetLastError());
+    LAUNCH_CHECK();
     int hc[8] = {0};
-    MHIP(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
-    MHIP(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     MaskedArgs A{};
     A.m = (int)m;
     A.a_ptr = a->ptr; A.a_idx = a->idx; A.a_val = a->val; A.K = (int)a->cols;
@@ -3028,7 +2975,7 @@ static int masked_impl(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int fl
         } else if (cl == MK_DOT_WG) {          // one workgroup per row
             const size_t lds = (size_t)8192 * 2 * sizeof(int);
             auto kern = smm_masked_dot_hash<8192, 13, 256, 1>;
-            MHIP(wg_kernel((const void *)kern, lds));
+            HIPCHK(wg_kernel((const void *)kern, lds));
             LAUNCH(c, "smm_masked_dot", kern, std::min<int64_t>(hc[cl], (int64_t)c->n_cu * 2), 256, lds, A, dot_g);
         } else if (cl == MK_ROW_WAVE) {
             const size_t lds = (size_t)4 * 512 * (sizeof(double) + sizeof(int) + 1);
@@ -3038,14 +2985,13 @@ static int masked_impl(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int fl
         } else if (cl == MK_ROW_WG) {
             const size_t lds = (size_t)8192 * (sizeof(double) + sizeof(int) + 1);
             auto kern = exact ? smm_masked_row_hash<8192, 13, 256, 1, true> : smm_masked_row_hash<8192, 13, 256, 1, false>;
-            MHIP(wg_kernel((const void *)kern, lds));
+            HIPCHK(wg_kernel((const void *)kern, lds));
             LAUNCH(c, "smm_masked_row", kern, std::min<int64_t>(hc[cl], (int64_t)c->n_cu), 256, lds, A);
         } else {                               // MK_DOT_GLOBAL / MK_ROW_GLOBAL
             const int64_t width = cl == MK_DOT_GLOBAL ? a->cols : b->cols;
             const int64_t grid = global_grid(hc[cl], width);
-            pool_free(c, map); map = nullptr;
-            MCHK(pool_get(c, (size_t)grid * (size_t)width, &map));
-            MHIP(hipMemsetAsync(map, 0, (size_t)grid * (size_t)width * sizeof(int), c->stream));
+            CHK(map.alloc((size_t)grid * (size_t)width));      // (the previous class's map goes back to the pool first)
+            HIPCHK(hipMemsetAsync(map, 0, (size_t)grid * (size_t)width * sizeof(int), c->stream));
             A.map = map;
             if (cl == MK_DOT_GLOBAL) {
                 LAUNCH(c, "smm_masked_dot", smm_masked_dot_global, grid, 256, 0, A, dot_g);
@@ -3054,11 +3000,10 @@ static int masked_impl(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int fl
                 else       LAUNCH(c, "smm_masked_row", smm_masked_row_global<false>, grid, 256, 0, A);
             }
         }
-        MHIP(hipGetLastError());
+        LAUNCH_CHECK();
     }
-#undef MCHK
-#undef MHIP
-    drop();
+    (void)hipStreamSynchronize(c->stream);
+    cls.reset(); lists.reset(); map.reset();
     return take_plan_error(c, "smm_spgemm_masked");
 }
 
@@ -3087,13 +3032,12 @@ extern "C" int smm_spgemm_masked_host(smm_ctx *c, smm_csr *a, smm_csr *b, smm_cs
     CHK(masked_args(c, a, b, mask, flags));
     if (mask->nnz == 0) return SMM_OK;
     if (!c_data) return fail(SMM_ERR_INVALID, "c_data is NULL but nnz(mask) > 0");
-    double *d = nullptr;
-    CHK(pool_get(c, (size_t)mask->nnz, &d));
-    int rc = masked_impl(c, a, b, mask, flags, d);
-    if (rc == SMM_OK) rc = download(c, c_data, d, (size_t)mask->nnz * sizeof(double));
+    PoolBuf<double> d(c);
+    CHK(d.alloc((size_t)mask->nnz));
+    CHK(masked_impl(c, a, b, mask, flags, d));
+    CHK(download(c, c_data, d, (size_t)mask->nnz * sizeof(double)));
     (void)hipStreamSynchronize(c->stream);
-    pool_free(c, d);
-    return rc;
+    return SMM_OK;
 }
 
 // ------------------------------------------------------------------------------ memory helpers

@@ -106,6 +106,10 @@ class Context:
     def pool_bytes(self):
         return int(self.lib.smm_ctx_pool_bytes(self.handle))
 
+    def live_bytes(self):
+        """Bytes of pooled scratch handed out: held by open plans and results only (smm_ctx_live_bytes)."""
+        return int(self.lib.smm_ctx_live_bytes(self.handle))
+
     def inject_alloc_failure(self, nth, hard=False):
         """TEST HOOK: the nth device allocation from now fails (first attempt only, or both with hard=True)."""
         check(self.lib, self.lib.smm_ctx_inject_alloc_failure(self.handle, int(nth), 1 if hard else 0))

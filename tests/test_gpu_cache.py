@@ -284,3 +284,92 @@ def test_a_failed_allocation_is_retried_after_the_pool_went_back_to_the_device(p
     ctx.inject_alloc_failure(1, hard=True)
     _check(smm(A4, B4), A4, B4, oracle)
     ctx.inject_alloc_failure(0)
+
+
+def test_a_failed_allocation_leaves_no_pool_block_handed_out(oracle):
+    """Every entry point, made to fail at its 1st, 2nd, ... device allocation (hard: the pool's flush does not help)
+    until it succeeds: each failure is SMM_ERR_ALLOC and gives every pool block it took back (smm_ctx_live_bytes is 0
+    with no plan or result open), and the call that finally succeeds matches the oracle."""
+    import scipy.sparse as sp
+    from sparse_matrix_mult_amd.engine import Context, SmmError
+    ctx = Context(0)
+    A, B = rand_csr(300, 400, 0.05, 41), rand_csr(400, 300, 0.05, 43)
+    H = signed(rand_csr(200, 300, 0.03, 45), 46)
+    S = rand_csr(300, 300, 0.01, 47)
+    Q = signed((S + S.T).tocsr(), 48)
+    L, M = rand_csr(200, 200, 0.1, 49), rand_csr(300, 300, 0.05, 50)
+    W = oracle.triple(arrays(H), arrays(Q), 300, 0)                  # H Q H^T, k >= i
+    AB = oracle.dense(arrays(A), arrays(B), 300)
+    p, i, v = oracle.sparse(arrays(A), arrays(B), 300)
+    ABs = sp.csr_matrix((v, i, p), shape=(300, 300)).toarray()
+    p, i, v = oracle.sparse(arrays(A), arrays(B), 300, symmetric=True)
+    up = sp.csr_matrix((v, i, p), shape=(300, 300))
+    handles = []
+    try:
+        a, b, h, q, lm, mk = (ctx.csr_from_scipy(X) for X in (A, B, H, Q, L, M))     # (uploads allocate too: before the sweep)
+        handles += [a, b, h, q, lm, mk]
+
+        def sparse_exact(res):
+            assert_csr_equal(res, oracle.sparse(arrays(A), arrays(B), 300), values="bits")
+
+        def slab_walk():                                             # B wider than the symbolic walk's slab: slab by slab
+            ctx.tune_shared(64, 4); ctx.tune(64, 4); ctx.tune_symbolic(200)
+            try:
+                return ctx.spgemm_host(a, b, exact=True)
+            finally:
+                ctx.tune_shared(20000, 16); ctx.tune(18000, 8); ctx.tune_symbolic(0)
+
+        def transpose():
+            t = ctx.transpose(a)
+            try:
+                return t.to_host()
+            finally:
+                t.close()
+
+        def dense_of(res, n):
+            return sp.csr_matrix((res[2], res[1], res[0]), shape=(n, n)).toarray()
+
+        U = sp.triu(L, format="csr")
+        U.sort_indices()
+        rows = np.repeat(np.arange(200), np.diff(U.indptr))
+        C = A.tocsc()
+        cases = [
+            ("spgemm_host", lambda: ctx.spgemm_host(a, b),
+             lambda r: assert_csr_equal(r, oracle.sparse(arrays(A), arrays(B), 300), values="close")),
+            ("spgemm_host exact", lambda: ctx.spgemm_host(a, b, exact=True), sparse_exact),
+            ("spgemm_host slabs", slab_walk, sparse_exact),
+            ("dense_host", lambda: ctx.dense_host(a, b, exact=True), lambda r: np.testing.assert_array_equal(r, AB)),
+            ("triple_host", lambda: ctx.triple_host(h, q, exact=True), lambda r: np.testing.assert_array_equal(r, W)),
+            ("triple_sparse_host full", lambda: ctx.triple_sparse_host(h, q, full=True, exact=True),
+             lambda r: np.testing.assert_array_equal(dense_of(r, 200), np.triu(W) + np.triu(W, 1).T)),
+            ("triple_sparse_host mask", lambda: ctx.triple_sparse_host(h, q, mask=lm, exact=True),
+             lambda r: (np.testing.assert_array_equal(r[0], U.indptr), np.testing.assert_array_equal(r[1], U.indices),
+                        np.testing.assert_array_equal(r[2], W[rows, U.indices]))),
+            ("spgemm_masked_host", lambda: ctx.spgemm_masked_host(a, b, mk, exact=True),
+             lambda r: np.testing.assert_array_equal(r, ABs[np.repeat(np.arange(300), np.diff(M.indptr)), M.indices])),
+            ("transpose", transpose,
+             lambda r: [np.testing.assert_array_equal(np.asarray(g, w.dtype), w) for g, w in zip(r, (C.indptr, C.indices, C.data))]),
+            ("spgemm_host_mirrored", lambda: ctx.spgemm_host_mirrored(a, b, exact=True),
+             lambda r: np.testing.assert_array_equal(dense_of(r, 300), (up + sp.triu(up, 1).T).toarray())),
+        ]
+        for name, call, check in cases:
+            for nth in range(1, 65):
+                ctx.release_pool()
+                ctx.inject_alloc_failure(nth, hard=True)
+                try:
+                    res = call()
+                except SmmError as e:
+                    assert e.code == -3, f"{name}, allocation {nth}: {e}"
+                    assert ctx.live_bytes() == 0, f"{name}, allocation {nth}: {ctx.live_bytes()} bytes still handed out"
+                    continue
+                finally:
+                    ctx.inject_alloc_failure(0)
+                check(res)
+                assert ctx.live_bytes() == 0, name
+                break
+            else:
+                pytest.fail(f"{name} still fails after 64 injected allocation failures")
+    finally:
+        for x in handles:
+            x.close()
+        ctx.close()
