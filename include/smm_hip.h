@@ -49,6 +49,7 @@ enum smm_flags {
                              is filled with the mirror image of the upper one, i.e. the full symmetric matrix
                              (what compute_full_matrix=1 was meant to give; SMM_FULL_MATRIX reproduces its
                              doubling bug instead).  Whole square results only.                          */
+    SMM_TRANSPOSE   = 16, /* op(A) = A^T in the sparse x dense product (smm_spmm* only)                      */
     SMM_EXACT       = 4   /* add every product in exactly the reference's order: float64 values
                              are then bit-identical to the CPU loop, for any legal CSR operand (B with
                              unsorted rows or repeated columns takes an ordered read-modify-write
@@ -321,6 +322,34 @@ int  smm_spgemm_masked_host(smm_ctx *ctx, smm_csr *a, smm_csr *b, smm_csr *mask,
 /* Path of the masked SpGEMM: 0 = per-row cost model (default), 1 = dot path, 2 = row path.  A that is not canonical
  * always takes the row path.  Results do not depend on it (bit for bit under SMM_EXACT). */
 int  smm_ctx_tune_masked(smm_ctx *ctx, int mode);
+
+/* ------------------------------------------------------------------ sparse x dense: Y = op(A) * X
+ * op(A) (m x K) is A, or A^T with SMM_TRANSPOSE (the transpose is built on the device on first use and cached on A's
+ * handle; smm_csr_update_values[_device] drops it).  X: K x k, Y: m x k, both row-major float64
+ * with leading dimensions ldx, ldy >= k; every element of Y's k columns is written, its padding columns are not.
+ * 64-bit offsets: rows * ld may exceed 2^31.  k = 0 is valid and does nothing.
+ *   SMM_EXACT: Y[i,j] starts at +0.0 and adds A[i,p] * X[col_p, j] for p in row i's stored order, one product at a time
+ *   (scipy's csr_matvec / csr_matvecs loop; for A^T the rows of scipy's A.tocsc()): bit-identical to scipy's A @ X and
+ *   A.T @ X for any legal CSR.  Without it: fused multiply-adds and long rows split across waves, within 1e-10 of
+ *   (|A| |X|)[i,j] of the exact value.  No float atomics: results are bitwise reproducible in both modes.
+ *   A pair that row i does not store is never multiplied (an inf in X[c,:] reaches Y[i,:] only through A[i,c]).
+ * Accepted flags: SMM_EXACT | SMM_TRANSPOSE; anything else, ldx < k, ldy < k, NULL buffers that should hold data and
+ * overlapping device ranges of X and Y are SMM_ERR_INVALID. */
+int  smm_spmm(smm_ctx *ctx, smm_csr *a, int flags, int64_t k, const double *d_x, int64_t ldx, double *d_y, int64_t ldy);
+/* Same with host X and Y (uploaded / downloaded through pool temporaries). */
+int  smm_spmm_host(smm_ctx *ctx, smm_csr *a, int flags, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy);
+/* Y = H * (Q * (H^T * X)) = S X with S = H Q H^T never formed: three sparse x dense products with device intermediates
+ * (H: n x K, Q: K x K, need not be symmetric; X, Y: n x k).  H^T comes from H's cached transpose.  X is taken in column
+ * blocks whose two K x block intermediates fit the context's apply budget (smm_ctx_tune_spmm).  SMM_EXACT (the only flag):
+ * bit-identical to scipy's H @ (Q @ (H.T @ X)). */
+int  smm_triple_apply(smm_ctx *ctx, smm_csr *h, smm_csr *q, int flags, int64_t k, const double *d_x, int64_t ldx,
+                      double *d_y, int64_t ldy);
+int  smm_triple_apply_host(smm_ctx *ctx, smm_csr *h, smm_csr *q, int flags, int64_t k, const double *x, int64_t ldx,
+                           double *y, int64_t ldy);
+/* Kernel classes of the sparse x dense product: mode 0 = rows binned by length (default), 1 / 2 / 3 = every row in the
+ * tiny / group / long class (tests).  apply_budget_bytes: bytes of smm_triple_apply's two intermediates per column block,
+ * 0 = the default, 1 GiB.  The result's shape and values never depend on either (bit for bit under SMM_EXACT). */
+int  smm_ctx_tune_spmm(smm_ctx *ctx, int mode, int64_t apply_budget_bytes);
 
 /* ------------------------------------------------------------------ device memory helpers
  * (so that hosts without torch can still hold results in HBM) */

@@ -20,6 +20,7 @@ SMM_SYMMETRIC = 1
 SMM_FULL_MATRIX = 2
 SMM_EXACT = 4
 SMM_MIRROR = 8
+SMM_TRANSPOSE = 16
 SMM_ERR_ALLOC = -3
 SMM_ERR_UNSUPPORTED = -6
 SMM_ERR_INTERNAL = -7
@@ -95,6 +96,11 @@ V2_PROTOTYPES = {
     "smm_spgemm_masked": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "smm_spgemm_masked_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "smm_ctx_tune_masked": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "smm_spmm": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
+    "smm_spmm_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
+    "smm_triple_apply": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
+    "smm_triple_apply_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
+    "smm_ctx_tune_spmm": (ctypes.c_int, [_vp, ctypes.c_int, _c_i64]),
     "smm_device_malloc": (ctypes.c_int, [_vp, _c_i64, _pp]),
     "smm_device_free": (ctypes.c_int, [_vp, _vp]),
     "smm_memcpy_d2h": (ctypes.c_int, [_vp, _vp, _vp, _c_i64]),

@@ -7,6 +7,7 @@
 #include "smm_ring.hpp"
 #include "smm_triple_sparse.hpp"
 #include "smm_masked.hpp"
+#include "smm_spmm.hpp"
 #include "../../include/smm_hip.h"
 
 #include <sys/mman.h>
@@ -95,6 +96,8 @@ struct smm_ctx {
     int narrow_idx = 1;      // 1: operands with < 65535 columns go through the symbolic phase as uint16 (column stream and lists)
     int64_t t3_max_t = (int64_t)1 << 27;   // sparse triple product: products of H[b] * Q (an upper bound of nnz(T_b)) per row block
     int masked_mode = 0;                   // masked SpGEMM: 0 per-row cost model, 1 dot path (canonical A only), 2 row path
+    int spmm_mode = 0;                     // sparse x dense: 0 rows binned by length, 1 / 2 / 3 every row in the tiny / group / long class
+    int64_t apply_budget = (int64_t)1 << 30;   // smm_triple_apply: bytes of the two intermediates of one column block
     int n_cu = 256;
     std::vector<PoolBlock> pool;          // free blocks
     std::map<void *, size_t> live;        // blocks handed out
@@ -781,7 +784,8 @@ struct smm_csr {
     int ring_npieces = 0; bool ring_spread = false; int64_t ring_bytes = 0;
     int64_t derived_bytes = 0;                   // HBM of every other cached copy (tile indices, payloads, ...)
     smm_csr *tr = nullptr;                       // H^T for the sparse triple product (pattern only: update_values leaves it)
-    smm_csr *trv = nullptr;                      // B^T with values for the masked SpGEMM's dot path (update_values drops it)
+    smm_csr *trv = nullptr;                      // A^T with values: the masked SpGEMM's dot path (B^T), the transposed sparse x dense
+                                                 // product and H^T of smm_triple_apply; built on first use, update_values drops it
 };
 
 // Rows [r0, r0 + nr) of a validated h as a borrowed operand without any of h's caches.  The row pointer is not rebased:
@@ -1462,7 +1466,7 @@ static int ensure_slab(smm_ctx *c, smm_csr *b, const SlabGeom &g, smm_csr::SlabC
 // whatever product is still running there.
 static int refresh_value_copies(smm_ctx *c, smm_csr *m)
 {
-    if (m->trv) { smm_csr_destroy(m->trv); m->trv = nullptr; }     // (rebuilt by the next masked product that needs it)
+    if (m->trv) { smm_csr_destroy(m->trv); m->trv = nullptr; }     // (rebuilt by the next product that needs it)
     for (auto &e : m->packs) {
         Geom gs; gs.nw = 1; gs.nct = e.nct; gs.wc = e.wc; gs.wf = e.wc; gs.n_ft = e.nct;
         const int *seg = nullptr;
@@ -3038,6 +3042,237 @@ extern "C" int smm_spgemm_masked_host(smm_ctx *c, smm_csr *a, smm_csr *b, smm_cs
     CHK(download(c, c_data, d, (size_t)mask->nnz * sizeof(double)));
     (void)hipStreamSynchronize(c->stream);
     return SMM_OK;
+}
+
+// ------------------------------------------------------------------------------ sparse x dense: Y = op(A) * X
+extern "C" int smm_ctx_tune_spmm(smm_ctx *c, int mode, int64_t apply_budget_bytes)
+{
+    if (!c || mode < 0 || mode > 3 || apply_budget_bytes < 0)
+        return fail(SMM_ERR_INVALID, "bad argument (mode: 0 auto, 1 tiny, 2 group, 3 long; apply_budget_bytes >= 0)");
+    CTX_LOCK(c);
+    c->spmm_mode = mode;
+    c->apply_budget = apply_budget_bytes > 0 ? apply_budget_bytes : (int64_t)1 << 30;
+    return SMM_OK;
+}
+
+// op(A) as a CSR: A, or A^T -- the transpose cached on A's handle (built on first use, dropped by a value update).
+static int spmm_op(smm_ctx *c, smm_csr *a, bool transpose, const smm_csr **out)
+{
+    if (transpose && !a->trv) CHK(transpose_impl(c, a, &a->trv));
+    *out = transpose ? a->trv : a;
+    return SMM_OK;
+}
+
+// Y = op X on the context's stream, no synchronisation (validated op; k, ldx, ldy checked by the caller).  Rows are binned
+// by length and each class goes to its kernel (smm_spmm.hpp); every row of Y gets columns [0, k) written, nothing else.
+static int spmm_impl(smm_ctx *c, const smm_csr *op, bool exact, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy)
+{
+    const int64_t m = op->rows;
+    if (m == 0 || k == 0) return SMM_OK;
+    PoolBuf<int> lists(c);
+    CHK(lists.alloc((size_t)SP_NCLS * m + 8));
+    int *cnt = lists + (size_t)SP_NCLS * m;
+    HIPCHK(hipMemsetAsync(cnt, 0, 8 * sizeof(int), c->stream));
+    LAUNCH(c, "smm_spmm_bin", smm_spmm_bin, std::min<int64_t>((m + 255) / 256, 4096), 256, 0, (int)m, op->ptr, k, c->spmm_mode, lists, cnt);
+    LAUNCH_CHECK();
+    int hc[8] = {0};
+    HIPCHK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    SpmmArgs A{};
+    A.m = (int)m; A.K = (int)op->cols; A.nnz = (int)op->nnz;
+    A.ptr = op->ptr; A.idx = op->idx; A.val = op->val;
+    A.k = k; A.ldx = ldx; A.ldy = ldy; A.x = x; A.y = y; A.err = c->d_err;
+    // 16-byte loads and stores of X and Y where every lane's pair of columns is aligned
+    const int vec = (k % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0) ? 2 : 1;
+    int gk = 4;                                        // lanes per row of the group class: one per VEC columns, 4 .. 64
+    while (gk < WAVE && (int64_t)gk * vec < k) gk *= 2;
+    const int64_t cap = (int64_t)c->n_cu * 32;         // workgroups of the grid-stride kernels
+    auto rows_grid = [&](int nrows, int rows_per_wave) {
+        return std::max<int64_t>(1, std::min<int64_t>(((int64_t)nrows + 4 * rows_per_wave - 1) / (4 * rows_per_wave), cap));
+    };
+    for (int cl = 0; cl < SP_NCLS; ++cl) {
+        if (hc[cl] <= 0) continue;
+        A.rowlist = lists + (size_t)cl * m; A.nrows = hc[cl];
+        const bool split = cl == SP_LONG && !exact;    // (SMM_EXACT: one wave walks a long row in order)
+        if (k == 1) {
+            if (split) {
+                LAUNCH(c, "smm_spmv_long", smm_spmv_long<SP_LONG_WAVES>, std::min<int64_t>(hc[cl], cap), SP_LONG_WAVES * WAVE, 0, A);
+            } else if (cl == SP_TINY) {
+                if (exact) LAUNCH(c, "smm_spmv_group", (smm_spmv_group<16, true>), rows_grid(hc[cl], 4), 256, 0, A);
+                else       LAUNCH(c, "smm_spmv_group", (smm_spmv_group<16, false>), rows_grid(hc[cl], 4), 256, 0, A);
+            } else {
+                if (exact) LAUNCH(c, "smm_spmv_group", (smm_spmv_group<64, true>), rows_grid(hc[cl], 1), 256, 0, A);
+                else       LAUNCH(c, "smm_spmv_group", (smm_spmv_group<64, false>), rows_grid(hc[cl], 1), 256, 0, A);
+            }
+        } else if (split) {
+            const int64_t ntiles = (k + (int64_t)WAVE * vec - 1) / ((int64_t)WAVE * vec);
+            if (ntiles > INT32_MAX) return fail(SMM_ERR_INVALID, "smm_spmm: k too large");
+            const int64_t grid = std::min<int64_t>((int64_t)hc[cl] * ntiles, cap);
+            if (vec == 2) LAUNCH(c, "smm_spmm_long", (smm_spmm_long<2, SP_LONG_WAVES>), grid, SP_LONG_WAVES * WAVE, 0, A, (int)ntiles);
+            else          LAUNCH(c, "smm_spmm_long", (smm_spmm_long<1, SP_LONG_WAVES>), grid, SP_LONG_WAVES * WAVE, 0, A, (int)ntiles);
+        } else {
+            const int g = cl == SP_TINY ? 4 : (cl == SP_LONG ? WAVE : gk);
+            const int64_t grid = rows_grid(hc[cl], WAVE / g);
+#define SPMM_GROUP(G_, V_)                                                                                                    \
+    if (g == G_ && vec == V_) {                                                                                               \
+        if (exact) LAUNCH(c, "smm_spmm_group", (smm_spmm_group<G_, V_, true>), grid, 256, 0, A);                              \
+        else       LAUNCH(c, "smm_spmm_group", (smm_spmm_group<G_, V_, false>), grid, 256, 0, A);                             \
+    }
+            SPMM_GROUP(4, 1) SPMM_GROUP(8, 1) SPMM_GROUP(16, 1) SPMM_GROUP(32, 1) SPMM_GROUP(64, 1)
+            SPMM_GROUP(4, 2) SPMM_GROUP(8, 2) SPMM_GROUP(16, 2) SPMM_GROUP(32, 2) SPMM_GROUP(64, 2)
+#undef SPMM_GROUP
+        }
+        LAUNCH_CHECK();
+    }
+    return SMM_OK;
+}
+
+// Bytes spanned by a row-major rows x k block with leading dimension ld (0 when empty).
+static int64_t span_bytes(int64_t rows, int64_t k, int64_t ld)
+{
+    return (rows <= 0 || k <= 0) ? 0 : ((rows - 1) * ld + k) * (int64_t)sizeof(double);
+}
+static bool ranges_overlap(const void *p, int64_t pb, const void *q, int64_t qb)
+{
+    if (pb <= 0 || qb <= 0) return false;
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
+}
+
+// Arguments common to smm_spmm[_host]: flags, operand, sizes.
+static int spmm_args(smm_ctx *c, smm_csr *a, int flags, int64_t k, int64_t ldx, int64_t ldy, const char *where)
+{
+    if (flags & ~(SMM_EXACT | SMM_TRANSPOSE)) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT and SMM_TRANSPOSE are flags of this call", where);
+    if (!a) return fail(SMM_ERR_INVALID, "%s: NULL operand", where);
+    if (a->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
+    if (k < 0 || ldx < k || ldy < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldx, ldy (k %lld, ldx %lld, ldy %lld)", where,
+                                                 (long long)k, (long long)ldx, (long long)ldy);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(validate(c, a));
+    return SMM_OK;
+}
+// Device buffers of Y = op X: present where they hold anything, and apart.
+static int spmm_buffers(int64_t m, int64_t kx, int64_t k, const double *x, int64_t ldx, const double *y, int64_t ldy, const char *where)
+{
+    const int64_t xb = span_bytes(kx, k, ldx), yb = span_bytes(m, k, ldy);
+    if ((xb > 0 && !x) || (yb > 0 && !y)) return fail(SMM_ERR_INVALID, "%s: X or Y is NULL", where);
+    if (ranges_overlap(x, xb, y, yb)) return fail(SMM_ERR_INVALID, "%s: the device ranges of X and Y overlap", where);
+    return SMM_OK;
+}
+
+extern "C" int smm_spmm(smm_ctx *c, smm_csr *a, int flags, int64_t k, const double *d_x, int64_t ldx, double *d_y, int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(spmm_args(c, a, flags, k, ldx, ldy, "smm_spmm"));
+    const bool tr = (flags & SMM_TRANSPOSE) != 0;
+    const int64_t m = tr ? a->cols : a->rows, kx = tr ? a->rows : a->cols;
+    CHK(spmm_buffers(m, kx, k, d_x, ldx, d_y, ldy, "smm_spmm"));
+    if (m == 0 || k == 0) return SMM_OK;
+    const smm_csr *op = nullptr;
+    CHK(spmm_op(c, a, tr, &op));
+    CHK(spmm_impl(c, op, (flags & SMM_EXACT) != 0, k, d_x, ldx, d_y, ldy));
+    return take_plan_error(c, "smm_spmm");
+}
+
+// Host rows x k (leading dimension ld) <-> packed device rows x k.
+static int upload_rows(smm_ctx *c, double *d, const double *h, int64_t rows, int64_t k, int64_t ld)
+{
+    if (rows <= 0 || k <= 0) return SMM_OK;
+    if (ld == k) HIPCHK(hipMemcpyAsync(d, h, (size_t)(rows * k) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    else HIPCHK(hipMemcpy2DAsync(d, (size_t)k * sizeof(double), h, (size_t)ld * sizeof(double), (size_t)k * sizeof(double), (size_t)rows,
+                                 hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SMM_OK;
+}
+static int download_rows(smm_ctx *c, double *h, const double *d, int64_t rows, int64_t k, int64_t ld)
+{
+    if (rows <= 0 || k <= 0) return SMM_OK;
+    if (ld == k) return download(c, h, d, (size_t)(rows * k) * sizeof(double));
+    HIPCHK(hipMemcpy2DAsync(h, (size_t)ld * sizeof(double), d, (size_t)k * sizeof(double), (size_t)k * sizeof(double), (size_t)rows,
+                            hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SMM_OK;
+}
+
+extern "C" int smm_spmm_host(smm_ctx *c, smm_csr *a, int flags, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(spmm_args(c, a, flags, k, ldx, ldy, "smm_spmm_host"));
+    const bool tr = (flags & SMM_TRANSPOSE) != 0;
+    const int64_t m = tr ? a->cols : a->rows, kx = tr ? a->rows : a->cols;
+    if ((span_bytes(kx, k, ldx) > 0 && !x) || (span_bytes(m, k, ldy) > 0 && !y)) return fail(SMM_ERR_INVALID, "smm_spmm_host: X or Y is NULL");
+    if (m == 0 || k == 0) return SMM_OK;
+    const smm_csr *op = nullptr;
+    CHK(spmm_op(c, a, tr, &op));
+    PoolBuf<double> dx(c), dy(c);
+    CHK(dx.alloc((size_t)std::max<int64_t>(kx * k, 1)));
+    CHK(dy.alloc((size_t)(m * k)));
+    CHK(upload_rows(c, dx, x, kx, k, ldx));
+    CHK(spmm_impl(c, op, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
+    CHK(take_plan_error(c, "smm_spmm_host"));
+    return download_rows(c, y, dy, m, k, ldy);
+}
+
+// Y = H (Q (H^T X)): H^T X through H's cached transpose, two pool intermediates of K x kb, X taken in column blocks of kb
+// columns so that both fit the context's apply budget (columns are independent: blocking changes no bit).
+static int triple_apply_impl(smm_ctx *c, smm_csr *h, smm_csr *q, bool exact, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy)
+{
+    const int64_t n = h->rows, K = h->cols;
+    if (n == 0 || k == 0) return SMM_OK;
+    const smm_csr *ht = nullptr;
+    CHK(spmm_op(c, h, true, &ht));
+    const int64_t kb = std::max<int64_t>(1, std::min<int64_t>(k, c->apply_budget / std::max<int64_t>(2 * K * (int64_t)sizeof(double), 1)));
+    PoolBuf<double> z1(c), z2(c);
+    CHK(z1.alloc((size_t)std::max<int64_t>(K * kb, 1)));
+    CHK(z2.alloc((size_t)std::max<int64_t>(K * kb, 1)));
+    for (int64_t j0 = 0; j0 < k; j0 += kb) {
+        const int64_t b = std::min(kb, k - j0);
+        CHK(spmm_impl(c, ht, exact, b, x + j0, ldx, z1, b));      // Z1 = H^T X[:, j0 .. j0 + b)
+        CHK(spmm_impl(c, q, exact, b, z1, b, z2, b));             // Z2 = Q Z1
+        CHK(spmm_impl(c, h, exact, b, z2, b, y + j0, ldy));       // Y[:, j0 .. j0 + b) = H Z2
+    }
+    return SMM_OK;
+}
+
+static int triple_apply_args(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t k, int64_t ldx, int64_t ldy, const char *where)
+{
+    if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call", where);
+    CHK(check_pair(c, h, q));
+    if (q->rows != q->cols) return fail(SMM_ERR_INVALID, "%s: Q must be square, got %lld x %lld", where, (long long)q->rows, (long long)q->cols);
+    if (k < 0 || ldx < k || ldy < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldx, ldy (k %lld, ldx %lld, ldy %lld)", where,
+                                                 (long long)k, (long long)ldx, (long long)ldy);
+    return SMM_OK;
+}
+
+extern "C" int smm_triple_apply(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t k, const double *d_x, int64_t ldx, double *d_y,
+                                int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(triple_apply_args(c, h, q, flags, k, ldx, ldy, "smm_triple_apply"));
+    CHK(spmm_buffers(h->rows, h->rows, k, d_x, ldx, d_y, ldy, "smm_triple_apply"));
+    CHK(triple_apply_impl(c, h, q, (flags & SMM_EXACT) != 0, k, d_x, ldx, d_y, ldy));
+    return take_plan_error(c, "smm_triple_apply");
+}
+
+extern "C" int smm_triple_apply_host(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t k, const double *x, int64_t ldx, double *y,
+                                     int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(triple_apply_args(c, h, q, flags, k, ldx, ldy, "smm_triple_apply_host"));
+    const int64_t n = h->rows;
+    if (span_bytes(n, k, std::max(ldx, ldy)) > 0 && (!x || !y)) return fail(SMM_ERR_INVALID, "smm_triple_apply_host: X or Y is NULL");
+    if (n == 0 || k == 0) return SMM_OK;
+    PoolBuf<double> dx(c), dy(c);
+    CHK(dx.alloc((size_t)(n * k)));
+    CHK(dy.alloc((size_t)(n * k)));
+    CHK(upload_rows(c, dx, x, n, k, ldx));
+    CHK(triple_apply_impl(c, h, q, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
+    CHK(take_plan_error(c, "smm_triple_apply_host"));
+    return download_rows(c, y, dy, n, k, ldy);
 }
 
 // ------------------------------------------------------------------------------ memory helpers

@@ -9,10 +9,10 @@ import threading
 
 import numpy as np
 
-from ._lib import SMM_EXACT, SMM_FULL_MATRIX, SMM_MIRROR, SMM_SYMMETRIC, SmmError, SmmLibrary, check
+from ._lib import SMM_EXACT, SMM_FULL_MATRIX, SMM_MIRROR, SMM_SYMMETRIC, SMM_TRANSPOSE, SmmError, SmmLibrary, check
 
 __all__ = ["Context", "DeviceCSR", "default_context", "SmmError",
-           "SMM_SYMMETRIC", "SMM_FULL_MATRIX", "SMM_EXACT", "SMM_MIRROR"]
+           "SMM_SYMMETRIC", "SMM_FULL_MATRIX", "SMM_EXACT", "SMM_MIRROR", "SMM_TRANSPOSE"]
 
 
 def _flags(symmetric=False, exact=False, full=False, mirror=False):
@@ -368,6 +368,80 @@ class Context:
         """spgemm_masked_host into caller-owned HBM (nnz(mask) float64 at d_ptr)."""
         check(self.lib, self.lib.smm_spgemm_masked(self.handle, a.handle, b.handle, mask.handle, _flags(False, exact),
                                                    ctypes.c_void_p(d_ptr or 0)))
+
+    # ------------------------------------------------------------------ sparse x dense
+    def tune_spmm(self, mode=0, apply_budget_bytes=0):
+        """Kernel classes of the sparse x dense product (0 rows binned by length, 1 / 2 / 3 every row in the tiny / group /
+        long class) and the bytes of triple_apply's two intermediates per column block (0 = default, 1 GiB)."""
+        check(self.lib, self.lib.smm_ctx_tune_spmm(self.handle, int(mode), int(apply_budget_bytes)))
+
+    def _sync_torch(self, t):
+        """Torch's current stream finished with t before the library reads it (csr_from_torch's rule)."""
+        import torch
+        cur = torch.cuda.current_stream(t.device)
+        if self.stream is None or int(cur.cuda_stream) != self.stream:
+            cur.synchronize()
+
+    @staticmethod
+    def _host_x(x):
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim not in (1, 2):
+            raise ValueError(f"X must be 1-D or 2-D, got {x.ndim} dimensions")
+        x = np.ascontiguousarray(x)
+        return x, (1 if x.ndim == 1 else x.shape[1])
+
+    def spmm_host(self, a, x, transpose=False, exact=False):
+        """Y = op(A) X with X a numpy array (1-D or 2-D, cast to C-contiguous float64): a numpy array of the same number
+        of dimensions (smm_spmm_host).  op(A) = A^T when transpose."""
+        x, k = self._host_x(x)
+        m, kx = (a.cols, a.rows) if transpose else (a.rows, a.cols)
+        if x.shape[0] != kx:
+            raise ValueError(f"X has {x.shape[0]} rows, op(A) has {kx} columns")
+        y = np.empty((m,) if x.ndim == 1 else (m, k), dtype=np.float64)
+        flags = _flags(exact=exact) | (SMM_TRANSPOSE if transpose else 0)
+        check(self.lib, self.lib.smm_spmm_host(self.handle, a.handle, flags, k, _ptr(x), k, _ptr(y), k))
+        return y
+
+    def spmm_into(self, a, d_x, ldx, k, d_y, ldy, transpose=False, exact=False):
+        """Y = op(A) X on device buffers: X (op(A).cols x k, leading dimension ldx) at d_x, Y (op(A).rows x k, leading
+        dimension ldy) at d_y (smm_spmm).  Ints (device addresses) or torch tensors: torch's current stream is
+        synchronised before the library reads, and the context before this returns."""
+        if hasattr(d_x, "data_ptr"):
+            self._sync_torch(d_x)
+        if hasattr(d_y, "data_ptr"):
+            self._sync_torch(d_y)
+        flags = _flags(exact=exact) | (SMM_TRANSPOSE if transpose else 0)
+        check(self.lib, self.lib.smm_spmm(self.handle, a.handle, flags, int(k), ctypes.c_void_p(_dptr(d_x)), int(ldx),
+                                          ctypes.c_void_p(_dptr(d_y)), int(ldy)))
+        self.synchronize()
+
+    def triple_apply_host(self, h, q, x, exact=False):
+        """Y = H (Q (H^T X)) with numpy X (n x k or n): the same shape back (smm_triple_apply_host)."""
+        x, k = self._host_x(x)
+        if x.shape[0] != h.rows:
+            raise ValueError(f"X has {x.shape[0]} rows, H has {h.rows}")
+        y = np.empty(x.shape, dtype=np.float64)
+        check(self.lib, self.lib.smm_triple_apply_host(self.handle, h.handle, q.handle, _flags(exact=exact), k, _ptr(x), k,
+                                                       _ptr(y), k))
+        return y
+
+    def triple_apply_into(self, h, q, d_x, ldx, k, d_y, ldy, exact=False):
+        """Y = H (Q (H^T X)) on device buffers (n x k, leading dimensions ldx / ldy; smm_triple_apply); stream rules as
+        spmm_into."""
+        if hasattr(d_x, "data_ptr"):
+            self._sync_torch(d_x)
+        if hasattr(d_y, "data_ptr"):
+            self._sync_torch(d_y)
+        check(self.lib, self.lib.smm_triple_apply(self.handle, h.handle, q.handle, _flags(exact=exact), int(k),
+                                                  ctypes.c_void_p(_dptr(d_x)), int(ldx), ctypes.c_void_p(_dptr(d_y)), int(ldy)))
+        self.synchronize()
+
+
+def _dptr(p):
+    """A device address: an int, or a torch tensor's data_ptr()."""
+    if p is None:
+        return 0
+    return int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)
 
 
 class DeviceCSR:

@@ -789,6 +789,110 @@ def masked_matrix_multiply(matrix_a, matrix_b, mask):
     return _with_leases(ctx, (matrix_a, matrix_b, mask), body)
 
 
+# ------------------------------------------------------------------ sparse x dense
+def _dense_operand(x, rows, what):
+    """(X, k, is_torch): X a float64 C-contiguous numpy array, or a float64 CUDA tensor with unit column stride; 1-D or
+    2-D with `rows` rows.  ValueError before any device work."""
+    is_torch = type(x).__module__.split(".")[0] == "torch"
+    if is_torch:
+        import torch
+        if x.dtype != torch.float64 or not x.is_cuda:
+            raise ValueError(f"{what}: a torch X must be a float64 CUDA tensor")
+        if x.dim() <= 2 and (x.stride(-1) != 1 or (x.dim() == 2 and x.stride(0) < x.shape[1])):
+            x = x.contiguous()
+    else:
+        x = np.asarray(x, dtype=np.float64)
+        x = np.ascontiguousarray(x) if x.ndim else x          # (ascontiguousarray would make a 0-d X 1-D)
+    ndim = x.dim() if is_torch else x.ndim
+    if ndim not in (1, 2):
+        raise ValueError(f"{what}: X must be 1-D or 2-D, got {ndim} dimensions")
+    if x.shape[0] != rows:
+        raise ValueError(f"{what}: X has {x.shape[0]} rows, expected {rows}")
+    return x, (1 if ndim == 1 else int(x.shape[1])), is_torch
+
+
+def _dense_apply(ctx, x, k, is_torch, out_rows, host_call, device_call):
+    """One sparse x dense product: numpy in and out through host_call(x) -> y, or on the device (torch X, or
+    set_result_device(True)) through device_call(d_x, ldx, d_y, ldy) into a torch result."""
+    if not (is_torch or _result_device):
+        return host_call(x)
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    if not is_torch:
+        x = torch.from_numpy(x).to(dev)
+    elif x.device != dev:
+        raise ValueError(f"X is on {x.device}, the library works on {dev}")
+    y = torch.empty((out_rows,) if x.dim() == 1 else (out_rows, k), dtype=torch.float64, device=dev)
+    device_call(x, 1 if x.dim() == 1 else x.stride(0), y, k)
+    return y
+
+
+def _dense_zeros(shape, on_device):
+    if on_device:
+        import torch
+        return torch.zeros(shape, dtype=torch.float64, device=torch.device("cuda", default_context().device))
+    return np.zeros(shape, dtype=np.float64)
+
+
+def sparse_dense_multiply(matrix_a, x, transpose=False):
+    """Y = A @ X, or A.T @ X with transpose=True, for a sparse A and a dense X, on the GPU.
+
+    matrix_a : scipy CSR, anything csr_matrix() accepts, or a PinnedOperand (the operand cache applies).
+    x        : a numpy array (cast to float64, C-contiguous) or a float64 CUDA tensor on the library's device; 1-D or
+               2-D.  A 1-D X gives a 1-D result.
+    Returns numpy for numpy input; a torch tensor on the device for torch input or under set_result_device(True).
+    Under set_exact(True) the result is bit-identical to scipy's A @ X / A.T @ X (each element starts at +0.0 and adds
+    the row's products in stored order); otherwise within 1e-10 of (|A| |X|)[i, j].  A pair that row i does not store is
+    never multiplied.  A.T comes from a transpose built on the device once and kept with the operand.
+    """
+    matrix_a = _as_csr(matrix_a)
+    m, kx = matrix_a.shape[::-1] if transpose else matrix_a.shape
+    x, k, is_torch = _dense_operand(x, kx, "sparse_dense_multiply")
+    out_shape = (m,) if len(x.shape) == 1 else (m, k)
+    if matrix_a.nnz == 0 or k == 0 or m == 0:
+        return _dense_zeros(out_shape, is_torch or _result_device)
+    ctx = default_context()
+
+    def body(la):
+        a = la.handle
+        return _dense_apply(ctx, x, k, is_torch, m,
+                            lambda xh: ctx.spmm_host(a, xh, transpose=transpose, exact=_exact),
+                            lambda dx, ldx, dy, ldy: ctx.spmm_into(a, dx, ldx, k, dy, ldy, transpose=transpose, exact=_exact))
+
+    return _with_leases(ctx, (matrix_a,), body)
+
+
+def triple_product_apply(matrix_h, matrix_q, x):
+    """Y = H @ (Q @ (H.T @ X)) = S X with S = H Q H^T never formed, on the GPU.
+
+    matrix_h : n x K, matrix_q : K x K (need not be symmetric); scipy CSR, anything csr_matrix() accepts, or a
+    PinnedOperand.  x : n x k or n, as in sparse_dense_multiply (numpy or a float64 CUDA tensor).  Returns the same kind
+    and shape as x (a torch tensor under set_result_device(True)).  Under set_exact(True) bit-identical to scipy's
+    H @ (Q @ (H.T @ X)); otherwise within rounding.  X is processed in column blocks whose two K x block intermediates fit
+    the context's budget (Context.tune_spmm; blocking changes no bit).
+    """
+    matrix_h = _as_csr(matrix_h)
+    matrix_q = _as_csr(matrix_q)
+    if matrix_q.shape[0] != matrix_q.shape[1]:
+        raise ValueError(f"triple_product_apply: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
+    if matrix_h.shape[1] != matrix_q.shape[0]:
+        raise ValueError("Matrix dimensions are incompatible for multiplication.")
+    n = matrix_h.shape[0]
+    x, k, is_torch = _dense_operand(x, n, "triple_product_apply")
+    out_shape = (n,) if len(x.shape) == 1 else (n, k)
+    if matrix_h.nnz == 0 or matrix_q.nnz == 0 or k == 0 or n == 0:
+        return _dense_zeros(out_shape, is_torch or _result_device)
+    ctx = default_context()
+
+    def body(lh, lq):
+        h, q = lh.handle, lq.handle
+        return _dense_apply(ctx, x, k, is_torch, n,
+                            lambda xh: ctx.triple_apply_host(h, q, xh, exact=_exact),
+                            lambda dx, ldx, dy, ldy: ctx.triple_apply_into(h, q, dx, ldx, k, dy, ldy, exact=_exact))
+
+    return _with_leases(ctx, (matrix_h, matrix_q), body)
+
+
 def _triple_masked(matrix_h, matrix_q, mask, out_shape, full):
     _check_mask_shape(mask, out_shape, "sparse_triple_product")
     if mask.nnz == 0:
