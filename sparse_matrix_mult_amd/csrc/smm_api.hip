@@ -2715,6 +2715,42 @@ extern "C" int smm_result_download(smm_ctx *c, smm_result *r, int64_t *indptr, v
     return SMM_OK;
 }
 
+// ------------------------------------------------------------------------------ row classes (triple, masked, sparse x dense)
+// Rows sorted into class lists on the device: list(c) holds count[c] rows of class c (at most 8 classes).  One pool
+// block holds the lists and the counts; bin(lists, counts) launches the caller's binning kernels on the zeroed counts,
+// and the counts come down with one synchronisation.
+struct ClassLists {
+    PoolBuf<int> buf;
+    int64_t m = 0;
+    int count[8] = {0};
+    explicit ClassLists(smm_ctx *c) : buf(c) {}
+    int *list(int cls) const { return buf + (size_t)cls * m; }
+};
+template <typename Bin> static int bin_rows(smm_ctx *c, int64_t m, int ncls, ClassLists &out, Bin bin)
+{
+    out.m = m;
+    CHK(out.buf.alloc((size_t)ncls * m + 8));
+    int *cnt = out.buf + (size_t)ncls * m;
+    HIPCHK(hipMemsetAsync(cnt, 0, 8 * sizeof(int), c->stream));
+    bin((int *)out.buf, cnt);
+    LAUNCH_CHECK();
+    HIPCHK(hipMemcpyAsync(out.count, cnt, sizeof(out.count), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SMM_OK;
+}
+// Workgroups of a global class, each with one zeroed row of row_bytes in HBM: at most one per CU and 256 MB of rows in
+// flight.
+static int64_t global_grid(const smm_ctx *c, int64_t nrows, int64_t row_bytes)
+{
+    return std::max<int64_t>(1, std::min<int64_t>({nrows, (int64_t)c->n_cu, ((int64_t)1 << 28) / std::max<int64_t>(row_bytes, 1)}));
+}
+// Opt-in of a kernel to `lds` bytes of dynamic LDS (the workgroup hash classes).
+template <typename Kern> static int lds_opt_in(Kern kern, size_t lds)
+{
+    HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return SMM_OK;
+}
+
 // One row block [b0, b1) of H (global rows): T_b = H[b] * Q, the pattern of its rows of S (k >= i, ascending), their values.
 // With a mask (canonical, n x n) the pattern is the mask's rows [b0, b1) filtered to k >= i: no H^T, no stage-2 symbolic
 // phase, no sort.
@@ -2728,8 +2764,9 @@ static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, 
     std::unique_ptr<smm_csr, Destroyer<smm_csr_destroy>> tb;
     int64_t tnnz = 0, snnz = 0;
     PoolBuf<int64_t> tptr(c), sptr(c);
-    PoolBuf<int> tidx(c), tptr32(c), lists(c), mcnt(c), sidx(c);
+    PoolBuf<int> tidx(c), tptr32(c), mcnt(c), sidx(c);
     PoolBuf<double> tval(c), dense(c), sval(c);
+    ClassLists bins(c);
     // stage 1: T_b, the engine's SpGEMM (first-touch rows, SMM_EXACT values in the reference's order)
     const bool zero = h->nnz == 0 || q->nnz == 0;       // (masked only: S is the mask's pattern filled with +0.0)
     smm_plan *pp = nullptr;
@@ -2774,14 +2811,11 @@ static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, 
     }
     // stage 2, values: rows binned by the length of T_i
     if (snnz > 0) {
-        CHK(lists.alloc((size_t)3 * nb + 4));
-        int *cnt = lists + 3 * nb;
-        HIPCHK(hipMemsetAsync(cnt, 0, 4 * sizeof(int), c->stream));
-        LAUNCH(c, "smm_triple_sparse_bin", smm_triple_sparse_bin, std::min<int64_t>((nb + 255) / 256, 4096), 256, 0, (int)nb,
-               (const int64_t *)tptr, (const int64_t *)sptr, lists, cnt);
-        int hc[4] = {0, 0, 0, 0};
-        HIPCHK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        CHK(bin_rows(c, nb, 3, bins, [&](int *lists, int *cnt) {
+            LAUNCH(c, "smm_triple_sparse_bin", smm_triple_sparse_bin, std::min<int64_t>((nb + 255) / 256, 4096), 256, 0, (int)nb,
+                   (const int64_t *)tptr, (const int64_t *)sptr, lists, cnt);
+        }));
+        const int *hc = bins.count;
         Triple3Args A{};
         A.m = (int)nb; A.row0 = b0;
         A.t_ptr = tptr; A.t_idx = tidx; A.t_val = tval;
@@ -2789,24 +2823,24 @@ static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, 
         A.h_ptr = h->ptr; A.h_idx = h->idx; A.h_val = h->val; A.n = (int)n; A.K = (int)K;
         A.err = c->d_err;
         if (hc[0] > 0) {            // one wave per row, four rows per workgroup
-            A.rowlist = lists; A.nrows = hc[0];
-            const size_t lds = (size_t)4 * 512 * (sizeof(double) + sizeof(int));
+            A.rowlist = bins.list(0); A.nrows = hc[0];
+            const size_t lds = t3_hash_lds<WaveHash>();
             const int grid = (int)std::min<int64_t>((hc[0] + 3) / 4, (int64_t)c->n_cu * 16);
-            if (exact) LAUNCH(c, "smm_triple_sparse_s2", (smm_triple_sparse_s2_hash<512, 9, 64, 4, false>), grid, 256, lds, A);
-            else       LAUNCH(c, "smm_triple_sparse_s2", (smm_triple_sparse_s2_hash<512, 9, 64, 4, true>), grid, 256, lds, A);
+            if (exact) LAUNCH(c, "smm_triple_sparse_s2", (t3_hash_kernel<WaveHash, false>), grid, 256, lds, A);
+            else       LAUNCH(c, "smm_triple_sparse_s2", (t3_hash_kernel<WaveHash, true>), grid, 256, lds, A);
             LAUNCH_CHECK();
         }
         if (hc[1] > 0) {            // one workgroup per row
-            A.rowlist = lists + nb; A.nrows = hc[1];
-            const size_t lds = (size_t)8192 * (sizeof(double) + sizeof(int));
-            auto kern = exact ? smm_triple_sparse_s2_hash<8192, 13, 256, 1, false> : smm_triple_sparse_s2_hash<8192, 13, 256, 1, true>;
-            HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            A.rowlist = bins.list(1); A.nrows = hc[1];
+            const size_t lds = t3_hash_lds<WgHash>();
+            auto kern = exact ? t3_hash_kernel<WgHash, false> : t3_hash_kernel<WgHash, true>;
+            CHK(lds_opt_in(kern, lds));
             LAUNCH(c, "smm_triple_sparse_s2", kern, std::min<int64_t>(hc[1], (int64_t)c->n_cu), 256, lds, A);
             LAUNCH_CHECK();
         }
         if (hc[2] > 0) {            // a zeroed global row of K doubles per workgroup, a bounded number in flight
-            A.rowlist = lists + 2 * nb; A.nrows = hc[2];
-            const int64_t grid = std::max<int64_t>(1, std::min<int64_t>({(int64_t)hc[2], (int64_t)c->n_cu, ((int64_t)1 << 28) / (8 * K)}));
+            A.rowlist = bins.list(2); A.nrows = hc[2];
+            const int64_t grid = global_grid(c, hc[2], 8 * K);
             CHK(dense.alloc((size_t)grid * (size_t)K));
             HIPCHK(hipMemsetAsync(dense, 0, (size_t)grid * (size_t)K * sizeof(double), c->stream));
             A.dense = dense;
@@ -2939,18 +2973,15 @@ static int masked_impl(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int fl
     const bool a_canonical = !(a->vflags & (CSR_UNSORTED | CSR_HAS_EQUAL));
     const bool dot = a_canonical && c->masked_mode != 2;
     if (dot && !b->trv) CHK(transpose_impl(c, b, &b->trv));
-    PoolBuf<int> cls(c), lists(c), map(c);
-    CHK(cls.alloc((size_t)m + 8));
-    CHK(lists.alloc((size_t)MK_NCLS * m));
-    int *cnt = cls + m;
-    HIPCHK(hipMemsetAsync(cnt, 0, 8 * sizeof(int), c->stream));
-    LAUNCH(c, "smm_masked_cost", smm_masked_cost, std::min<int64_t>((m + 3) / 4, 16384), 256, 0, (int)m, mask->ptr, mask->idx, a->ptr, a->idx,
-           b->ptr, (int)b->rows, dot ? (const int *)b->trv->ptr : nullptr, (int)b->cols, c->masked_mode, cls);
-    LAUNCH(c, "smm_masked_bin", smm_masked_bin, std::min<int64_t>((m + 255) / 256, 4096), 256, 0, (int)m, (const int *)cls, lists, cnt);
-    LAUNCH_CHECK();
-    int hc[8] = {0};
-    HIPCHK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    PoolBuf<int> cls(c), map(c);
+    ClassLists bins(c);
+    CHK(cls.alloc((size_t)m));
+    CHK(bin_rows(c, m, MK_NCLS, bins, [&](int *lists, int *cnt) {
+        LAUNCH(c, "smm_masked_cost", smm_masked_cost, std::min<int64_t>((m + 3) / 4, 16384), 256, 0, (int)m, mask->ptr, mask->idx, a->ptr,
+               a->idx, b->ptr, (int)b->rows, dot ? (const int *)b->trv->ptr : nullptr, (int)b->cols, c->masked_mode, cls);
+        LAUNCH(c, "smm_masked_bin", smm_masked_bin, std::min<int64_t>((m + 255) / 256, 4096), 256, 0, (int)m, (const int *)cls, lists, cnt);
+    }));
+    const int *hc = bins.count;
     MaskedArgs A{};
     A.m = (int)m;
     A.a_ptr = a->ptr; A.a_idx = a->idx; A.a_val = a->val; A.K = (int)a->cols;
@@ -2962,38 +2993,26 @@ static int masked_impl(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int fl
     // dot path: lanes per mask entry, the mean length of a row of B^T rounded up to a power of two in [4, 64]
     int dot_g = 4;
     while (dot_g < WAVE && (int64_t)dot_g * b->cols < b->nnz) dot_g *= 2;
-    auto wg_kernel = [&](const void *kern, size_t lds) -> hipError_t {
-        return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    };
-    // global classes: one zeroed row of `width` ints per workgroup, at most 256 MB of them in flight
-    auto global_grid = [&](int nrows, int64_t width) {
-        return std::max<int64_t>(1, std::min<int64_t>({(int64_t)nrows, (int64_t)c->n_cu, ((int64_t)1 << 26) / std::max<int64_t>(width, 1)}));
-    };
     for (int cl = 0; cl < MK_NCLS; ++cl) {
         if (hc[cl] <= 0) continue;
-        A.rowlist = lists + (size_t)cl * m; A.nrows = hc[cl];
+        A.rowlist = bins.list(cl); A.nrows = hc[cl];
         if (cl == MK_DOT_WAVE) {               // one wave per row, four rows per workgroup
-            const size_t lds = (size_t)4 * 512 * 2 * sizeof(int);
             const int64_t grid = std::min<int64_t>((hc[cl] + 3) / 4, (int64_t)c->n_cu * 16);
-            LAUNCH(c, "smm_masked_dot", (smm_masked_dot_hash<512, 9, 64, 4>), grid, 256, lds, A, dot_g);
+            LAUNCH(c, "smm_masked_dot", mk_dot_kernel<WaveHash>, grid, 256, mk_dot_lds<WaveHash>(), A, dot_g);
         } else if (cl == MK_DOT_WG) {          // one workgroup per row
-            const size_t lds = (size_t)8192 * 2 * sizeof(int);
-            auto kern = smm_masked_dot_hash<8192, 13, 256, 1>;
-            HIPCHK(wg_kernel((const void *)kern, lds));
-            LAUNCH(c, "smm_masked_dot", kern, std::min<int64_t>(hc[cl], (int64_t)c->n_cu * 2), 256, lds, A, dot_g);
+            CHK(lds_opt_in(mk_dot_kernel<WgHash>, mk_dot_lds<WgHash>()));
+            LAUNCH(c, "smm_masked_dot", mk_dot_kernel<WgHash>, std::min<int64_t>(hc[cl], (int64_t)c->n_cu * 2), 256, mk_dot_lds<WgHash>(), A, dot_g);
         } else if (cl == MK_ROW_WAVE) {
-            const size_t lds = (size_t)4 * 512 * (sizeof(double) + sizeof(int) + 1);
             const int64_t grid = std::min<int64_t>((hc[cl] + 3) / 4, (int64_t)c->n_cu * 16);
-            if (exact) LAUNCH(c, "smm_masked_row", (smm_masked_row_hash<512, 9, 64, 4, true>), grid, 256, lds, A);
-            else       LAUNCH(c, "smm_masked_row", (smm_masked_row_hash<512, 9, 64, 4, false>), grid, 256, lds, A);
+            if (exact) LAUNCH(c, "smm_masked_row", (mk_row_kernel<WaveHash, true>), grid, 256, mk_row_lds<WaveHash>(), A);
+            else       LAUNCH(c, "smm_masked_row", (mk_row_kernel<WaveHash, false>), grid, 256, mk_row_lds<WaveHash>(), A);
         } else if (cl == MK_ROW_WG) {
-            const size_t lds = (size_t)8192 * (sizeof(double) + sizeof(int) + 1);
-            auto kern = exact ? smm_masked_row_hash<8192, 13, 256, 1, true> : smm_masked_row_hash<8192, 13, 256, 1, false>;
-            HIPCHK(wg_kernel((const void *)kern, lds));
-            LAUNCH(c, "smm_masked_row", kern, std::min<int64_t>(hc[cl], (int64_t)c->n_cu), 256, lds, A);
-        } else {                               // MK_DOT_GLOBAL / MK_ROW_GLOBAL
+            auto kern = exact ? mk_row_kernel<WgHash, true> : mk_row_kernel<WgHash, false>;
+            CHK(lds_opt_in(kern, mk_row_lds<WgHash>()));
+            LAUNCH(c, "smm_masked_row", kern, std::min<int64_t>(hc[cl], (int64_t)c->n_cu), 256, mk_row_lds<WgHash>(), A);
+        } else {                               // MK_DOT_GLOBAL / MK_ROW_GLOBAL: one zeroed row of `width` ints per workgroup
             const int64_t width = cl == MK_DOT_GLOBAL ? a->cols : b->cols;
-            const int64_t grid = global_grid(hc[cl], width);
+            const int64_t grid = global_grid(c, hc[cl], width * (int64_t)sizeof(int));
             CHK(map.alloc((size_t)grid * (size_t)width));      // (the previous class's map goes back to the pool first)
             HIPCHK(hipMemsetAsync(map, 0, (size_t)grid * (size_t)width * sizeof(int), c->stream));
             A.map = map;
@@ -3007,7 +3026,7 @@ static int masked_impl(smm_ctx *c, smm_csr *a, smm_csr *b, smm_csr *mask, int fl
         LAUNCH_CHECK();
     }
     (void)hipStreamSynchronize(c->stream);
-    cls.reset(); lists.reset(); map.reset();
+    cls.reset(); bins.buf.reset(); map.reset();
     return take_plan_error(c, "smm_spgemm_masked");
 }
 
@@ -3069,15 +3088,11 @@ static int spmm_impl(smm_ctx *c, const smm_csr *op, bool exact, int64_t k, const
 {
     const int64_t m = op->rows;
     if (m == 0 || k == 0) return SMM_OK;
-    PoolBuf<int> lists(c);
-    CHK(lists.alloc((size_t)SP_NCLS * m + 8));
-    int *cnt = lists + (size_t)SP_NCLS * m;
-    HIPCHK(hipMemsetAsync(cnt, 0, 8 * sizeof(int), c->stream));
-    LAUNCH(c, "smm_spmm_bin", smm_spmm_bin, std::min<int64_t>((m + 255) / 256, 4096), 256, 0, (int)m, op->ptr, k, c->spmm_mode, lists, cnt);
-    LAUNCH_CHECK();
-    int hc[8] = {0};
-    HIPCHK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    ClassLists bins(c);
+    CHK(bin_rows(c, m, SP_NCLS, bins, [&](int *lists, int *cnt) {
+        LAUNCH(c, "smm_spmm_bin", smm_spmm_bin, std::min<int64_t>((m + 255) / 256, 4096), 256, 0, (int)m, op->ptr, k, c->spmm_mode, lists, cnt);
+    }));
+    const int *hc = bins.count;
     SpmmArgs A{};
     A.m = (int)m; A.K = (int)op->cols; A.nnz = (int)op->nnz;
     A.ptr = op->ptr; A.idx = op->idx; A.val = op->val;
@@ -3092,7 +3107,7 @@ static int spmm_impl(smm_ctx *c, const smm_csr *op, bool exact, int64_t k, const
     };
     for (int cl = 0; cl < SP_NCLS; ++cl) {
         if (hc[cl] <= 0) continue;
-        A.rowlist = lists + (size_t)cl * m; A.nrows = hc[cl];
+        A.rowlist = bins.list(cl); A.nrows = hc[cl];
         const bool split = cl == SP_LONG && !exact;    // (SMM_EXACT: one wave walks a long row in order)
         if (k == 1) {
             if (split) {

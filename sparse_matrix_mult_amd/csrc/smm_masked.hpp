@@ -18,12 +18,10 @@
 // acc = a*b) next to a touched flag; a mask position no product reaches is written as +0.0.  A pair (k, j) that A_i
 // does not store is never multiplied, so an inf in B cannot leak into C through a missing A[i,k].
 #pragma once
-#include "smm_kernels.hpp"
+#include "smm_rowclass.hpp"
 
 namespace smm {
 
-constexpr int MK_WAVE_MAX = 256;       // entries held by a wave's hash (512 slots)
-constexpr int MK_WG_MAX = 4096;        // ... by a workgroup's hash (8192 slots)
 constexpr int MK_TOUCH = 1 << 30;      // row-global slot map: "some product reached this slot"
 enum { MK_DOT_WAVE = 0, MK_DOT_WG = 1, MK_DOT_GLOBAL = 2, MK_ROW_WAVE = 3, MK_ROW_WG = 4, MK_ROW_GLOBAL = 5, MK_NCLS = 6 };
 
@@ -40,7 +38,6 @@ struct MaskedArgs {
     unsigned *err;
 };
 
-__device__ __forceinline__ unsigned mk_hash(int key, int bits) { return ((unsigned)key * 2654435761u) >> (32 - bits); }
 __device__ __forceinline__ int mk_clamp(int v, int hi) { return v < 0 ? 0 : (v >= hi ? hi - 1 : v); }
 
 // ------------------------------------------------------------------------------ cost model and binning
@@ -72,27 +69,17 @@ __global__ __launch_bounds__(256) void smm_masked_cost(int m, const int *__restr
             dot = dc + al <= rc;
         }
         if (lane == 0)
-            cls[r] = dot ? (al <= MK_WAVE_MAX ? MK_DOT_WAVE : (al <= MK_WG_MAX ? MK_DOT_WG : MK_DOT_GLOBAL))
-                         : (ml <= MK_WAVE_MAX ? MK_ROW_WAVE : (ml <= MK_WG_MAX ? MK_ROW_WG : MK_ROW_GLOBAL));
+            cls[r] = dot ? (al <= WaveHash::MAX ? MK_DOT_WAVE : (al <= WgHash::MAX ? MK_DOT_WG : MK_DOT_GLOBAL))
+                         : (ml <= WaveHash::MAX ? MK_ROW_WAVE : (ml <= WgHash::MAX ? MK_ROW_WG : MK_ROW_GLOBAL));
     }
 }
 
-// lists[c*m ..] = rows of class c, counts[c]; one atomic per wave and class (as smm_triple_sparse_bin).
+// lists[c*m ..] = rows of class c, counts[c]; one atomic per wave and class.
 __global__ __launch_bounds__(256) void smm_masked_bin(int m, const int *__restrict__ cls, int *__restrict__ lists, int *__restrict__ counts)
 {
-    const int lane = lane_id();
     for (int r0 = blockIdx.x * blockDim.x; r0 < m; r0 += gridDim.x * blockDim.x) {     // (uniform over the block)
         const int r = r0 + (int)threadIdx.x;
-        const int b = r < m ? cls[r] : -1;
-        for (int c = 0; c < MK_NCLS; ++c) {
-            const unsigned long long mask = __ballot(b == c);
-            if (!mask) continue;
-            const int leader = __ffsll((long long)mask) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(&counts[c], __popcll(mask));
-            base = __shfl(base, leader);
-            if (b == c) lists[(int64_t)c * m + base + __popcll(mask & ((1ull << lane) - 1ull))] = r;
-        }
+        class_list_append(r < m ? cls[r] : -1, MK_NCLS, m, r, lists, counts);
     }
 }
 
@@ -136,48 +123,39 @@ __device__ __forceinline__ void mk_dot_values(const MaskedArgs &A, int r, int t,
     }
 }
 
-// A_i in an LDS hash k -> source position: HS slots per row group of TPR threads, RPB row groups per workgroup.
-// Dynamic LDS: RPB * HS * 8 bytes.
+// A_i in an LDS hash k -> source position: HS slots per row group of TPR threads, RPB row groups per workgroup;
+// dynamic LDS mk_dot_lds<H>().
 template <int HS, int BITS, int TPR, int RPB>
 __global__ __launch_bounds__(TPR * RPB) void smm_masked_dot_hash(const MaskedArgs A, int G)
 {
-    static_assert((1 << BITS) == HS, "hash size");
     extern __shared__ int mk_dlds[];
     const int g = threadIdx.x / TPR, t = threadIdx.x % TPR;
-    int *hk = mk_dlds + (size_t)g * 2 * HS, *hp = hk + HS;
+    const LdsHash<HS, BITS> h{mk_dlds + (size_t)g * 2 * HS};
+    int *hp = h.key + HS;
     for (int base = blockIdx.x * RPB; base < A.nrows; base += gridDim.x * RPB) {     // (uniform over the block)
         const int li = base + g;
         const bool have = li < A.nrows;
         const int r = have ? mk_row(A, li) : 0;
-        for (int s = t; s < HS; s += TPR) hk[s] = -1;
+        h.clear(t, TPR);
         __syncthreads();
         const int a0 = A.a_ptr[r];
         int al = A.a_ptr[r + 1] - a0;
         if (al > HS / 2) { if (have && t == 0) plan_err(A.err, PLAN_ERR_HASH, r); al = HS / 2; }
         if (have) {
             for (int e = t; e < al; e += TPR) {
-                const int k = A.a_idx[a0 + e];
-                unsigned s = mk_hash(k, BITS);
-                for (int probe = 0; probe < HS; ++probe, s = (s + 1) & (HS - 1)) {
-                    const int prev = atomicCAS(&hk[s], -1, k);
-                    if (prev == -1 || prev == k) { hp[s] = a0 + e; break; }
-                }
+                const int s = h.insert(A.a_idx[a0 + e]);
+                if (s >= 0) hp[s] = a0 + e;
             }
         }
         __syncthreads();
         if (have)
-            mk_dot_values(A, r, t, TPR, G, [&](int k) -> int {
-                unsigned s = mk_hash(k, BITS);
-                for (int probe = 0; probe < HS; ++probe, s = (s + 1) & (HS - 1)) {
-                    const int kk = hk[s];
-                    if (kk == k) return hp[s];
-                    if (kk == -1) break;
-                }
-                return -1;
-            });
+            mk_dot_values(A, r, t, TPR, G, [&](int k) { return h.find(k, -1, [&](int s) { return hp[s]; }); });
         __syncthreads();
     }
 }
+// Its instance for hash class H and its dynamic LDS: per row, HS keys then HS source positions.
+template <class H> constexpr auto mk_dot_kernel = smm_masked_dot_hash<H::HS, H::BITS, H::TPR, H::RPB>;
+template <class H> constexpr size_t mk_dot_lds() { return (size_t)H::RPB * H::HS * 2 * sizeof(int); }
 
 // Long A_i: source positions + 1 scattered into this workgroup's zeroed row of K ints, put back to zero afterwards.
 __global__ __launch_bounds__(256) void smm_masked_dot_global(const MaskedArgs A, int G)
@@ -197,45 +175,28 @@ __global__ __launch_bounds__(256) void smm_masked_dot_global(const MaskedArgs A,
 
 // ------------------------------------------------------------------------------ row path
 // M_i in an LDS hash column -> accumulator (-0.0) + touched byte: HS slots per row group of TPR threads, RPB row groups
-// per workgroup.  Dynamic LDS: RPB * HS * 13 bytes.  A_i is walked by one wave (EXACT, or TPR == WAVE) or by all waves
+// per workgroup; dynamic LDS mk_row_lds<H>().  A_i is walked by one wave (EXACT, or TPR == WAVE) or by all waves
 // of the group, each taking every (TPR / WAVE)-th k.
 template <int HS, int BITS, int TPR, int RPB, bool EXACT>
 __global__ __launch_bounds__(TPR * RPB) void smm_masked_row_hash(const MaskedArgs A)
 {
-    static_assert((1 << BITS) == HS, "hash size");
     extern __shared__ double mk_rlds[];
     const int g = threadIdx.x / TPR, t = threadIdx.x % TPR;
     const int lane = t % WAVE, w = t / WAVE, nw = EXACT ? 1 : TPR / WAVE;
     double *hv = mk_rlds + (size_t)g * HS;
-    int *hk = (int *)(mk_rlds + (size_t)RPB * HS) + (size_t)g * HS;
+    const LdsHash<HS, BITS> h{(int *)(mk_rlds + (size_t)RPB * HS) + (size_t)g * HS};
     unsigned char *ht = (unsigned char *)((int *)(mk_rlds + (size_t)RPB * HS) + (size_t)RPB * HS) + (size_t)g * HS;
-    auto look = [&](int col) -> int {
-        unsigned s = mk_hash(col, BITS);
-        for (int probe = 0; probe < HS; ++probe, s = (s + 1) & (HS - 1)) {
-            const int kk = hk[s];
-            if (kk == col) return (int)s;
-            if (kk == -1) break;
-        }
-        return -1;
-    };
     for (int base = blockIdx.x * RPB; base < A.nrows; base += gridDim.x * RPB) {     // (uniform over the block)
         const int li = base + g;
         const bool have = li < A.nrows;
         const int r = have ? mk_row(A, li) : 0;
-        for (int s = t; s < HS; s += TPR) { hk[s] = -1; hv[s] = -0.0; ht[s] = 0; }
+        h.clear(t, TPR, [&](int s) { hv[s] = -0.0; ht[s] = 0; });
         __syncthreads();
         const int m0 = A.m_ptr[r], m1 = A.m_ptr[r + 1];
         int ml = m1 - m0;
         if (ml > HS / 2) { if (have && t == 0) plan_err(A.err, PLAN_ERR_HASH, r); ml = HS / 2; }
         if (have) {
-            for (int q = t; q < ml; q += TPR) {
-                const int col = A.m_idx[m0 + q];
-                unsigned s = mk_hash(col, BITS);
-                for (int probe = 0; probe < HS; ++probe, s = (s + 1) & (HS - 1)) {
-                    const int prev = atomicCAS(&hk[s], -1, col);
-                    if (prev == -1 || prev == col) break;
-                }
-            }
+            for (int q = t; q < ml; q += TPR) (void)h.insert(A.m_idx[m0 + q]);
         }
         __syncthreads();
         if (have && w < nw) {
@@ -245,7 +206,7 @@ __global__ __launch_bounds__(TPR * RPB) void smm_masked_row_hash(const MaskedArg
                 const double a = A.a_val[p];
                 const int e1 = A.b_ptr[k + 1];
                 for (int e = A.b_ptr[k] + lane; e < e1; e += WAVE) {
-                    const int s = look(A.b_idx[e]);
+                    const int s = h.find(A.b_idx[e]);
                     if (s < 0) continue;
                     lds_add(&hv[s], a * A.b_val[e]);
                     ht[s] = 1;
@@ -255,12 +216,17 @@ __global__ __launch_bounds__(TPR * RPB) void smm_masked_row_hash(const MaskedArg
         __syncthreads();
         if (have)
             for (int q = m0 + t; q < m1; q += TPR) {
-                const int s = look(A.m_idx[q]);
+                const int s = h.find(A.m_idx[q]);
                 A.out[q] = (s >= 0 && ht[s]) ? hv[s] : 0.0;
             }
         __syncthreads();
     }
 }
+
+// Its instance for hash class H and its dynamic LDS: the accumulators of the RPB rows (HS doubles each), their keys,
+// their touched bytes.
+template <class H, bool EXACT> constexpr auto mk_row_kernel = smm_masked_row_hash<H::HS, H::BITS, H::TPR, H::RPB, EXACT>;
+template <class H> constexpr size_t mk_row_lds() { return (size_t)H::RPB * H::HS * (sizeof(double) + sizeof(int) + 1); }
 
 // Long mask rows: slot + 1 (| MK_TOUCH once a product lands) in this workgroup's zeroed map of n ints, accumulators in
 // the output itself.  EXACT: wave 0 alone walks A_i with plain read-modify-writes (one wave's accesses to global memory

@@ -22,7 +22,7 @@
 // Always-on clamps: a row-list entry outside [0, m), a row range outside [0, nnz) and a column outside [0, K) are
 // recorded in the context's error word (SMM_ERR_INTERNAL for the caller) and skipped -- never a fault.
 #pragma once
-#include "smm_kernels.hpp"
+#include "smm_rowclass.hpp"
 
 namespace smm {
 
@@ -46,7 +46,6 @@ struct SpmmArgs {
 __global__ __launch_bounds__(256) void smm_spmm_bin(int m, const int *__restrict__ ptr, int64_t k, int mode, int *__restrict__ lists,
                                                     int *__restrict__ counts)
 {
-    const int lane = lane_id();
     for (int r0 = blockIdx.x * blockDim.x; r0 < m; r0 += gridDim.x * blockDim.x) {     // (uniform over the block)
         const int r = r0 + (int)threadIdx.x;
         int b = -1;
@@ -56,15 +55,7 @@ __global__ __launch_bounds__(256) void smm_spmm_bin(int m, const int *__restrict
             else if (k == 1) b = len <= SP_TINY_NNZ ? SP_TINY : (len > SP_LONG_NNZ_VEC ? SP_LONG : SP_GROUP);
             else b = len > SP_LONG_NNZ_WIDE ? SP_LONG : SP_GROUP;
         }
-        for (int c = 0; c < SP_NCLS; ++c) {
-            const unsigned long long mask = __ballot(b == c);
-            if (!mask) continue;
-            const int leader = __ffsll((long long)mask) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(&counts[c], __popcll(mask));
-            base = __shfl(base, leader);
-            if (b == c) lists[(int64_t)c * m + base + __popcll(mask & ((1ull << lane) - 1ull))] = r;
-        }
+        class_list_append(b, SP_NCLS, m, r, lists, counts);
     }
 }
 

@@ -11,7 +11,7 @@
 //                  (sparse_sparse_dense.cpp:201-211), T_i looked up in an LDS hash (wave / workgroup per row) or a
 //                  zeroed global row of K doubles (rows whose T_i exceeds LDS).
 #pragma once
-#include "smm_kernels.hpp"
+#include "smm_rowclass.hpp"
 
 namespace smm {
 
@@ -136,31 +136,20 @@ __global__ __launch_bounds__(256) void smm_triple_sparse_rebase(int64_t n, const
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i] + base;
 }
 
-constexpr int T3_WAVE_MAX = 256;       // T_i entries held by a wave's hash (512 slots)
-constexpr int T3_WG_MAX = 4096;        // ... by a workgroup's hash (8192 slots: 96 KB of LDS)
 // Rows of the block with a non-empty row of S, by the length of T_i: lists[0..m) wave hash, [m..2m) workgroup hash,
 // [2m..3m) global row.  counts[0..2].  One atomic per wave and class (almost every row of a local H falls into one
 // class: per-row atomics on one counter cost 2.3 ms at 200 000 rows).
 __global__ __launch_bounds__(256) void smm_triple_sparse_bin(int m, const int64_t *__restrict__ t_ptr, const int64_t *__restrict__ s_ptr,
                                                              int *__restrict__ lists, int *__restrict__ counts)
 {
-    const int lane = lane_id();
     for (int r0 = blockIdx.x * blockDim.x; r0 < m; r0 += gridDim.x * blockDim.x) {     // (uniform over the block)
         const int r = r0 + (int)threadIdx.x;
         int b = -1;
         if (r < m && s_ptr[r + 1] != s_ptr[r]) {
             const int64_t len = t_ptr[r + 1] - t_ptr[r];
-            b = len <= T3_WAVE_MAX ? 0 : (len <= T3_WG_MAX ? 1 : 2);
+            b = len <= WaveHash::MAX ? 0 : (len <= WgHash::MAX ? 1 : 2);
         }
-        for (int cls = 0; cls < 3; ++cls) {
-            const unsigned long long mask = __ballot(b == cls);
-            if (!mask) continue;
-            const int leader = __ffsll((long long)mask) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(&counts[cls], __popcll(mask));
-            base = __shfl(base, leader);
-            if (b == cls) lists[(int64_t)cls * m + base + __popcll(mask & ((1ull << lane) - 1ull))] = r;
-        }
+        class_list_append(b, 3, m, r, lists, counts);
     }
 }
 
@@ -174,8 +163,6 @@ struct Triple3Args {
     double *dense;                      // global path: one zeroed row of K doubles per workgroup
     unsigned *err;
 };
-
-__device__ __forceinline__ unsigned t3_hash(int col, int bits) { return ((unsigned)col * 2654435761u) >> (32 - bits); }
 
 // S[i,k] for the k of row i: lanes take consecutive k, each walks H_k in stored order.  look(col) -> T[i,col] or +0.0.
 template <bool FMA, typename Look>
@@ -195,50 +182,39 @@ __device__ __forceinline__ void t3_row_values(const Triple3Args &A, int r, int t
     }
 }
 
-// LDS hash of T_i: HS slots per row group of TPR threads, RPB row groups per workgroup.  Dynamic LDS:
-// RPB * HS * (4 + 8) bytes.
+// LDS hash of T_i: HS slots per row group of TPR threads, RPB row groups per workgroup; dynamic LDS t3_hash_lds<H>().
 template <int HS, int BITS, int TPR, int RPB, bool FMA>
 __global__ __launch_bounds__(TPR * RPB) void smm_triple_sparse_s2_hash(const Triple3Args A)
 {
-    static_assert((1 << BITS) == HS, "hash size");
     extern __shared__ double t3_lds[];
     const int g = threadIdx.x / TPR, t = threadIdx.x % TPR;
     double *hv = t3_lds + (size_t)g * HS;
-    int *hk = (int *)(t3_lds + (size_t)RPB * HS) + (size_t)g * HS;
+    const LdsHash<HS, BITS> h{(int *)(t3_lds + (size_t)RPB * HS) + (size_t)g * HS};
     for (int base = blockIdx.x * RPB; base < A.nrows; base += gridDim.x * RPB) {     // (uniform over the block)
         const int li = base + g;
         const bool have = li < A.nrows;
         int r = have ? A.rowlist[li] : 0;
         if (r < 0 || r >= A.m) { plan_err(A.err, PLAN_ERR_LIST, 0); r = 0; }
-        for (int s = t; s < HS; s += TPR) hk[s] = -1;
+        h.clear(t, TPR);
         __syncthreads();
         const int64_t t0 = A.t_ptr[r];
         int64_t tl = A.t_ptr[r + 1] - t0;
         if (tl > HS / 2) { if (have && t == 0) plan_err(A.err, PLAN_ERR_HASH, (int)(A.row0 + r)); tl = HS / 2; }
         if (have) {
             for (int64_t e = t; e < tl; e += TPR) {
-                const int col = A.t_idx[t0 + e];
-                unsigned s = t3_hash(col, BITS);
-                for (int probe = 0; probe < HS; ++probe, s = (s + 1) & (HS - 1)) {
-                    const int prev = atomicCAS(&hk[s], -1, col);
-                    if (prev == -1 || prev == col) { hv[s] = A.t_val[t0 + e]; break; }
-                }
+                const int s = h.insert(A.t_idx[t0 + e]);
+                if (s >= 0) hv[s] = A.t_val[t0 + e];
             }
         }
         __syncthreads();
         if (have)
-            t3_row_values<FMA>(A, r, t, TPR, [&](int col) -> double {
-                unsigned s = t3_hash(col, BITS);
-                for (int probe = 0; probe < HS; ++probe, s = (s + 1) & (HS - 1)) {
-                    const int kk = hk[s];
-                    if (kk == col) return hv[s];
-                    if (kk == -1) break;
-                }
-                return 0.0;
-            });
+            t3_row_values<FMA>(A, r, t, TPR, [&](int col) { return h.find(col, 0.0, [&](int s) { return hv[s]; }); });
         __syncthreads();
     }
 }
+// Its instance for hash class H and its dynamic LDS: the values of the RPB rows (HS doubles each), then their keys.
+template <class H, bool FMA> constexpr auto t3_hash_kernel = smm_triple_sparse_s2_hash<H::HS, H::BITS, H::TPR, H::RPB, FMA>;
+template <class H> constexpr size_t t3_hash_lds() { return (size_t)H::RPB * H::HS * (sizeof(double) + sizeof(int)); }
 
 // Rows whose T_i exceeds LDS: T_i scattered into this workgroup's zeroed row of K doubles, put back to zero afterwards.
 template <bool FMA>

@@ -453,25 +453,43 @@ def _device_zeros(ctx, shape, sparse):
                            torch.empty(0, dtype=torch.float64, device=dev), shape)
 
 
+def _zero_result(shape, sparse=True):
+    """An all-zero product: on the device under set_result_device(True), else a scipy CSR (sparse) or numpy array."""
+    if _result_device:
+        return _device_zeros(default_context(), shape, sparse)
+    return csr_matrix(shape) if sparse else np.zeros(shape)
+
+
+def _on_device(ctx, call):
+    """call() with its result left in HBM (torch tensors).  The library works on the context's own stream: torch's
+    current stream is drained first (its allocator may hand out memory that kernels queued there still use) and the
+    context is synchronised before the result is returned -- which also reports anything the kernels' bounds clamps
+    recorded (SMM_ERR_INTERNAL)."""
+    import torch
+    torch.cuda.current_stream(torch.device("cuda", ctx.device)).synchronize()
+    out = call()
+    ctx.synchronize()
+    return out
+
+
 def _product_on_device(ctx, la, lb, triple, output_format, symmetric, compute_full_matrix):
-    """The product of two leased operands with the result left in HBM (torch tensors).  The library works on the
-    context's own stream: torch's current stream is drained first (its allocator may hand out memory that kernels
-    queued there still use) and the context is synchronised before the tensors are returned -- which also reports
-    anything the kernels' bounds clamps recorded (SMM_ERR_INTERNAL)."""
+    """The product of two leased operands with the result left in HBM (torch tensors), through _on_device."""
     import torch
     dev = torch.device("cuda", ctx.device)
     a, b = la.handle, lb.handle
-    torch.cuda.current_stream(dev).synchronize()
-    if triple:
-        mirror = compute_full_matrix == 'mirror' or (_full_symmetric and compute_full_matrix == 0)
-        out = torch.empty((a.rows, a.rows), dtype=torch.float64, device=dev)
-        ctx.triple_into(a, b, out.data_ptr(), full=(compute_full_matrix == 1), exact=_exact, mirror=mirror)
-    elif output_format == 'dense':
-        out = torch.empty((a.rows, b.cols), dtype=torch.float64, device=dev)
-        ctx.dense_into(a, b, out.data_ptr(), symmetric=symmetric, exact=_exact, mirror=symmetric and _full_symmetric)
-    elif symmetric and _full_symmetric:
-        out = DeviceCSRResult(*ctx.spgemm_mirrored_torch(a, b, exact=_exact), (a.rows, b.cols))
-    else:
+
+    def call():
+        if triple:
+            mirror = compute_full_matrix == 'mirror' or (_full_symmetric and compute_full_matrix == 0)
+            out = torch.empty((a.rows, a.rows), dtype=torch.float64, device=dev)
+            ctx.triple_into(a, b, out.data_ptr(), full=(compute_full_matrix == 1), exact=_exact, mirror=mirror)
+            return out
+        if output_format == 'dense':
+            out = torch.empty((a.rows, b.cols), dtype=torch.float64, device=dev)
+            ctx.dense_into(a, b, out.data_ptr(), symmetric=symmetric, exact=_exact, mirror=symmetric and _full_symmetric)
+            return out
+        if symmetric and _full_symmetric:
+            return DeviceCSRResult(*ctx.spgemm_mirrored_torch(a, b, exact=_exact), (a.rows, b.cols))
         plan, release = _plan_for(ctx, la, lb, symmetric, _exact)
         try:
             indptr = torch.empty(a.rows + 1, dtype=torch.int64, device=dev)
@@ -480,9 +498,9 @@ def _product_on_device(ctx, la, lb, triple, output_format, symmetric, compute_fu
             plan.numeric_into(indptr.data_ptr(), indices.data_ptr(), data.data_ptr())
         finally:
             release()
-        out = DeviceCSRResult(indptr, indices, data, (a.rows, b.cols))
-    ctx.synchronize()
-    return out
+        return DeviceCSRResult(indptr, indices, data, (a.rows, b.cols))
+
+    return _on_device(ctx, call)
 
 
 def _as_csr(x):
@@ -545,9 +563,7 @@ def sparse_matrix_multiply(matrix_a, matrix_b, output_format='sparse', symmetric
 
     out_shape = (matrix_a.shape[0], matrix_b.shape[1])
     if matrix_a.nnz == 0 or matrix_b.nnz == 0:               # reference :315-319
-        if _result_device:
-            return _device_zeros(default_context(), out_shape, output_format == 'sparse')
-        return csr_matrix(out_shape) if output_format == 'sparse' else np.zeros(out_shape)
+        return _zero_result(out_shape, output_format == 'sparse')
 
     if symmetric and out_shape[0] != out_shape[1]:           # reference :321-322
         raise ValueError("For symmetric output, the resulting matrix must be square.")
@@ -559,46 +575,28 @@ def sparse_matrix_multiply(matrix_a, matrix_b, output_format='sparse', symmetric
 
     ctx = default_context()
 
-    def product():
-        # both keys first: looking A up must not evict the entry B is about to hit
-        cached = _cache_entries > 0
-        key_a = _operand_key(matrix_a) if cached and not isinstance(matrix_a, PinnedOperand) else None
-        key_b = _operand_key(matrix_b) if cached and not isinstance(matrix_b, PinnedOperand) else None
-        la = _acquire(ctx, matrix_a, key_a, protect=(key_b[0],) if key_b else ())
-        try:
-            lb = _acquire(ctx, matrix_b, key_b)
+    def product(la, lb):
+        a, b = la.handle, lb.handle
+        if _result_device:
+            return _product_on_device(ctx, la, lb, use_triple_product, output_format, bool(symmetric), compute_full_matrix)
+        if use_triple_product:                                   # reference :325-336
+            mirror = compute_full_matrix == 'mirror' or (_full_symmetric and compute_full_matrix == 0)
+            return ctx.triple_host(a, b, full=(compute_full_matrix == 1), exact=_exact, mirror=mirror)
+        if output_format == 'sparse' and symmetric and _full_symmetric:
+            # opt-in mirror epilogue: the full symmetric CSR (row i = mirrored entries in ascending column
+            # order, then the reference's upper-triangle row in its first-touch order)
+            return _result_csr(*ctx.spgemm_host_mirrored(a, b, exact=_exact), out_shape)
+        if output_format == 'sparse':                            # reference :338-351
+            plan, release = _plan_for(ctx, la, lb, bool(symmetric), _exact)
             try:
-                a, b = la.handle, lb.handle
-                if _result_device:
-                    return _product_on_device(ctx, la, lb, use_triple_product, output_format, bool(symmetric), compute_full_matrix)
-                if use_triple_product:                           # reference :325-336
-                    mirror = compute_full_matrix == 'mirror' or (_full_symmetric and compute_full_matrix == 0)
-                    return ctx.triple_host(a, b, full=(compute_full_matrix == 1), exact=_exact, mirror=mirror)
-                if output_format == 'sparse' and symmetric and _full_symmetric:
-                    # opt-in mirror epilogue: the full symmetric CSR (row i = mirrored entries in ascending column
-                    # order, then the reference's upper-triangle row in its first-touch order)
-                    return _result_csr(*ctx.spgemm_host_mirrored(a, b, exact=_exact), out_shape)
-                if output_format == 'sparse':                    # reference :338-351
-                    plan, release = _plan_for(ctx, la, lb, bool(symmetric), _exact)
-                    try:
-                        indptr, indices, data = plan.numeric_host()
-                    finally:
-                        release()
-                    return _result_csr(indptr, indices, data, out_shape)
-                return ctx.dense_host(a, b, symmetric=bool(symmetric), exact=_exact,  # reference :353-365
-                                      mirror=bool(symmetric) and _full_symmetric)
+                indptr, indices, data = plan.numeric_host()
             finally:
-                lb.release()
-        finally:
-            la.release()
+                release()
+            return _result_csr(indptr, indices, data, out_shape)
+        return ctx.dense_host(a, b, symmetric=bool(symmetric), exact=_exact,  # reference :353-365
+                              mirror=bool(symmetric) and _full_symmetric)
 
-    try:
-        result = product()
-    except SmmError as e:
-        if e.code != SMM_ERR_ALLOC or not (_cache or _plans):
-            raise
-        clear_cache()                                            # the resident operands / plans were in the way
-        result = product()
+    result = _with_leases(ctx, (matrix_a, matrix_b), product)
 
     if _result_device and not isinstance(result, (np.ndarray, csr_matrix)):
         empty = result.nnz == 0 if isinstance(result, DeviceCSRResult) else not bool(result.any())
@@ -638,42 +636,35 @@ def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False, mask=No
         raise ValueError("Matrix dimensions are incompatible for multiplication.")
     n = matrix_h.shape[0]
     out_shape = (n, n)
-    if mask is not None:
-        return _triple_masked(matrix_h, matrix_q, _as_csr(mask), out_shape, bool(compute_full_matrix))
-    if matrix_h.nnz == 0 or matrix_q.nnz == 0:
-        if _result_device:
-            return _device_zeros(default_context(), out_shape, True)
-        return csr_matrix(out_shape)
-    ctx = default_context()
     full = bool(compute_full_matrix)
+    if mask is not None:
+        mask = _as_csr(mask)
+        _check_mask_shape(mask, out_shape, "sparse_triple_product")
+        if mask.nnz == 0:
+            return _zero_result(out_shape)
+        if matrix_h.nnz == 0 or matrix_q.nnz == 0:
+            # the mask's upper part (mirrored when full) filled with +0.0, on the host
+            ctx = default_context() if (_result_device or isinstance(mask, PinnedOperand)) else None
+            indptr, indices = _mask_pattern(_canonical_mask(mask))
+            rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+            keep = indices >= rows
+            up = csr_matrix((np.ones(int(keep.sum())), (rows[keep], indices[keep])), shape=out_shape)
+            if full:
+                up = (up + up.T).tocsr()
+            up.sort_indices()
+            return _pattern_result(ctx, up.indptr.astype(np.int32), up.indices.astype(np.int32), np.zeros(up.nnz), out_shape)
+    elif matrix_h.nnz == 0 or matrix_q.nnz == 0:
+        return _zero_result(out_shape)
+    ctx = default_context()
+    mats = (matrix_h, matrix_q) if mask is None else (matrix_h, matrix_q, _canonical_mask(mask))
 
-    def product():
-        cached = _cache_entries > 0
-        key_h = _operand_key(matrix_h) if cached and not isinstance(matrix_h, PinnedOperand) else None
-        key_q = _operand_key(matrix_q) if cached and not isinstance(matrix_q, PinnedOperand) else None
-        lh = _acquire(ctx, matrix_h, key_h, protect=(key_q[0],) if key_q else ())
-        try:
-            lq = _acquire(ctx, matrix_q, key_q)
-            try:
-                if _result_device:
-                    import torch
-                    torch.cuda.current_stream(torch.device("cuda", ctx.device)).synchronize()
-                    out = DeviceCSRResult(*ctx.triple_sparse_torch(lh.handle, lq.handle, full=full, exact=_exact), out_shape)
-                    ctx.synchronize()
-                    return out
-                return _result_csr(*ctx.triple_sparse_host(lh.handle, lq.handle, full=full, exact=_exact), out_shape)
-            finally:
-                lq.release()
-        finally:
-            lh.release()
+    def body(lh, lq, lm=None):
+        h, q, m = lh.handle, lq.handle, (lm.handle if lm is not None else None)
+        if _result_device:
+            return _on_device(ctx, lambda: DeviceCSRResult(*ctx.triple_sparse_torch(h, q, full=full, exact=_exact, mask=m), out_shape))
+        return _result_csr(*ctx.triple_sparse_host(h, q, full=full, exact=_exact, mask=m), out_shape)
 
-    try:
-        return product()
-    except SmmError as e:
-        if e.code != SMM_ERR_ALLOC or not (_cache or _plans):
-            raise
-        clear_cache()                                            # the resident operands / plans were in the way
-        return product()
+    return _with_leases(ctx, mats, body)
 
 
 # ------------------------------------------------------------------ products on a given pattern
@@ -763,9 +754,7 @@ def masked_matrix_multiply(matrix_a, matrix_b, mask):
     out_shape = (matrix_a.shape[0], matrix_b.shape[1])
     _check_mask_shape(mask, out_shape, "masked_matrix_multiply")
     if mask.nnz == 0:
-        if _result_device:
-            return _device_zeros(default_context(), out_shape, True)
-        return csr_matrix(out_shape)
+        return _zero_result(out_shape)
     if matrix_a.nnz == 0 or matrix_b.nnz == 0:
         ctx = default_context() if (_result_device or isinstance(mask, PinnedOperand)) else None
         mask = _canonical_mask(mask)
@@ -778,12 +767,13 @@ def masked_matrix_multiply(matrix_a, matrix_b, mask):
         indptr, indices = _mask_pattern(mask)
         if _result_device:
             import torch
-            dev = torch.device("cuda", ctx.device)
-            torch.cuda.current_stream(dev).synchronize()
-            data = torch.empty(lm.handle.nnz, dtype=torch.float64, device=dev)
-            ctx.spgemm_masked_into(la.handle, lb.handle, lm.handle, data.data_ptr(), exact=_exact)
-            ctx.synchronize()
-            return _pattern_result(ctx, indptr, indices, data, out_shape)
+
+            def call():
+                data = torch.empty(lm.handle.nnz, dtype=torch.float64, device=torch.device("cuda", ctx.device))
+                ctx.spgemm_masked_into(la.handle, lb.handle, lm.handle, data.data_ptr(), exact=_exact)
+                return data
+
+            return _pattern_result(ctx, indptr, indices, _on_device(ctx, call), out_shape)
         return _result_csr(indptr, indices, ctx.spgemm_masked_host(la.handle, lb.handle, lm.handle, exact=_exact), out_shape)
 
     return _with_leases(ctx, (matrix_a, matrix_b, mask), body)
@@ -893,33 +883,3 @@ def triple_product_apply(matrix_h, matrix_q, x):
     return _with_leases(ctx, (matrix_h, matrix_q), body)
 
 
-def _triple_masked(matrix_h, matrix_q, mask, out_shape, full):
-    _check_mask_shape(mask, out_shape, "sparse_triple_product")
-    if mask.nnz == 0:
-        if _result_device:
-            return _device_zeros(default_context(), out_shape, True)
-        return csr_matrix(out_shape)
-    if matrix_h.nnz == 0 or matrix_q.nnz == 0:
-        # the mask's upper part (mirrored when full) filled with +0.0, on the host
-        ctx = default_context() if (_result_device or isinstance(mask, PinnedOperand)) else None
-        indptr, indices = _mask_pattern(_canonical_mask(mask))
-        rows = np.repeat(np.arange(out_shape[0], dtype=np.int64), np.diff(indptr))
-        keep = indices >= rows
-        up = csr_matrix((np.ones(int(keep.sum())), (rows[keep], indices[keep])), shape=out_shape)
-        if full:
-            up = (up + up.T).tocsr()
-        up.sort_indices()
-        return _pattern_result(ctx, up.indptr.astype(np.int32), up.indices.astype(np.int32), np.zeros(up.nnz), out_shape)
-    ctx = default_context()
-    mask = _canonical_mask(mask)
-
-    def body(lh, lq, lm):
-        if _result_device:
-            import torch
-            torch.cuda.current_stream(torch.device("cuda", ctx.device)).synchronize()
-            out = DeviceCSRResult(*ctx.triple_sparse_torch(lh.handle, lq.handle, full=full, exact=_exact, mask=lm.handle), out_shape)
-            ctx.synchronize()
-            return out
-        return _result_csr(*ctx.triple_sparse_host(lh.handle, lq.handle, full=full, exact=_exact, mask=lm.handle), out_shape)
-
-    return _with_leases(ctx, (matrix_h, matrix_q, mask), body)
