@@ -351,6 +351,44 @@ int  smm_triple_apply_host(smm_ctx *ctx, smm_csr *h, smm_csr *q, int flags, int6
  * 0 = the default, 1 GiB.  The result's shape and values never depend on either (bit for bit under SMM_EXACT). */
 int  smm_ctx_tune_spmm(smm_ctx *ctx, int mode, int64_t apply_budget_bytes);
 
+/* ------------------------------------------------------------------ conjugate gradients on (H Q H^T + R) Z = D
+ * S = H Q H^T is never formed (H: n x K, Q: K x K, R: n x n sparse or NULL for S alone; the system is expected to be
+ * symmetric positive definite).  B (the right-hand sides D) and X (the solution Z) are n x k row-major float64 with
+ * leading dimensions ldb, ldx >= k.  Every column is its own CG with x0 = 0; the columns share each sparse x dense
+ * product.  Nothing but one count of live columns per iteration comes to the host between B and X.  Per column:
+ *     r = d;  p = r;  rho = dot(r, r);  rhs_sq = rho;  thr = (tol * tol) * rhs_sq
+ *     rho <= thr: converged, 0 iterations (a zero column gives x = 0)
+ *     for it = 1 .. maxiter:
+ *         w = H (Q (H^T p)) + R p              one add per element; without R, w = S p
+ *         pw = dot(p, w);  not (pw > 0): status 2, iterations = it - 1, frozen   (pw <= 0 and NaN)
+ *         alpha = rho / pw;  x = x + alpha p;  r = r - alpha w;  rho_new = dot(r, r)
+ *         rho_new <= thr: status 0, iterations = it, frozen
+ *         beta = rho_new / rho;  p = r + beta p;  rho = rho_new
+ *     still live after maxiter: status 1, iterations = maxiter
+ * A frozen column's x, residual_sq and iterations never change again; columns cannot influence each other.  The test is
+ * on squared norms of the recurrence's residual (no square root); alpha and beta are IEEE divisions done on the device.
+ * dot(u, v), for T = SMM_CG_LANES: partial t starts at +0.0 and adds u[i] v[i] for i = t, t + T, t + 2T, ... in
+ * ascending i; then s[t] = s[t] + s[t + h] for h = T/2, T/4, ..., 1; the result is s[0].
+ *   SMM_EXACT (the only flag): the three products are the exact sparse x dense product above, every multiply in a dot
+ *   or a vector update is rounded before its add, and X and the four outputs are bit-identical to that recipe carried
+ *   out in IEEE double, for any legal CSR operands.  Without it: fused multiply-adds and the default sparse x dense
+ *   kernels; no float atomics, so two runs give the same bits.
+ * The right-hand sides are solved in column blocks when five n x block vectors and two K x block intermediates exceed the
+ * apply budget (smm_ctx_tune_spmm); blocking changes no bit under SMM_EXACT (default mode: as long as no block is a single
+ * column).  The rows of H^T, Q, H and R are binned once per column block, not per iteration.
+ * Outputs, host arrays of k entries each: iterations, status (0 converged, 1 iteration limit, 2 breakdown),
+ * residual_sq (the recurrence's dot(r, r) when the column froze or the solve ended) and rhs_sq (dot(d, d)).
+ * Non-convergence is reported there, not as an error.  k < 0, ldb < k, ldx < k, tol not finite and positive, maxiter < 0,
+ * NULL buffers that should hold data, overlapping ranges of B and X and shapes that do not fit are SMM_ERR_INVALID. */
+#define SMM_CG_LANES 2048
+int  smm_innovation_solve(smm_ctx *ctx, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, const double *d_b,
+                          int64_t ldb, double *d_x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
+                          double *residual_sq, double *rhs_sq);
+/* Same with host B and X (uploaded / downloaded through pool temporaries). */
+int  smm_innovation_solve_host(smm_ctx *ctx, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, const double *b,
+                               int64_t ldb, double *x, int64_t ldx, double tol, int64_t maxiter, int *iterations,
+                               int *status, double *residual_sq, double *rhs_sq);
+
 /* ------------------------------------------------------------------ device memory helpers
  * (so that hosts without torch can still hold results in HBM) */
 int  smm_device_malloc(smm_ctx *ctx, int64_t bytes, void **d_ptr);

@@ -8,6 +8,7 @@
 #include "smm_triple_sparse.hpp"
 #include "smm_masked.hpp"
 #include "smm_spmm.hpp"
+#include "smm_cg.hpp"
 #include "../../include/smm_hip.h"
 
 #include <sys/mman.h>
@@ -15,6 +16,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -108,6 +110,8 @@ struct smm_ctx {
     static constexpr size_t PIN_BYTES = (size_t)32 << 20;
     void *pin[PIN_SLOTS] = {nullptr};
     hipEvent_t pin_ev[PIN_SLOTS] = {nullptr};
+    int *cg_live = nullptr;          // smm_innovation_solve: two pinned words for the count of live columns, with their events
+    hipEvent_t cg_ev[2] = {nullptr, nullptr};
     int exact_checked = 0;           // SMM_EXACT guard (smm_ctx_exact_selftest): 0 not run yet, 1 passed, -1 failed
     int check = 0;                   // 1: every symbolic phase ends with the plan checker (env SMM_CHECK, smm_ctx_set_check)
     int inject_alloc_nth = 0;        // test hook: the n-th dev_malloc from now fails (its first attempt, or both: _hard)
@@ -310,6 +314,8 @@ extern "C" void smm_ctx_destroy(smm_ctx *c)
         if (c->pin[i]) (void)hipHostFree(c->pin[i]);
         if (c->pin_ev[i]) (void)hipEventDestroy(c->pin_ev[i]);
     }
+    if (c->cg_live) (void)hipHostFree(c->cg_live);
+    for (hipEvent_t e : c->cg_ev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -3082,16 +3088,23 @@ static int spmm_op(smm_ctx *c, smm_csr *a, bool transpose, const smm_csr **out)
     return SMM_OK;
 }
 
-// Y = op X on the context's stream, no synchronisation (validated op; k, ldx, ldy checked by the caller).  Rows are binned
-// by length and each class goes to its kernel (smm_spmm.hpp); every row of Y gets columns [0, k) written, nothing else.
-static int spmm_impl(smm_ctx *c, const smm_csr *op, bool exact, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy)
+// Y = op X on the context's stream (validated op; k, ldx, ldy checked by the caller).  Rows are binned by length and each
+// class goes to its kernel (smm_spmm.hpp); every row of Y gets columns [0, k) written, nothing else.  In two halves: the
+// rows of op binned for width k (one synchronisation for the class counts), and the class kernels launched from such
+// lists without one.  A solver that applies one operator many times at one width bins it once.
+static int spmm_bin(smm_ctx *c, const smm_csr *op, int64_t k, ClassLists &bins)
 {
     const int64_t m = op->rows;
     if (m == 0 || k == 0) return SMM_OK;
-    ClassLists bins(c);
-    CHK(bin_rows(c, m, SP_NCLS, bins, [&](int *lists, int *cnt) {
+    return bin_rows(c, m, SP_NCLS, bins, [&](int *lists, int *cnt) {
         LAUNCH(c, "smm_spmm_bin", smm_spmm_bin, std::min<int64_t>((m + 255) / 256, 4096), 256, 0, (int)m, op->ptr, k, c->spmm_mode, lists, cnt);
-    }));
+    });
+}
+static int spmm_launch(smm_ctx *c, const smm_csr *op, const ClassLists &bins, bool exact, int64_t k, const double *x, int64_t ldx, double *y,
+                       int64_t ldy)
+{
+    const int64_t m = op->rows;
+    if (m == 0 || k == 0) return SMM_OK;
     const int *hc = bins.count;
     SpmmArgs A{};
     A.m = (int)m; A.K = (int)op->cols; A.nnz = (int)op->nnz;
@@ -3140,6 +3153,13 @@ static int spmm_impl(smm_ctx *c, const smm_csr *op, bool exact, int64_t k, const
         LAUNCH_CHECK();
     }
     return SMM_OK;
+}
+// Both halves back to back.
+static int spmm_impl(smm_ctx *c, const smm_csr *op, bool exact, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy)
+{
+    ClassLists bins(c);
+    CHK(spmm_bin(c, op, k, bins));
+    return spmm_launch(c, op, bins, exact, k, x, ldx, y, ldy);
 }
 
 // Bytes spanned by a row-major rows x k block with leading dimension ld (0 when empty).
@@ -3288,6 +3308,182 @@ extern "C" int smm_triple_apply_host(smm_ctx *c, smm_csr *h, smm_csr *q, int fla
     CHK(triple_apply_impl(c, h, q, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
     CHK(take_plan_error(c, "smm_triple_apply_host"));
     return download_rows(c, y, dy, n, k, ldy);
+}
+
+// ------------------------------------------------------------------------------ CG on (H Q H^T + R) Z = D
+// The pinned words and events through which the host follows the count of live columns (made on first use).
+static int cg_host_words(smm_ctx *c)
+{
+    if (!c->cg_live) {
+        if (hipHostMalloc((void **)&c->cg_live, 64, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            c->cg_live = nullptr;
+            return fail(SMM_ERR_ALLOC, "smm_innovation_solve: hipHostMalloc of the live-column words failed");
+        }
+    }
+    for (hipEvent_t &e : c->cg_ev)
+        if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return SMM_OK;
+}
+
+// One column block of the solve (smm_cg.hpp; the contract is in include/smm_hip.h).  b / x point at the block's first column.
+// The host enqueues iteration it, then waits for the live count that iteration it - 1 left: the device always has one
+// iteration queued, and at most one runs after the last column froze -- on frozen columns, which no kernel writes.
+static int cg_block(smm_ctx *c, const smm_csr *ht, const smm_csr *q, const smm_csr *h, const smm_csr *r, bool exact, int64_t k,
+                    const double *b, int64_t ldb, double *x, int64_t ldx, double tol, int64_t maxiter, double *rv, double *pv, double *wv,
+                    double *rpv, double *z1, double *z2, double *part, double *sc, int *iterations, int *status, double *residual_sq,
+                    double *rhs_sq)
+{
+    const int64_t n = h->rows;
+    ClassLists bht(c), bq(c), bh(c), br(c);
+    CHK(spmm_bin(c, ht, k, bht));
+    CHK(spmm_bin(c, q, k, bq));
+    CHK(spmm_bin(c, h, k, bh));
+    if (r) CHK(spmm_bin(c, r, k, br));
+    int *st = reinterpret_cast<int *>(sc + CG_NSC * k);
+    CgArgs A{};
+    A.n = n; A.k = k; A.b = b; A.ldb = ldb; A.x = x; A.ldx = ldx;
+    A.r = rv; A.p = pv; A.w = wv; A.rp = rpv; A.part = part; A.sc = sc; A.st = st;
+    // 16-byte accesses where every thread's pair of columns is aligned in every vector (the pool's blocks are)
+    const int vec = (k % 2 == 0 && ldb % 2 == 0 && ldx % 2 == 0 && (uintptr_t)b % 16 == 0 && (uintptr_t)x % 16 == 0) ? 2 : 1;
+    const int64_t threads = (int64_t)CG_T * (k / vec);
+    const int block = threads <= 16384 ? 64 : 256;            // (few columns: the T partials spread over more CUs)
+    const int64_t grid = (threads + block - 1) / block;
+    const double tol2 = tol * tol;
+#define CG_LAUNCH(name, kern, ...)                                                                          \
+    do {                                                                                                 \
+        if (vec == 2) { if (exact) LAUNCH(c, name, (kern<2, true __VA_ARGS__>), grid, block, 0, A);      \
+                        else       LAUNCH(c, name, (kern<2, false __VA_ARGS__>), grid, block, 0, A); }   \
+        else          { if (exact) LAUNCH(c, name, (kern<1, true __VA_ARGS__>), grid, block, 0, A);      \
+                        else       LAUNCH(c, name, (kern<1, false __VA_ARGS__>), grid, block, 0, A); }   \
+    } while (0)
+#define CG_COMMA ,
+    HIPCHK(hipMemsetAsync(st + 3 * k, 0, sizeof(int), c->stream));
+    CG_LAUNCH("smm_cg_init", smm_cg_init);
+    LAUNCH(c, "smm_cg_finish", smm_cg_finish<0>, k, CG_FIN, 0, part, k, sc, st, tol2, 0);
+    LAUNCH_CHECK();
+    HIPCHK(hipMemcpyAsync(c->cg_live, st + 3 * k, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    bool live = c->cg_live[0] > 0;
+    for (int64_t it = 1; live && it <= maxiter; ++it) {
+        CHK(spmm_launch(c, ht, bht, exact, k, pv, k, z1, k));         // Z1 = H^T P
+        CHK(spmm_launch(c, q, bq, exact, k, z1, k, z2, k));           // Z2 = Q Z1
+        CHK(spmm_launch(c, h, bh, exact, k, z2, k, wv, k));           // W = H Z2
+        if (r) {
+            CHK(spmm_launch(c, r, br, exact, k, pv, k, rpv, k));      // R P, added to W on the way to dot(p, w)
+            CG_LAUNCH("smm_cg_pw", smm_cg_pw, CG_COMMA true);
+        } else {
+            CG_LAUNCH("smm_cg_pw", smm_cg_pw, CG_COMMA false);
+        }
+        LAUNCH(c, "smm_cg_finish", smm_cg_finish<1>, k, CG_FIN, 0, part, k, sc, st, tol2, (int)it);
+        CG_LAUNCH("smm_cg_update", smm_cg_update);
+        LAUNCH(c, "smm_cg_finish", smm_cg_finish<2>, k, CG_FIN, 0, part, k, sc, st, tol2, (int)it);
+        CG_LAUNCH("smm_cg_direction", smm_cg_direction);
+        LAUNCH_CHECK();
+        const int slot = (int)(it & 1);
+        HIPCHK(hipMemcpyAsync(c->cg_live + 8 * slot, st + 3 * k, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipEventRecord(c->cg_ev[slot], c->stream));
+        if (it >= 2) {
+            HIPCHK(hipEventSynchronize(c->cg_ev[slot ^ 1]));
+            live = c->cg_live[8 * (slot ^ 1)] > 0;
+        }
+    }
+#undef CG_COMMA
+#undef CG_LAUNCH
+    // the block's scalars, as the device left them
+    std::vector<double> hs((size_t)(CG_NSC * k + (3 * k + 2) / 2 + 1));
+    CHK(download(c, hs.data(), sc, ((size_t)CG_NSC * k) * sizeof(double) + ((size_t)3 * k + 1) * sizeof(int)));
+    const int *hst = reinterpret_cast<const int *>(hs.data() + CG_NSC * k);
+    for (int64_t j = 0; j < k; ++j) {
+        status[j] = hst[j]; iterations[j] = hst[k + j];
+        residual_sq[j] = hs[(size_t)(CG_RES * k + j)]; rhs_sq[j] = hs[(size_t)(CG_RHS * k + j)];
+    }
+    return SMM_OK;
+}
+
+// Vectors of one column block: r, p, w, R p (n x kb), the two intermediates (K x kb), the dot partials and the scalars.
+static int innovation_impl(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, bool exact, int64_t k, const double *b, int64_t ldb, double *x,
+                           int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status, double *residual_sq, double *rhs_sq)
+{
+    const int64_t n = h->rows, K = h->cols;
+    if (n == 0 || k == 0) return SMM_OK;
+    const smm_csr *ht = nullptr;
+    CHK(spmm_op(c, h, true, &ht));
+    CHK(cg_host_words(c));
+    const int64_t per_col = (5 * n + 2 * K) * (int64_t)sizeof(double);
+    int64_t kb = std::max<int64_t>(1, std::min<int64_t>(k, c->apply_budget / std::max<int64_t>(per_col, 1)));
+    const int64_t nblocks = (k + kb - 1) / kb, even = (k + nblocks - 1) / nblocks;      // blocks of one size (64 = 32 + 32, not 44 + 20),
+    kb = (even % 2 && even < kb) ? even + 1 : even;                                      // of an even width where the budget allows
+    PoolBuf<double> rv(c), pv(c), wv(c), rpv(c), z1(c), z2(c), part(c), sc(c);
+    CHK(rv.alloc((size_t)(n * kb)));
+    CHK(pv.alloc((size_t)(n * kb)));
+    CHK(wv.alloc((size_t)(n * kb)));
+    if (r) CHK(rpv.alloc((size_t)(n * kb)));
+    CHK(z1.alloc((size_t)std::max<int64_t>(K * kb, 1)));
+    CHK(z2.alloc((size_t)std::max<int64_t>(K * kb, 1)));
+    CHK(part.alloc((size_t)CG_T * kb));
+    CHK(sc.alloc((size_t)(CG_NSC * kb + (3 * kb + 2) / 2 + 1)));
+    for (int64_t j0 = 0; j0 < k; j0 += kb) {
+        const int64_t w = std::min(kb, k - j0);
+        CHK(cg_block(c, ht, q, h, r, exact, w, b + j0, ldb, x + j0, ldx, tol, maxiter, rv, pv, wv, rpv, z1, z2, part, sc, iterations + j0,
+                     status + j0, residual_sq + j0, rhs_sq + j0));
+    }
+    return SMM_OK;
+}
+
+static int innovation_args(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, int64_t ldb, int64_t ldx, double tol,
+                           int64_t maxiter, const int *iterations, const int *status, const double *residual_sq, const double *rhs_sq,
+                           const char *where)
+{
+    if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call", where);
+    CHK(check_pair(c, h, q));
+    if (q->rows != q->cols) return fail(SMM_ERR_INVALID, "%s: Q must be square, got %lld x %lld", where, (long long)q->rows, (long long)q->cols);
+    if (r) {
+        if (r->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
+        if (r->rows != h->rows || r->cols != h->rows)
+            return fail(SMM_ERR_INVALID, "%s: R must be %lld x %lld, got %lld x %lld", where, (long long)h->rows, (long long)h->rows,
+                        (long long)r->rows, (long long)r->cols);
+        CHK(validate(c, r));
+    }
+    if (k < 0 || ldb < k || ldx < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldb, ldx (k %lld, ldb %lld, ldx %lld)", where,
+                                                 (long long)k, (long long)ldb, (long long)ldx);
+    if (!(tol > 0.0) || !std::isfinite(tol)) return fail(SMM_ERR_INVALID, "%s: tol must be a finite positive number", where);
+    if (maxiter < 0 || maxiter > INT32_MAX) return fail(SMM_ERR_INVALID, "%s: need 0 <= maxiter < 2^31", where);
+    if (k > 0 && (!iterations || !status || !residual_sq || !rhs_sq)) return fail(SMM_ERR_INVALID, "%s: a per-column output is NULL", where);
+    return SMM_OK;
+}
+
+extern "C" int smm_innovation_solve(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, const double *d_b, int64_t ldb,
+                                    double *d_x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status, double *residual_sq,
+                                    double *rhs_sq)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(innovation_args(c, h, q, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq, "smm_innovation_solve"));
+    const int64_t n = h->rows, bb = span_bytes(n, k, ldb), xb = span_bytes(n, k, ldx);
+    if ((bb > 0 && !d_b) || (xb > 0 && !d_x)) return fail(SMM_ERR_INVALID, "smm_innovation_solve: B or X is NULL");
+    if (ranges_overlap(d_b, bb, d_x, xb)) return fail(SMM_ERR_INVALID, "smm_innovation_solve: the device ranges of B and X overlap");
+    CHK(innovation_impl(c, h, q, r, (flags & SMM_EXACT) != 0, k, d_b, ldb, d_x, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq));
+    return take_plan_error(c, "smm_innovation_solve");
+}
+
+extern "C" int smm_innovation_solve_host(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, const double *b, int64_t ldb,
+                                         double *x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
+                                         double *residual_sq, double *rhs_sq)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(innovation_args(c, h, q, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq, "smm_innovation_solve_host"));
+    const int64_t n = h->rows;
+    if (span_bytes(n, k, std::max(ldb, ldx)) > 0 && (!b || !x)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_host: B or X is NULL");
+    if (n == 0 || k == 0) return SMM_OK;
+    PoolBuf<double> db(c), dx(c);
+    CHK(db.alloc((size_t)(n * k)));
+    CHK(dx.alloc((size_t)(n * k)));
+    CHK(upload_rows(c, db, b, n, k, ldb));
+    CHK(innovation_impl(c, h, q, r, (flags & SMM_EXACT) != 0, k, db, k, dx, k, tol, maxiter, iterations, status, residual_sq, rhs_sq));
+    CHK(take_plan_error(c, "smm_innovation_solve_host"));
+    return download_rows(c, x, dx, n, k, ldx);
 }
 
 // ------------------------------------------------------------------------------ memory helpers

@@ -436,6 +436,57 @@ class Context:
                                                   ctypes.c_void_p(_dptr(d_x)), int(ldx), ctypes.c_void_p(_dptr(d_y)), int(ldy)))
         self.synchronize()
 
+    # ------------------------------------------------------------------ CG on (H Q H^T + R) Z = D
+    def _solve(self, entry, h, q, r, k, b, ldb, x, ldx, tol, maxiter, exact):
+        info = SolveInfo(k)
+        check(self.lib, entry(self.handle, h.handle, q.handle, r.handle if r is not None else None, _flags(exact=exact), int(k),
+                              b, int(ldb), x, int(ldx), float(tol), int(maxiter), _ptr(info.iterations), _ptr(info.status),
+                              _ptr(info.residual_sq), _ptr(info.rhs_sq)))
+        return info
+
+    def innovation_solve_host(self, h, q, r, d, tol=1e-8, maxiter=None, exact=False):
+        """(Z, info) with (H Q H^T + R) Z = D by conjugate gradients, one CG per column of the numpy D (n x k or n), Z of
+        the same shape (smm_innovation_solve_host).  r: a DeviceCSR (n x n) or None; maxiter None means n."""
+        d, k = self._host_x(d)
+        if d.shape[0] != h.rows:
+            raise ValueError(f"D has {d.shape[0]} rows, H has {h.rows}")
+        z = np.zeros(d.shape, dtype=np.float64)
+        info = self._solve(self.lib.smm_innovation_solve_host, h, q, r, k, _ptr(d), k, _ptr(z), k, tol,
+                           h.rows if maxiter is None else maxiter, exact)
+        return z, info
+
+    def innovation_solve_into(self, h, q, r, d_b, ldb, k, d_x, ldx, tol=1e-8, maxiter=None, exact=False):
+        """The same on device buffers: D (n x k, leading dimension ldb) at d_b, Z (leading dimension ldx) at d_x
+        (smm_innovation_solve); stream rules as spmm_into.  Returns info."""
+        if hasattr(d_b, "data_ptr"):
+            self._sync_torch(d_b)
+        if hasattr(d_x, "data_ptr"):
+            self._sync_torch(d_x)
+        info = self._solve(self.lib.smm_innovation_solve, h, q, r, k, ctypes.c_void_p(_dptr(d_b)), ldb, ctypes.c_void_p(_dptr(d_x)),
+                           ldx, tol, h.rows if maxiter is None else maxiter, exact)
+        self.synchronize()
+        return info
+
+
+class SolveInfo:
+    """Per-column outcome of innovation_solve: iterations (int32), status (int32: 0 converged, 1 iteration limit,
+    2 breakdown), residual_sq (the recurrence's dot(r, r) at the end) and rhs_sq (dot(d, d)), numpy arrays of k entries."""
+    CONVERGED, ITERATION_LIMIT, BREAKDOWN = 0, 1, 2
+
+    def __init__(self, k):
+        self.iterations = np.zeros(k, dtype=np.int32)
+        self.status = np.zeros(k, dtype=np.int32)
+        self.residual_sq = np.zeros(k, dtype=np.float64)
+        self.rhs_sq = np.zeros(k, dtype=np.float64)
+
+    @property
+    def converged(self):
+        return bool(np.all(self.status == 0))
+
+    def __repr__(self):
+        return (f"SolveInfo(iterations={self.iterations.tolist()}, status={self.status.tolist()}, "
+                f"residual_sq={self.residual_sq.tolist()}, rhs_sq={self.rhs_sq.tolist()})")
+
 
 def _dptr(p):
     """A device address: an int, or a torch tensor's data_ptr()."""

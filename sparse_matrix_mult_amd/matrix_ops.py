@@ -22,7 +22,7 @@ import numpy as np
 from scipy.sparse import csr_matrix, isspmatrix_csr
 
 from ._lib import SMM_ERR_ALLOC, SmmError, SmmLibrary
-from .engine import default_context
+from .engine import SolveInfo, default_context
 
 _INT32_MAX = np.iinfo(np.int32).max
 
@@ -780,14 +780,14 @@ def masked_matrix_multiply(matrix_a, matrix_b, mask):
 
 
 # ------------------------------------------------------------------ sparse x dense
-def _dense_operand(x, rows, what):
+def _dense_operand(x, rows, what, name="X"):
     """(X, k, is_torch): X a float64 C-contiguous numpy array, or a float64 CUDA tensor with unit column stride; 1-D or
-    2-D with `rows` rows.  ValueError before any device work."""
+    2-D with `rows` rows.  ValueError before any device work (`name`: what the messages call the operand)."""
     is_torch = type(x).__module__.split(".")[0] == "torch"
     if is_torch:
         import torch
         if x.dtype != torch.float64 or not x.is_cuda:
-            raise ValueError(f"{what}: a torch X must be a float64 CUDA tensor")
+            raise ValueError(f"{what}: a torch {name} must be a float64 CUDA tensor")
         if x.dim() <= 2 and (x.stride(-1) != 1 or (x.dim() == 2 and x.stride(0) < x.shape[1])):
             x = x.contiguous()
     else:
@@ -795,9 +795,9 @@ def _dense_operand(x, rows, what):
         x = np.ascontiguousarray(x) if x.ndim else x          # (ascontiguousarray would make a 0-d X 1-D)
     ndim = x.dim() if is_torch else x.ndim
     if ndim not in (1, 2):
-        raise ValueError(f"{what}: X must be 1-D or 2-D, got {ndim} dimensions")
+        raise ValueError(f"{what}: {name} must be 1-D or 2-D, got {ndim} dimensions")
     if x.shape[0] != rows:
-        raise ValueError(f"{what}: X has {x.shape[0]} rows, expected {rows}")
+        raise ValueError(f"{what}: {name} has {x.shape[0]} rows, expected {rows}")
     return x, (1 if ndim == 1 else int(x.shape[1])), is_torch
 
 
@@ -883,3 +883,141 @@ def triple_product_apply(matrix_h, matrix_q, x):
     return _with_leases(ctx, (matrix_h, matrix_q), body)
 
 
+# ------------------------------------------------------------------ CG on (H Q H^T + R) Z = D
+CG_LANES = 2048          # SMM_CG_LANES of include/smm_hip.h: the dot product's number of partial sums
+
+
+def _cg_dot(u, v):
+    """Column-wise dot(u, v) in the library's fixed order: CG_LANES partial sums over strided rows, then a halving tree."""
+    n, k = u.shape
+    s = np.zeros((CG_LANES, k))
+    for i0 in range(0, n, CG_LANES):
+        m = min(CG_LANES, n - i0)
+        s[:m] = s[:m] + u[i0:i0 + m] * v[i0:i0 + m]
+    h = CG_LANES // 2
+    while h:
+        s = s[:h] + s[h:2 * h]
+        h //= 2
+    return s[0]
+
+
+def _cg_on_host(apply, d, tol, maxiter):
+    """The iteration of smm_innovation_solve in numpy, for the systems that never reach the device (S = 0): apply(P)
+    is (S + R) P.  Returns (Z, info)."""
+    n, k = d.shape
+    info = SolveInfo(k)
+    x, r, p = np.zeros((n, k)), d.copy(), d.copy()
+    with np.errstate(all="ignore"):
+        rho = _cg_dot(r, r)
+        thr = (tol * tol) * rho
+        info.rhs_sq[:] = rho
+        info.residual_sq[:] = rho
+        live = ~(rho <= thr)
+        info.status[live] = SolveInfo.ITERATION_LIMIT
+        for it in range(1, maxiter + 1):
+            if not live.any():
+                break
+            w = apply(p)
+            pw = _cg_dot(p, w)
+            broke = live & ~(pw > 0)
+            info.status[broke], info.iterations[broke] = SolveInfo.BREAKDOWN, it - 1
+            live = live & ~broke
+            j = np.flatnonzero(live)
+            alpha = rho[j] / pw[j]
+            x[:, j] = x[:, j] + alpha * p[:, j]
+            r[:, j] = r[:, j] - alpha * w[:, j]
+            rho_new = _cg_dot(r[:, j], r[:, j])
+            info.residual_sq[j], info.iterations[j] = rho_new, it
+            done = rho_new <= thr[j]
+            info.status[j[done]] = SolveInfo.CONVERGED
+            live[j[done]] = False
+            j, rho_new = j[~done], rho_new[~done]
+            p[:, j] = r[:, j] + (rho_new / rho[j]) * p[:, j]
+            rho[j] = rho_new
+    return x, info
+
+
+def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
+    """(Z, info) with (H Q H^T + R) Z = D by conjugate gradients on the GPU; S = H Q H^T is never formed.
+
+    matrix_h : n x K, matrix_q : K x K; scipy CSR, anything csr_matrix() accepts, or a PinnedOperand.
+    matrix_r : n x n in the same forms, a 1-D array of the n diagonal entries, or None for S alone.  S + R is expected
+               to be symmetric positive definite.
+    d        : n x k or n, numpy or a float64 CUDA tensor as in triple_product_apply.  Every column is its own CG from
+               x0 = 0; all columns share each sparse x dense product.  Z has d's kind and shape (a torch tensor under
+               set_result_device(True)).
+    tol      : a column converges when the recurrence's ||r||^2 <= tol^2 ||d||^2.  maxiter : None means n.
+    info     : a SolveInfo with per-column arrays iterations, status (0 converged, 1 iteration limit, 2 breakdown: p^T (S + R) p
+               was not positive), residual_sq and rhs_sq.  Non-convergence is reported there, not raised.
+    Dot products are summed in a fixed order (include/smm_hip.h); under set_exact(True) Z and info are bit-identical to
+    that recipe in IEEE double, otherwise fused multiply-adds are used and two runs still agree bit for bit.  The vectors
+    of a block of columns are sized by Context.tune_spmm's apply budget.
+    """
+    matrix_h = _as_csr(matrix_h)
+    matrix_q = _as_csr(matrix_q)
+    if matrix_q.shape[0] != matrix_q.shape[1]:
+        raise ValueError(f"innovation_solve: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
+    if matrix_h.shape[1] != matrix_q.shape[0]:
+        raise ValueError("Matrix dimensions are incompatible for multiplication.")
+    n = matrix_h.shape[0]
+    if matrix_r is not None:
+        if not (isspmatrix_csr(matrix_r) or isinstance(matrix_r, PinnedOperand) or hasattr(matrix_r, "tocsr")):
+            dense_r = np.asarray(matrix_r, dtype=np.float64)
+            if dense_r.ndim == 1:                        # the diagonal; zeros stay stored
+                if dense_r.shape[0] != n:
+                    raise ValueError(f"innovation_solve: the diagonal of R has {dense_r.shape[0]} entries, expected {n}")
+                matrix_r = csr_matrix((dense_r, np.arange(n, dtype=np.int32), np.arange(n + 1, dtype=np.int32)), shape=(n, n))
+        matrix_r = _as_csr(matrix_r)
+        if tuple(matrix_r.shape) != (n, n):
+            raise ValueError(f"innovation_solve: R must be {n} x {n}, got {matrix_r.shape[0]} x {matrix_r.shape[1]}")
+    d, k, is_torch = _dense_operand(d, n, "innovation_solve", "D")
+    try:
+        tol = float(tol)
+    except (TypeError, ValueError):
+        raise ValueError("innovation_solve: tol must be a finite positive number") from None
+    if not (tol > 0.0 and np.isfinite(tol)):
+        raise ValueError(f"innovation_solve: tol must be a finite positive number, got {tol}")
+    if maxiter is None:
+        maxiter = n
+    if int(maxiter) != maxiter or maxiter < 0:
+        raise ValueError(f"innovation_solve: maxiter must be a non-negative integer, got {maxiter}")
+    maxiter = int(maxiter)
+    on_device = is_torch or _result_device
+    if matrix_r is not None and matrix_r.nnz == 0:
+        matrix_r = None
+    if k == 0 or n == 0:
+        return _dense_zeros(tuple(d.shape), on_device), SolveInfo(k)
+    if matrix_h.nnz == 0 or matrix_q.nnz == 0:           # S = 0: R Z = D, iterated on the host
+        dh = (d.cpu().numpy() if is_torch else d).reshape(n, k)
+        if matrix_r is None:
+            apply = np.zeros_like
+        elif isinstance(matrix_r, PinnedOperand):
+            ctx = default_context()
+            apply = lambda p: 0.0 + _with_leases(ctx, (matrix_r,), lambda lr: ctx.spmm_host(lr.handle, p, exact=True))  # noqa: E731
+        else:
+            apply = lambda p: 0.0 + np.asarray(matrix_r @ p)  # noqa: E731
+        z, info = _cg_on_host(apply, dh, tol, maxiter)
+        z = z.reshape(tuple(d.shape))
+        if on_device:
+            import torch
+            z = torch.from_numpy(z).to(torch.device("cuda", default_context().device))
+        return z, info
+    ctx = default_context()
+
+    def body(lh, lq, *lr):
+        h, q, r = lh.handle, lq.handle, (lr[0].handle if lr else None)
+        if not on_device:
+            return ctx.innovation_solve_host(h, q, r, d, tol, maxiter, exact=_exact)
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        if not is_torch:
+            b = torch.from_numpy(d).to(dev)
+        elif d.device != dev:
+            raise ValueError(f"D is on {d.device}, the library works on {dev}")
+        else:
+            b = d
+        z = torch.empty(tuple(b.shape), dtype=torch.float64, device=dev)
+        info = ctx.innovation_solve_into(h, q, r, b, 1 if b.dim() == 1 else b.stride(0), k, z, k, tol, maxiter, exact=_exact)
+        return z, info
+
+    return _with_leases(ctx, (matrix_h, matrix_q) + ((matrix_r,) if matrix_r is not None else ()), body)
