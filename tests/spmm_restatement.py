@@ -52,10 +52,14 @@ def raw_csr(indptr, indices, data, shape):
     return M
 
 
+BOUNDARY_LENGTHS = [1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 511, 512, 513, 1023, 1024, 1025, 4095, 4096, 4097]
+
+
 @functools.lru_cache(maxsize=None)
 def operands():
     """name -> CSR: uniform random, unsorted rows with repeated columns, empty rows, power-law row lengths with one row of
-    100 000 entries, hypersparse, tall-skinny.  Values signed (cancellation, signed zeros)."""
+    100 000 entries, hypersparse, tall-skinny, one row of every boundary length.  Values signed (cancellation, signed
+    zeros)."""
     rng = np.random.default_rng(2024)
     out = {}
     U = sp.random(300, 200, density=0.05, format="csr", random_state=rng)
@@ -81,4 +85,12 @@ def operands():
     T = sp.random(20000, 9, density=0.3, format="csr", random_state=rng)
     T.data = rng.uniform(-1, 1, T.nnz)
     out["tall_skinny"] = T
+    # one row on either side of every length at which a kernel changes its path (class thresholds 16, 1024 and 4096,
+    # batches of 64 lanes and of 8 waves x 64), and an empty one; 50 columns drawn with a power-law weight, so rows hold
+    # repeats in any order and the transposed operand has rows beyond 4096 and 1024 entries too
+    lens = np.array([0] + BOUNDARY_LENGTHS)[rng.permutation(len(BOUNDARY_LENGTHS) + 1)]
+    ptr = np.concatenate([[0], np.cumsum(lens)])
+    wgt = 1.0 / np.arange(1, 51) ** 1.5
+    idx = rng.choice(50, size=int(ptr[-1]), p=wgt / wgt.sum())
+    out["boundaries"] = raw_csr(ptr, idx, rng.uniform(-1, 1, idx.size), (len(lens), 50))
     return out

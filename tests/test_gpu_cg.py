@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from cg_restatement import (BREAKDOWN, CASES, CONVERGED, LIMIT, diag_csr, dominant_diagonal, local_h, random_band, restate_cg,
-                            rhs, system, true_residual)
+from cg_restatement import (BREAKDOWN, CASES, CONVERGED, LANES, LIMIT, diag_csr, dominant_diagonal, gaussian_band, local_h,
+                            random_band, restate_cg, rhs, system, true_residual)
 from spmm_restatement import raw_csr
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(1800)]
@@ -68,6 +68,25 @@ def test_exact_is_the_restatement_at_every_width(ctx, small, k):
     assert np.all(want[1].status == CONVERGED) and want[1].iterations.max() > 30
     if k >= 5:
         assert want[1].iterations[2] == 0
+
+
+@pytest.mark.parametrize("n", [1, LANES - 1, LANES, LANES + 1])
+def test_exact_is_the_restatement_around_the_lane_count(ctx, n):
+    """dot(u, v) keeps LANES partial sums: systems of 1, LANES - 1, LANES and LANES + 1 rows leave all but one partial
+    empty, the last one empty, none empty, and give the first one a second term."""
+    K = max(64, 3 * n)
+    H, Q = local_h(n, K, 300 + n % 7), gaussian_band(K, 8)
+    R = diag_csr(dominant_diagonal(H, Q, 301))
+    h, q, r = (ctx.csr_from_scipy(M) for M in (H, Q, R))
+    try:
+        for k in (1, 5):
+            D = rhs(n, k, 302 + k, 2 if k >= 5 else None)
+            want = restate_cg(H, Q, R, D, TOL)
+            _assert_exact(ctx.innovation_solve_host(h, q, r, D, TOL, exact=True), want, f"n={n} k={k}")
+            assert np.all(want[1].status == CONVERGED) and want[1].iterations.max() >= 1
+    finally:
+        for hd in (h, q, r):
+            hd.close()
 
 
 def test_public_interface_exact():

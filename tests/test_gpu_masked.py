@@ -7,39 +7,11 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from helpers import arrays, rand_csr, rel_err, shuffle_rows, signed
+from helpers import check_masked_values as _check_values, masked_want as _want, rand_csr, rel_err, shuffle_rows, signed
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(1200)]
 RTOL = 1e-10
 MODES = [0, 1, 2]          # auto, dot, row
-
-
-def _want(oracle, A, B):
-    """The oracle's unmasked product scattered to dense arrays: values and the stored-position map."""
-    m, n = A.shape[0], B.shape[1]
-    ptr, idx, val = oracle.sparse(arrays(A), arrays(B), n)
-    rows = np.repeat(np.arange(m), np.diff(ptr))
-    W = np.zeros((m, n))
-    S = np.zeros((m, n), dtype=bool)
-    W[rows, idx] = val
-    S[rows, idx] = True
-    return W, S
-
-
-def _check_values(got, M, A, B, W, S, exact):
-    """got: values in the canonical mask M's order."""
-    rows = np.repeat(np.arange(M.shape[0]), np.diff(M.indptr))
-    cols = M.indices
-    assert got.shape == (M.nnz,)
-    want, stored = W[rows, cols], S[rows, cols]
-    assert np.array_equal(got[~stored].view(np.int64), np.zeros(int((~stored).sum()), dtype=np.int64)), \
-        "a mask position no product reaches is not +0.0"
-    g, w = got[stored], want[stored]
-    if exact:
-        assert np.array_equal(g.view(np.int64), w.view(np.int64)), f"values differ bitwise (max rel {rel_err(g, w):.3e})"
-    else:
-        mag = np.asarray((abs(A) @ abs(B))[rows[stored], cols[stored]]).ravel()
-        assert np.all(np.abs(g - w) <= RTOL * mag), f"values: max rel {rel_err(g, w):.3e}"
 
 
 def _canon(M):

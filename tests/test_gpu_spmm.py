@@ -46,7 +46,7 @@ def _assert_close(got, want, A, X, transpose, what):
 
 
 def _widths(name):
-    return WIDTHS if name in ("uniform", "unsorted_dup", "empty_rows") else [0, 1, 3, 8, 65]
+    return WIDTHS if name in ("uniform", "unsorted_dup", "empty_rows", "boundaries") else [0, 1, 3, 8, 65]
 
 
 @pytest.mark.parametrize("name", list(operands()))
@@ -142,6 +142,49 @@ def test_strides_leave_the_padding_untouched(ctx):
                 ctx.tune_spmm(0)
     finally:
         a.close()
+
+
+@pytest.mark.parametrize("shift_x,shift_y", [(1, 0), (0, 1), (1, 1)])
+def test_views_one_double_into_an_aligned_buffer(ctx, shift_x, shift_y):
+    """X, Y or both start 8 bytes into a 16-byte aligned buffer, with even k, ldx and ldy: the 16-byte path must not be
+    taken on them.  Bits against the restatement under exact; the padding, the element before the view and the tail
+    keep the sentinel."""
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    rng = np.random.default_rng(6)
+    for name in ("unsorted_dup", "boundaries"):
+        A = operands()[name]
+        a = ctx.csr_from_scipy(A)
+        try:
+            for transpose in (False, True):
+                m, kx = op_rows(A, transpose), op_rows(A, not transpose)
+                for k, ldx, ldy in ((2, 2, 2), (8, 10, 12), (64, 64, 66)):
+                    Xp = rng.standard_normal((kx, ldx))
+                    want = restate_spmm(A, Xp[:, :k], transpose)
+                    xbuf = torch.zeros(kx * ldx + 2, dtype=torch.float64, device=dev)
+                    xbuf[shift_x:shift_x + kx * ldx] = torch.from_numpy(Xp.ravel()).to(dev)
+                    dx = xbuf[shift_x:shift_x + kx * ldx]
+                    for mode in MODES:
+                        ctx.tune_spmm(mode)
+                        for exact in (True, False):
+                            ybuf = torch.full((m * ldy + 2,), -7.25, dtype=torch.float64, device=dev)
+                            dy = ybuf[shift_y:shift_y + m * ldy]
+                            assert xbuf.data_ptr() % 16 == 0 and ybuf.data_ptr() % 16 == 0
+                            assert dx.data_ptr() % 16 == 8 * shift_x and dy.data_ptr() % 16 == 8 * shift_y
+                            ctx.spmm_into(a, dx, ldx, k, dy, ldy, transpose=transpose, exact=exact)
+                            flat = ybuf.cpu().numpy()
+                            what = f"{name} T={transpose} k={k} ldy={ldy} mode={mode}"
+                            assert np.all(flat[:shift_y] == -7.25) and np.all(flat[shift_y + m * ldy:] == -7.25), f"outside the view: {what}"
+                            Y = flat[shift_y:shift_y + m * ldy].reshape(m, ldy)
+                            assert np.all(Y[:, k:] == -7.25), f"padding written: {what}"
+                            if exact:
+                                _assert_bits(Y[:, :k], want, what)
+                            else:
+                                _assert_close(Y[:, :k], want, A, Xp[:, :k], transpose, what)
+                    ctx.tune_spmm(0)
+        finally:
+            ctx.tune_spmm(0)
+            a.close()
 
 
 def test_bad_arguments_are_refused(ctx):

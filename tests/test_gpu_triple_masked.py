@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from helpers import arrays, rand_csr, rel_err, shuffle_rows, signed
+from helpers import arrays, check_triple_masked as _check, rand_csr, shuffle_rows, signed, upper_mask as _upper
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
 RTOL = 1e-10
@@ -24,30 +24,6 @@ def _masks(n):
     rnd = rand_csr(n, n, 0.05, 6)
     return {"diag": sp.identity(n, format="csr"), "band": band, "random": rnd,
             "random_unsorted": shuffle_rows(rnd, 7)}
-
-
-def _upper(L, row_begin=0, row_end=None):
-    L = L.tocsr().copy()
-    L.sum_duplicates()
-    U = sp.triu(L, format="csr")
-    U.sort_indices()
-    row_end = L.shape[0] if row_end is None else row_end
-    return U[row_begin:row_end]
-
-
-def _check(res, U, want, H, Q, exact, row_begin=0):
-    ptr, idx, val = res
-    assert np.array_equal(ptr.astype(np.int64), U.indptr.astype(np.int64)), "indptr is not triu(L)'s"
-    assert np.array_equal(idx.astype(np.int64), U.indices.astype(np.int64)), "indices are not triu(L)'s"
-    rows = np.repeat(np.arange(U.shape[0]), np.diff(U.indptr)) + row_begin
-    w = want[rows, idx]
-    if exact:
-        assert np.array_equal(val.view(np.int64), w.view(np.int64)), f"values differ bitwise (max rel {rel_err(val, w):.3e})"
-    else:
-        mag = (abs(H) @ abs(Q) @ abs(H).T).toarray()[rows, idx]
-        assert np.all(np.abs(val - w) <= RTOL * mag), f"values: max rel {rel_err(val, w):.3e}"
-    if exact:                                                  # positions the oracle holds as zero are zeros
-        assert np.array_equal(val[w == 0].view(np.int64) & np.int64(0x7FFFFFFFFFFFFFFF), np.zeros(int((w == 0).sum()), np.int64))
 
 
 @pytest.mark.parametrize("kind", ["diag", "band", "random", "random_unsorted"])

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from helpers import arrays, rand_csr, rel_err, shuffle_rows, signed, wide_csr
+from helpers import (arrays, check_triple_sparse as _check, rand_csr, shuffle_rows, signed, triple_pattern as _pattern,
+                     wide_csr)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
 RTOL = 1e-10
@@ -19,50 +20,9 @@ def _q(k, d, seed):
     return (S + S.T).tocsr()
 
 
-def _ones(m):
-    m = m.copy()
-    m.data = np.ones_like(m.data)
-    return m
-
-
-def _pattern(H, Q, row_begin=0, row_end=None):
-    """(indptr, indices) of triu(Hb @ Qb @ Hb.T)[row_begin:row_end], canonical."""
-    n = H.shape[0]
-    row_end = n if row_end is None else row_end
-    Hb, Qb = _ones(H), _ones(Q)
-    P = sp.triu((Hb @ Qb @ Hb.T).tocsr()).tocsr()[row_begin:row_end]
-    P.sum_duplicates()
-    P.sort_indices()
-    return P.indptr.astype(np.int64), P.indices
-
-
 def _dense(res, rows, n):
     ptr, idx, val = res
     return sp.csr_matrix((val, idx, ptr), shape=(rows, n)).toarray()
-
-
-def _check(res, H, Q, want, exact, row_begin=0, row_end=None):
-    """res: (indptr, indices, data) of rows [row_begin, row_end); want: the oracle's dense n x n triple (full=0)."""
-    n = H.shape[0]
-    row_end = n if row_end is None else row_end
-    ptr, idx, val = res
-    pp, pi = _pattern(H, Q, row_begin, row_end)
-    assert np.array_equal(ptr, pp), "indptr differs from the structural pattern"
-    assert np.array_equal(idx.astype(np.int64), pi.astype(np.int64)), "indices differ from the structural pattern"
-    for i in range(row_end - row_begin):
-        assert np.all(np.diff(idx[ptr[i]:ptr[i + 1]]) > 0), f"row {i}: columns not strictly ascending"
-    rows = np.repeat(np.arange(row_begin, row_end), np.diff(ptr))
-    w = want[rows, idx]
-    if exact:
-        assert np.array_equal(val.view(np.int64), w.view(np.int64)), f"values differ bitwise (max rel {rel_err(val, w):.3e})"
-    else:
-        # relative to the sum of the magnitudes of the terms (signed values cancel: a near-zero sum has no own scale)
-        mag = (abs(H) @ abs(Q) @ abs(H).T).toarray()[rows, idx]
-        assert np.all(np.abs(val - w) <= RTOL * mag), f"values: max rel {rel_err(val, w):.3e}"
-    stored = np.zeros((row_end - row_begin, n), dtype=bool)
-    stored[rows - row_begin, idx] = True
-    upper = np.triu(np.ones((n, n), dtype=bool))[row_begin:row_end]
-    assert not np.any(want[row_begin:row_end][upper & ~stored]), "a nonzero of the oracle is missing from the pattern"
 
 
 def _run(ctx, H, Q, **kw):
