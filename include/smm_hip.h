@@ -50,6 +50,7 @@ enum smm_flags {
                              (what compute_full_matrix=1 was meant to give; SMM_FULL_MATRIX reproduces its
                              doubling bug instead).  Whole square results only.                          */
     SMM_TRANSPOSE   = 16, /* op(A) = A^T in the sparse x dense product (smm_spmm* only)                      */
+    SMM_SCALE_BY_MASK = 32, /* smm_sddmm* only: multiply each result by the mask's stored value                 */
     SMM_EXACT       = 4   /* add every product in exactly the reference's order: float64 values
                              are then bit-identical to the CPU loop, for any legal CSR operand (B with
                              unsorted rows or repeated columns takes an ordered read-modify-write
@@ -350,6 +351,37 @@ int  smm_triple_apply_host(smm_ctx *ctx, smm_csr *h, smm_csr *q, int flags, int6
  * tiny / group / long class (tests).  apply_budget_bytes: bytes of smm_triple_apply's two intermediates per column block,
  * 0 = the default, 1 GiB.  The result's shape and values never depend on either (bit for bit under SMM_EXACT). */
 int  smm_ctx_tune_spmm(smm_ctx *ctx, int mode, int64_t apply_budget_bytes);
+
+/* ------------------------------------------------------------------ sampled dense product: (X Y^T) on a pattern
+ * Writes nnz(mask) values, in the mask's stored order, of C[p] = X[i,:] . Y[j,:] for every stored entry p = (i, j) of mask
+ * (m x n) into caller-owned memory -- SDDMM with dense operands, the dense counterpart of smm_spgemm_masked.  mask may be
+ * any legal CSR: rows may be unsorted and may repeat columns (a repeated position yields a repeated value); its values
+ * are read only with SMM_SCALE_BY_MASK.  X: m x k, Y: n x k, both row-major float64 with leading dimensions ldx, ldy >= k
+ * (one row = one state variable's ensemble members); 64-bit offsets.  d_y == d_x with ldy == ldx is the covariance case
+ * X X^T.  The call allocates no pattern, runs no symbolic phase and builds no transpose.
+ *   SMM_EXACT: s = +0.0; s = s + X[i,e] * Y[j,e] for e = 0 .. k-1, every product rounded before its add: bit-identical to
+ *   that loop for any legal mask, any k, any ld, aligned or unaligned bases.
+ *   Without it, with NP = 2 G and G = ceil(k / 2) rounded up to a power of two in [4, 64] (so NP depends on k alone):
+ *   partial q of NP starts at +0.0 and takes s[q] = fma(X[i,e], Y[j,e], s[q]) for e = q, q + NP, q + 2 NP, ... in ascending
+ *   e; then s[q] = s[q] + s[q + h] for every q that is a multiple of 2 h, for h = 1, 2, 4, ..., NP / 2; the result is s[0].
+ *   The order does not depend on the mask, on a row's length, on the entry's place in its row, on the alignment of the
+ *   operands or on smm_ctx_tune_sddmm: two runs agree bit for bit, and so does one (i, j) in two different masks.
+ *   Within 1e-10 (|X| |Y|^T)[i,j] (times |w| when scaled) of the exact value.  No float atomics.
+ *   SMM_SCALE_BY_MASK: C[p] = mask.data[p] * s, the multiply always carried out (0 * inf = NaN); without it C[p] = s.
+ *   k = 0 writes +0.0 (w * +0.0 when scaled).
+ * X[i,:] and Y[j,:] are read only for the entries that name them: an inf or NaN in row j of Y reaches exactly the entries
+ * of column j, and rows that no entry names are never loaded.
+ * Flags other than SMM_EXACT | SMM_SCALE_BY_MASK, k < 0, ldx < k, ldy < k, NULL buffers that should hold data and an
+ * output range that overlaps X or Y are SMM_ERR_INVALID, before any launch. */
+int  smm_sddmm(smm_ctx *ctx, smm_csr *mask, int flags, int64_t k, const double *d_x, int64_t ldx, const double *d_y, int64_t ldy,
+               double *d_c_data);
+/* Same with host X, Y and c_data (uploaded / downloaded through pool temporaries). */
+int  smm_sddmm_host(smm_ctx *ctx, smm_csr *mask, int flags, int64_t k, const double *x, int64_t ldx, const double *y, int64_t ldy,
+                    double *c_data);
+/* Kernel classes of the sampled dense product: mode 0 = chosen from nnz(mask) (default), 1 = neighbouring lane groups take
+ * neighbouring entries, 2 = every lane group walks a run of consecutive entries and keeps X[i,:] in registers (tests).
+ * Results never depend on it, bit for bit, in either mode. */
+int  smm_ctx_tune_sddmm(smm_ctx *ctx, int mode);
 
 /* ------------------------------------------------------------------ conjugate gradients on (H Q H^T + R) Z = D
  * S = H Q H^T is never formed (H: n x K, Q: K x K, R: n x n sparse or NULL for S alone; the system is expected to be

@@ -21,6 +21,7 @@ SMM_FULL_MATRIX = 2
 SMM_EXACT = 4
 SMM_MIRROR = 8
 SMM_TRANSPOSE = 16
+SMM_SCALE_BY_MASK = 32
 SMM_ERR_ALLOC = -3
 SMM_ERR_UNSUPPORTED = -6
 SMM_ERR_INTERNAL = -7
@@ -101,6 +102,9 @@ V2_PROTOTYPES = {
     "smm_triple_apply": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
     "smm_triple_apply_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
     "smm_ctx_tune_spmm": (ctypes.c_int, [_vp, ctypes.c_int, _c_i64]),
+    "smm_sddmm": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "smm_sddmm_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "smm_ctx_tune_sddmm": (ctypes.c_int, [_vp, ctypes.c_int]),
     "smm_innovation_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_double,
                                             _c_i64, _vp, _vp, _vp, _vp]),
     "smm_innovation_solve_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_double,

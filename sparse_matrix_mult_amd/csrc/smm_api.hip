@@ -9,6 +9,7 @@
 #include "smm_masked.hpp"
 #include "smm_spmm.hpp"
 #include "smm_cg.hpp"
+#include "smm_sddmm.hpp"
 #include "../../include/smm_hip.h"
 
 #include <sys/mman.h>
@@ -100,6 +101,7 @@ struct smm_ctx {
     int masked_mode = 0;                   // masked SpGEMM: 0 per-row cost model, 1 dot path (canonical A only), 2 row path
     int spmm_mode = 0;                     // sparse x dense: 0 rows binned by length, 1 / 2 / 3 every row in the tiny / group / long class
     int64_t apply_budget = (int64_t)1 << 30;   // smm_triple_apply: bytes of the two intermediates of one column block
+    int sddmm_mode = 0;                    // sampled dense product: 0 chosen from nnz(mask), 1 interleaved entries, 2 runs of entries
     int n_cu = 256;
     std::vector<PoolBlock> pool;          // free blocks
     std::map<void *, size_t> live;        // blocks handed out
@@ -3308,6 +3310,102 @@ extern "C" int smm_triple_apply_host(smm_ctx *c, smm_csr *h, smm_csr *q, int fla
     CHK(triple_apply_impl(c, h, q, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
     CHK(take_plan_error(c, "smm_triple_apply_host"));
     return download_rows(c, y, dy, n, k, ldy);
+}
+
+// ------------------------------------------------------------------------------ sampled dense product (X Y^T on a pattern)
+extern "C" int smm_ctx_tune_sddmm(smm_ctx *c, int mode)
+{
+    if (!c || mode < 0 || mode > 2) return fail(SMM_ERR_INVALID, "bad argument (mode: 0 auto, 1 interleaved entries, 2 runs of entries)");
+    CTX_LOCK(c);
+    c->sddmm_mode = mode;
+    return SMM_OK;
+}
+
+// Arguments common to smm_sddmm[_host]: flags, sizes, the mask (any legal CSR of this context).
+static int sddmm_args(smm_ctx *c, smm_csr *mask, int flags, int64_t k, int64_t ldx, int64_t ldy, const char *where)
+{
+    if (flags & ~(SMM_EXACT | SMM_SCALE_BY_MASK)) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT and SMM_SCALE_BY_MASK are flags of this call", where);
+    if (!mask) return fail(SMM_ERR_INVALID, "%s: mask is NULL", where);
+    if (mask->ctx != c) return fail(SMM_ERR_INVALID, "%s: mask belongs to another context", where);
+    if (k < 0 || ldx < k || ldy < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldx, ldy (k %lld, ldx %lld, ldy %lld)", where,
+                                                 (long long)k, (long long)ldx, (long long)ldy);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(validate(c, mask));
+    if ((flags & SMM_SCALE_BY_MASK) && mask->nnz > 0 && !mask->val) return fail(SMM_ERR_INVALID, "%s: SMM_SCALE_BY_MASK needs the mask's values", where);
+    return SMM_OK;
+}
+
+// nnz(mask) values into d_out on the context's stream (validated mask with nnz > 0; sizes and buffers checked by the
+// caller).  One launch: no pattern, no symbolic phase, no transpose, no allocation.
+static int sddmm_impl(smm_ctx *c, const smm_csr *mask, int flags, int64_t k, const double *x, int64_t ldx, const double *y, int64_t ldy,
+                      double *d_out)
+{
+    const bool exact = (flags & SMM_EXACT) != 0;
+    SddmmArgs A{};
+    A.m = (int)mask->rows; A.n = (int)mask->cols; A.nnz = (int)mask->nnz;
+    A.ptr = mask->ptr; A.idx = mask->idx; A.w = mask->val;
+    A.k = k; A.ldx = ldx; A.ldy = ldy; A.x = x; A.y = y; A.out = d_out;
+    A.scale = (flags & SMM_SCALE_BY_MASK) ? 1 : 0;
+    A.err = c->d_err;
+    // 16-byte loads of X and Y where every lane's pair of elements is aligned (the rule of spmm_launch)
+    const int vec = (k % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0) ? 2 : 1;
+    int g = 4;                                         // lanes per entry: one per two elements, 4 .. 64 -- from k alone
+    while (g < WAVE && (int64_t)g * 2 < k) g *= 2;
+    const int gpw = WAVE / g;
+    // runs of entries where the mask has enough of them to fill the device that way, else one entry per group and step
+    const int64_t full = (int64_t)c->n_cu * 16 * gpw * SD_RUN;
+    const int cls = c->sddmm_mode ? c->sddmm_mode : (mask->nnz >= full ? 2 : 1);
+    A.run = cls == 2 ? SD_RUN : 1;
+    const int64_t runs = (mask->nnz + A.run - 1) / A.run, waves = (runs + gpw - 1) / gpw;
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)c->n_cu * 16));
+#define SDDMM_CASE(G_, V_)                                                                                                    \
+    if (g == G_ && vec == V_) {                                                                                               \
+        if (exact) LAUNCH(c, "smm_sddmm", (smm_sddmm<G_, V_, true>), grid, 256, 0, A);                                        \
+        else       LAUNCH(c, "smm_sddmm", (smm_sddmm<G_, V_, false>), grid, 256, 0, A);                                       \
+    }
+    SDDMM_CASE(4, 1) SDDMM_CASE(8, 1) SDDMM_CASE(16, 1) SDDMM_CASE(32, 1) SDDMM_CASE(64, 1)
+    SDDMM_CASE(4, 2) SDDMM_CASE(8, 2) SDDMM_CASE(16, 2) SDDMM_CASE(32, 2) SDDMM_CASE(64, 2)
+#undef SDDMM_CASE
+    LAUNCH_CHECK();
+    return SMM_OK;
+}
+
+extern "C" int smm_sddmm(smm_ctx *c, smm_csr *mask, int flags, int64_t k, const double *d_x, int64_t ldx, const double *d_y, int64_t ldy,
+                         double *d_c_data)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(sddmm_args(c, mask, flags, k, ldx, ldy, "smm_sddmm"));
+    const int64_t xb = span_bytes(mask->rows, k, ldx), yb = span_bytes(mask->cols, k, ldy), cb = mask->nnz * (int64_t)sizeof(double);
+    if ((xb > 0 && !d_x) || (yb > 0 && !d_y) || (cb > 0 && !d_c_data)) return fail(SMM_ERR_INVALID, "smm_sddmm: X, Y or the output is NULL");
+    if (ranges_overlap(d_c_data, cb, d_x, xb) || ranges_overlap(d_c_data, cb, d_y, yb))
+        return fail(SMM_ERR_INVALID, "smm_sddmm: the output's device range overlaps X or Y");
+    if (mask->nnz == 0) return SMM_OK;
+    CHK(sddmm_impl(c, mask, flags, k, d_x, ldx, d_y, ldy, d_c_data));
+    return take_plan_error(c, "smm_sddmm");
+}
+
+// Same with host X, Y and output; y == x with ldy == ldx (a square mask) is uploaded once.
+extern "C" int smm_sddmm_host(smm_ctx *c, smm_csr *mask, int flags, int64_t k, const double *x, int64_t ldx, const double *y, int64_t ldy,
+                              double *c_data)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(sddmm_args(c, mask, flags, k, ldx, ldy, "smm_sddmm_host"));
+    const int64_t m = mask->rows, n = mask->cols;
+    if ((span_bytes(m, k, ldx) > 0 && !x) || (span_bytes(n, k, ldy) > 0 && !y) || (mask->nnz > 0 && !c_data))
+        return fail(SMM_ERR_INVALID, "smm_sddmm_host: X, Y or the output is NULL");
+    if (mask->nnz == 0) return SMM_OK;
+    const bool same = y == x && ldy == ldx && m == n;
+    PoolBuf<double> dx(c), dy(c), dc(c);
+    CHK(dx.alloc((size_t)std::max<int64_t>(m * k, 1)));
+    if (!same) CHK(dy.alloc((size_t)std::max<int64_t>(n * k, 1)));
+    CHK(dc.alloc((size_t)mask->nnz));
+    CHK(upload_rows(c, dx, x, m, k, ldx));
+    if (!same) CHK(upload_rows(c, dy, y, n, k, ldy));
+    CHK(sddmm_impl(c, mask, flags, k, dx, k, same ? (const double *)dx : (const double *)dy, k, dc));
+    CHK(take_plan_error(c, "smm_sddmm_host"));
+    return download(c, c_data, dc, (size_t)mask->nnz * sizeof(double));
 }
 
 // ------------------------------------------------------------------------------ CG on (H Q H^T + R) Z = D

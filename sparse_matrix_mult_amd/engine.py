@@ -9,10 +9,11 @@ import threading
 
 import numpy as np
 
-from ._lib import SMM_EXACT, SMM_FULL_MATRIX, SMM_MIRROR, SMM_SYMMETRIC, SMM_TRANSPOSE, SmmError, SmmLibrary, check
+from ._lib import (SMM_EXACT, SMM_FULL_MATRIX, SMM_MIRROR, SMM_SCALE_BY_MASK, SMM_SYMMETRIC, SMM_TRANSPOSE, SmmError, SmmLibrary,
+                   check)
 
 __all__ = ["Context", "DeviceCSR", "default_context", "SmmError",
-           "SMM_SYMMETRIC", "SMM_FULL_MATRIX", "SMM_EXACT", "SMM_MIRROR", "SMM_TRANSPOSE"]
+           "SMM_SYMMETRIC", "SMM_FULL_MATRIX", "SMM_EXACT", "SMM_MIRROR", "SMM_TRANSPOSE", "SMM_SCALE_BY_MASK"]
 
 
 def _flags(symmetric=False, exact=False, full=False, mirror=False):
@@ -434,6 +435,47 @@ class Context:
             self._sync_torch(d_y)
         check(self.lib, self.lib.smm_triple_apply(self.handle, h.handle, q.handle, _flags(exact=exact), int(k),
                                                   ctypes.c_void_p(_dptr(d_x)), int(ldx), ctypes.c_void_p(_dptr(d_y)), int(ldy)))
+        self.synchronize()
+
+    # ------------------------------------------------------------------ (X Y^T) on a pattern
+    def tune_sddmm(self, mode=0):
+        """Kernel class of the sampled dense product: 0 chosen from nnz(mask) (default), 1 neighbouring lane groups take
+        neighbouring entries, 2 every lane group walks a run of consecutive entries.  Results never depend on it."""
+        check(self.lib, self.lib.smm_ctx_tune_sddmm(self.handle, int(mode)))
+
+    @staticmethod
+    def _host_2d(x, rows, name):
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+        if x.ndim != 2:
+            raise ValueError(f"{name} must be 2-D, got {x.ndim} dimensions")
+        if x.shape[0] != rows:
+            raise ValueError(f"{name} has {x.shape[0]} rows, expected {rows}")
+        return x
+
+    def sddmm_host(self, mask, x, y, scale=False, exact=False):
+        """X[i,:] . Y[j,:] at every stored entry (i, j) of mask (a DeviceCSR, any legal CSR), times the entry's value with
+        scale, in the mask's stored order: a float64 numpy array of nnz(mask) (smm_sddmm_host).  x: m x k, y: n x k numpy
+        arrays (cast to C-contiguous float64); y=None means y = x."""
+        x = self._host_2d(x, mask.rows, "X")
+        y = x if y is None else self._host_2d(y, mask.cols, "Y")
+        if y.shape != (mask.cols, x.shape[1]):
+            raise ValueError(f"Y is {y.shape[0]} x {y.shape[1]}, expected {mask.cols} x {x.shape[1]}")
+        k = x.shape[1]
+        out = np.empty(mask.nnz, dtype=np.float64)
+        flags = _flags(exact=exact) | (SMM_SCALE_BY_MASK if scale else 0)
+        check(self.lib, self.lib.smm_sddmm_host(self.handle, mask.handle, flags, k, _ptr(x), k, _ptr(y), k, _ptr(out)))
+        return out
+
+    def sddmm_into(self, mask, d_x, ldx, d_y, ldy, k, d_c, scale=False, exact=False):
+        """sddmm_host on device buffers: X (mask.rows x k, leading dimension ldx) at d_x, Y (mask.cols x k, leading
+        dimension ldy) at d_y, nnz(mask) float64 written at d_c (smm_sddmm).  Ints (device addresses) or torch tensors;
+        stream rules as spmm_into."""
+        for t in (d_x, d_y, d_c):
+            if hasattr(t, "data_ptr"):
+                self._sync_torch(t)
+        flags = _flags(exact=exact) | (SMM_SCALE_BY_MASK if scale else 0)
+        check(self.lib, self.lib.smm_sddmm(self.handle, mask.handle, flags, int(k), ctypes.c_void_p(_dptr(d_x)), int(ldx),
+                                           ctypes.c_void_p(_dptr(d_y)), int(ldy), ctypes.c_void_p(_dptr(d_c))))
         self.synchronize()
 
     # ------------------------------------------------------------------ CG on (H Q H^T + R) Z = D

@@ -883,6 +883,91 @@ def triple_product_apply(matrix_h, matrix_q, x):
     return _with_leases(ctx, (matrix_h, matrix_q), body)
 
 
+# ------------------------------------------------------------------ (X Y^T) on a pattern
+def _dense_2d(x, rows, what, name):
+    """_dense_operand for an operand that must be 2-D: (X, k, is_torch)."""
+    ndim = x.dim() if type(x).__module__.split(".")[0] == "torch" else np.ndim(x)
+    if ndim != 2:
+        raise ValueError(f"{what}: {name} must be 2-D, got {ndim} dimensions")
+    return _dense_operand(x, rows, what, name)
+
+
+def sampled_dense_product(x, y, mask, scale_by_mask=False):
+    """C = (X @ Y.T) evaluated only at the positions of `mask`, on the GPU (SDDMM with dense operands; the dense
+    counterpart of masked_matrix_multiply).
+
+    x    : m x k, y : n x k (None means y = x, the covariance case X @ X.T); each a 2-D numpy array (cast to float64,
+           C-contiguous) or a float64 CUDA tensor on the library's device.  One row holds one state variable's ensemble
+           members.  A strided tensor with unit column stride (a column slice of a wider tensor) is used in place.
+    mask : m x n; scipy CSR, anything csr_matrix() accepts, or a PinnedOperand (the operand cache applies).
+    C's pattern is exactly the mask's (canonicalised: columns strictly ascending, duplicates merged); explicitly stored
+    zeros are positions.  With scale_by_mask every value is multiplied by the mask's stored value -- C = mask * (X @ Y.T)
+    elementwise, merged duplicates carrying their summed weight (the localised covariance Q = L o (E E^T)); without it
+    the mask's values are ignored.  Under set_exact(True) C[i,j] is bit-identical to s = 0.0; s += X[i,e] * Y[j,e] for
+    e = 0 .. k-1 (times the weight); otherwise within 1e-10 of (|X| @ |Y|.T)[i,j] (times |weight|), in a summation order
+    that depends on k only: the same (i, j) gives the same bits whatever the mask.  X[i,:] and Y[j,:] are read only for
+    the positions that name them.  Returns a scipy CSR (a DeviceCSRResult under set_result_device(True)).  Nothing is
+    printed.
+    """
+    what = "sampled_dense_product"
+    mask = _as_csr(mask)
+    m, n = mask.shape
+    x, k, x_torch = _dense_2d(x, m, what, "X")
+    if y is None:
+        if m != n:
+            raise ValueError(f"{what}: Y has {m} rows, expected {n}")
+        y, y_torch = x, x_torch
+    else:
+        y, ky, y_torch = _dense_2d(y, n, what, "Y")
+        if ky != k:
+            raise ValueError(f"{what}: X has {k} columns, Y has {ky}")
+    out_shape = (m, n)
+    if mask.nnz == 0:
+        return _zero_result(out_shape)
+    if k == 0:
+        ctx = default_context() if (_result_device or isinstance(mask, PinnedOperand)) else None
+        mask = _canonical_mask(mask)
+        indptr, indices = _mask_pattern(mask)
+        data = np.zeros(len(indices), dtype=np.float64)
+        if scale_by_mask:
+            weights = mask._handle.to_host()[2] if isinstance(mask, PinnedOperand) else mask.data[:len(indices)]
+            with np.errstate(invalid="ignore"):
+                data = np.asarray(weights, dtype=np.float64) * data      # (w * +0.0: the weight's sign stays, inf gives NaN)
+        return _pattern_result(ctx, indptr, indices, data, out_shape)
+    ctx = default_context()
+    mask = _canonical_mask(mask)
+
+    def body(lm):
+        indptr, indices = _mask_pattern(mask)
+        if not (x_torch or y_torch or _result_device):
+            data = ctx.sddmm_host(lm.handle, x, None if y is x else y, scale=scale_by_mask, exact=_exact)
+            return _result_csr(indptr, indices, data, out_shape)
+        import torch
+        dev = torch.device("cuda", ctx.device)
+
+        def on_dev(t, is_torch, name):
+            if not is_torch:
+                return torch.from_numpy(t).to(dev)
+            if t.device != dev:
+                raise ValueError(f"{what}: {name} is on {t.device}, the library works on {dev}")
+            return t
+
+        dx = on_dev(x, x_torch, "X")
+        dy = dx if y is x else on_dev(y, y_torch, "Y")
+
+        def call():
+            data = torch.empty(lm.handle.nnz, dtype=torch.float64, device=dev)
+            ctx.sddmm_into(lm.handle, dx, dx.stride(0), dy, dy.stride(0), k, data, scale=scale_by_mask, exact=_exact)
+            return data
+
+        data = _on_device(ctx, call)
+        if _result_device:
+            return _pattern_result(ctx, indptr, indices, data, out_shape)
+        return _result_csr(indptr, indices, data.cpu().numpy(), out_shape)
+
+    return _with_leases(ctx, (mask,), body)
+
+
 # ------------------------------------------------------------------ CG on (H Q H^T + R) Z = D
 CG_LANES = 2048          # SMM_CG_LANES of include/smm_hip.h: the dot product's number of partial sums
 
