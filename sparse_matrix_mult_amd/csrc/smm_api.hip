@@ -204,15 +204,24 @@ template <typename T> struct PoolBuf {
     T *release() { T *q = p; p = nullptr; return q; }
     operator T *() const { return p; }
 };
-// Owner of a dev_malloc'd array until it is committed to an operand or a cache entry (release()).
+// Owner of a dev_malloc'd array, and the record of its size: an operand's own arrays and every cached copy are held
+// by one of these for their whole life (smm_csr_device_bytes sums `bytes`).  An empty one never calls into the runtime:
+// the row views of csr_row_view die on the stack, possibly on a thread that has no device set.
 template <typename T> struct DevBuf {
     T *p = nullptr;
+    int64_t bytes = 0;
     DevBuf() = default;
-    DevBuf(DevBuf &&o) noexcept : p(o.release()) {}
-    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { (void)hipFree(p); p = o.release(); } return *this; }
-    ~DevBuf() { (void)hipFree(p); }
-    hipError_t alloc(smm_ctx *c, size_t count) { return dev_malloc(c, (void **)&p, count * sizeof(T)); }
-    T *release() { T *q = p; p = nullptr; return q; }
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); std::swap(p, o.p); std::swap(bytes, o.bytes); } return *this; }
+    ~DevBuf() { reset(); }
+    hipError_t alloc(smm_ctx *c, size_t count)
+    {
+        reset();
+        const hipError_t e = dev_malloc(c, (void **)&p, count * sizeof(T));
+        if (e == hipSuccess) bytes = (int64_t)(count * sizeof(T));
+        return e;
+    }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
     operator T *() const { return p; }
 };
 // unique_ptr deleter that calls one of the ABI's destroy functions (plans and results under construction)
@@ -759,40 +768,57 @@ static int download(smm_ctx *c, void *dst, const void *src_dev, size_t bytes, bo
 }
 
 // ------------------------------------------------------------------------------ operands
+using CsrPtr = std::unique_ptr<smm_csr, Destroyer<smm_csr_destroy>>;
 struct smm_csr {
     smm_ctx *ctx = nullptr;
     int64_t rows = 0, cols = 0, nnz = 0;
-    const int *ptr = nullptr, *idx = nullptr;
+    const int *ptr = nullptr, *idx = nullptr;    // what everything reads: own_* below, or the caller's arrays (smm_csr_from_device)
     const double *val = nullptr;
-    bool owned = false;
+    DevBuf<int> own_ptr, own_idx; DevBuf<double> own_val;    // empty for a borrowed operand
+    bool owned() const { return own_ptr.p != nullptr; }
     bool validated = false;
     unsigned vflags = 0;
+    // Cached copies.  Every entry owns its arrays; plans and launch code get plain values (a raw pointer, or a *View),
+    // never a pointer into a vector here, which may grow.  The device arrays themselves never move once built.
     // cached tile indices (sorted operands only), one per tile geometry that has been asked for:
     // plans keep the pointer of theirs, so a later product with another geometry (SMM_EXACT vs
     // default, another tuning, the ELL chunks of the triple product) never invalidates it
-    struct SegCache { int wf, n_ft; int *seg; };
-    struct LocCache { int wc; short *loc; };          // tile-local columns for coarse width wc
-    struct SlabCache { int ws, n_slabs; int *soff; short *scol; double *sval; };   // slab-major copy (smm_slab.hpp)
+    struct SegCache { int wf, n_ft; DevBuf<int> seg; };
+    struct LocCache { int wc; DevBuf<short> loc; };   // tile-local columns for coarse width wc
+    // slab-major copy (smm_slab.hpp); seg: the tile index it was built from (one of segs), as in the entries below
+    struct SlabView { int ws, n_slabs; int *soff; short *scol; double *sval; };
+    struct SlabCache {
+        int ws, n_slabs; const int *seg; DevBuf<int> soff; DevBuf<short> scol; DevBuf<double> sval;
+        SlabView view() const { return {ws, n_slabs, soff, scol, sval}; }
+    };
+    // packed tile-major payload (smm_pack_*); maxlen: longest piece
+    struct PackView { int wc, nct; int2 *desc; double *pay; int maxlen; };
+    struct PackCache {
+        int wc, nct; const int *seg; DevBuf<int2> desc; DevBuf<double> pay; int maxlen;
+        PackView view() const { return {wc, nct, desc, pay, maxlen}; }
+    };
+    // chunk-padded 16-bit column stream per column slab (smm_ccs_*): the symbolic phase's gather stream
+    // (same_word: share of neighbouring entries in one bitmap word)
+    struct CcsView { int ws, n_slabs, bm_words, guard_chunk; int *cptr; unsigned short *stream; double same_word; };
+    struct CcsCache {
+        int ws, n_slabs, bm_words, guard_chunk; DevBuf<int> cptr; DevBuf<unsigned short> stream; double same_word;
+        CcsView view() const { return {ws, n_slabs, bm_words, guard_chunk, cptr, stream, same_word}; }
+    };
+    // sliced-ELL copy for triple-product stage 2 (chunk width `chunk`); built = val holds an array
+    struct EllCopy { int chunk = 0, nchunks = 0; bool spread = false; const int *seg = nullptr; DevBuf<int64_t> off; DevBuf<short> col; DevBuf<double> val; };
+    // scheduled streams for the ring kernel of triple-product stage 2 (smm_ring.hpp), one per (k-group, wave)
+    struct RingCopy { int npieces = 0; bool spread = false; DevBuf<int64_t> off; DevBuf<short> col; DevBuf<double> val; DevBuf<unsigned> hdr; };
     std::vector<SegCache> segs;
     std::vector<LocCache> locs;
-    struct PackCache { int wc, nct; int2 *desc; double *pay; int maxlen; };   // packed tile-major payload (smm_pack_*); longest piece
     std::vector<SlabCache> slabs;
     std::vector<PackCache> packs;
-    // chunk-padded 16-bit column stream per column slab (smm_ccs_*): the symbolic phase's gather stream
-    struct CcsCache { int ws, n_slabs, bm_words, guard_chunk; int *cptr; unsigned short *stream; double same_word; };   // same_word: share of neighbouring entries in one bitmap word
     std::vector<CcsCache> ccs;
-    unsigned short *idx16 = nullptr;             // 16-bit copy of idx (cols < 65535): the symbolic phase's gather stream
-    int *idx_pad = nullptr;                      // borrowed operands with >= 65535 columns: a copy of idx with two ints of slack (wide symbolic walk)
-    // sliced-ELL copy for triple-product stage 2 (chunk width ell_chunk)
-    int ell_chunk = 0, ell_nchunks = 0; bool ell_spread = false; int64_t *ell_off = nullptr;
-    short *ell_col = nullptr; double *ell_val = nullptr;
-    int64_t ell_bytes = 0;                       // HBM of the ELL copy
-    // scheduled streams for the ring kernel of triple-product stage 2 (smm_ring.hpp), one per (k-group, wave)
-    int64_t *ring_off = nullptr; short *ring_col = nullptr; double *ring_val = nullptr; unsigned *ring_hdr = nullptr;
-    int ring_npieces = 0; bool ring_spread = false; int64_t ring_bytes = 0;
-    int64_t derived_bytes = 0;                   // HBM of every other cached copy (tile indices, payloads, ...)
-    smm_csr *tr = nullptr;                       // H^T for the sparse triple product (pattern only: update_values leaves it)
-    smm_csr *trv = nullptr;                      // A^T with values: the masked SpGEMM's dot path (B^T), the transposed sparse x dense
+    DevBuf<unsigned short> idx16;                // 16-bit copy of idx (cols < 65535): the symbolic phase's gather stream
+    DevBuf<int> idx_pad;                         // borrowed operands with >= 65535 columns: a copy of idx with two ints of slack (wide symbolic walk)
+    EllCopy ell;
+    RingCopy ring;
+    CsrPtr tr;                                   // H^T for the sparse triple product (pattern only: update_values leaves it)
+    CsrPtr trv;                                  // A^T with values: the masked SpGEMM's dot path (B^T), the transposed sparse x dense
                                                  // product and H^T of smm_triple_apply; built on first use, update_values drops it
 };
 
@@ -835,6 +861,22 @@ static int csr_common(smm_ctx *c, int64_t rows, int64_t cols, int64_t nnz)
     return SMM_OK;
 }
 
+static CsrPtr new_csr(smm_ctx *c, int64_t rows, int64_t cols, int64_t nnz)
+{
+    CsrPtr m(new smm_csr());
+    m->ctx = c; m->rows = rows; m->cols = cols; m->nnz = nnz;
+    return m;
+}
+// The three arrays of an operand that owns them (idx with 2 ints of slack: the wide symbolic walk reads columns in pairs).
+static int alloc_owned(smm_ctx *c, smm_csr *m, const char *what)
+{
+    const size_t n = (size_t)std::max<int64_t>(m->nnz, 1);
+    if (m->own_ptr.alloc(c, (size_t)m->rows + 1) != hipSuccess || m->own_idx.alloc(c, n + 2) != hipSuccess || m->own_val.alloc(c, n) != hipSuccess)
+        return fail(SMM_ERR_ALLOC, "hipMalloc of %s failed", what);
+    m->ptr = m->own_ptr; m->idx = m->own_idx; m->val = m->own_val;
+    return SMM_OK;
+}
+
 extern "C" int smm_csr_from_host(smm_ctx *c, int64_t rows, int64_t cols, int64_t nnz, const int32_t *indptr,
                                  const int32_t *indices, const double *data, smm_csr **out)
 {
@@ -843,22 +885,16 @@ extern "C" int smm_csr_from_host(smm_ctx *c, int64_t rows, int64_t cols, int64_t
     CHK(csr_common(c, rows, cols, nnz));
     CTX_LOCK(c);
     if (!indptr || (nnz > 0 && (!indices || !data))) return fail(SMM_ERR_INVALID, "NULL CSR array");
-    DevBuf<int> dp, di; DevBuf<double> dv;
-    if (dp.alloc(c, rows + 1) != hipSuccess || di.alloc(c, std::max<int64_t>(nnz, 1) + 2) != hipSuccess ||     // + slack: the wide symbolic walk reads columns in pairs
-        dv.alloc(c, std::max<int64_t>(nnz, 1)) != hipSuccess)
-        return fail(SMM_ERR_ALLOC, "hipMalloc of a CSR operand failed");
-    HIPCHK(hipMemcpyAsync(dp, indptr, (rows + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    CsrPtr m = new_csr(c, rows, cols, nnz);
+    CHK(alloc_owned(c, m.get(), "a CSR operand"));
+    HIPCHK(hipMemcpyAsync(m->own_ptr, indptr, (rows + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     if (nnz > 0) {
-        HIPCHK(hipMemcpyAsync(di, indices, nnz * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(dv, data, nnz * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(m->own_idx, indices, nnz * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(m->own_val, data, nnz * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
-    smm_csr *m = new smm_csr();
-    m->ctx = c; m->rows = rows; m->cols = cols; m->nnz = nnz;
-    m->ptr = dp.release(); m->idx = di.release(); m->val = dv.release(); m->owned = true;
-    int rc = validate(c, m);
-    if (rc != SMM_OK) { smm_csr_destroy(m); return rc; }
-    *out = m;
+    CHK(validate(c, m.get()));
+    *out = m.release();
     return SMM_OK;
 }
 
@@ -870,32 +906,20 @@ extern "C" int smm_csr_from_device(smm_ctx *c, int64_t rows, int64_t cols, int64
     CHK(csr_common(c, rows, cols, nnz));
     CTX_LOCK(c);
     if (!d_indptr || (nnz > 0 && (!d_indices || !d_data))) return fail(SMM_ERR_INVALID, "NULL CSR array");
-    smm_csr *m = new smm_csr();
-    m->ctx = c; m->rows = rows; m->cols = cols; m->nnz = nnz;
-    m->ptr = d_indptr; m->idx = d_indices; m->val = d_data; m->owned = false;
-    int rc = validate(c, m);
-    if (rc != SMM_OK) { delete m; return rc; }
-    *out = m;
+    CsrPtr m = new_csr(c, rows, cols, nnz);
+    m->ptr = d_indptr; m->idx = d_indices; m->val = d_data;
+    CHK(validate(c, m.get()));
+    *out = m.release();
     return SMM_OK;
 }
 
+// (every array the handle owns, and its transposes, go with it: the members' destructors)
 extern "C" void smm_csr_destroy(smm_csr *m)
 {
     if (!m) return;
     CTX_LOCK(m->ctx);
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
-    if (m->owned) { (void)hipFree((void *)m->ptr); (void)hipFree((void *)m->idx); (void)hipFree((void *)m->val); }
-    for (auto &e : m->segs) (void)hipFree(e.seg);
-    for (auto &e : m->locs) (void)hipFree(e.loc);
-    for (auto &e : m->slabs) { (void)hipFree(e.soff); (void)hipFree(e.scol); (void)hipFree(e.sval); }
-    for (auto &e : m->packs) { (void)hipFree(e.desc); (void)hipFree(e.pay); }
-    for (auto &e : m->ccs) { (void)hipFree(e.cptr); (void)hipFree(e.stream); }
-    (void)hipFree(m->idx16); (void)hipFree(m->idx_pad);
-    (void)hipFree(m->ell_off); (void)hipFree(m->ell_col); (void)hipFree(m->ell_val);
-    (void)hipFree(m->ring_off); (void)hipFree(m->ring_col); (void)hipFree(m->ring_val); (void)hipFree(m->ring_hdr);
-    smm_csr_destroy(m->tr);
-    smm_csr_destroy(m->trv);
     delete m;
 }
 extern "C" int64_t smm_csr_rows(const smm_csr *m) { return m ? m->rows : -1; }
@@ -913,14 +937,22 @@ extern "C" int64_t smm_csr_device_bytes(const smm_csr *m)
 {
     if (!m) return -1;
     CTX_LOCK(m->ctx);
-    int64_t own = 0;
-    if (m->owned) own = (m->rows + 1) * (int64_t)sizeof(int) + (std::max<int64_t>(m->nnz, 1) + 2) * (int64_t)sizeof(int) + std::max<int64_t>(m->nnz, 1) * (int64_t)sizeof(double);
-    return own + m->derived_bytes + m->ell_bytes + m->ring_bytes + (m->tr ? smm_csr_device_bytes(m->tr) : 0) +
-           (m->trv ? smm_csr_device_bytes(m->trv) : 0);
+    // HBM of everything the handle owns: what each array's owner recorded when it allocated it
+    int64_t total = m->own_ptr.bytes + m->own_idx.bytes + m->own_val.bytes + m->idx16.bytes + m->idx_pad.bytes;
+    for (auto &e : m->segs) total += e.seg.bytes;
+    for (auto &e : m->locs) total += e.loc.bytes;
+    for (auto &e : m->slabs) total += e.soff.bytes + e.scol.bytes + e.sval.bytes;
+    for (auto &e : m->packs) total += e.desc.bytes + e.pay.bytes;
+    for (auto &e : m->ccs) total += e.cptr.bytes + e.stream.bytes;
+    total += m->ell.off.bytes + m->ell.col.bytes + m->ell.val.bytes;
+    total += m->ring.off.bytes + m->ring.col.bytes + m->ring.val.bytes + m->ring.hdr.bytes;
+    return total + (m->tr ? smm_csr_device_bytes(m->tr.get()) : 0) + (m->trv ? smm_csr_device_bytes(m->trv.get()) : 0);
 }
 
 // Tile geometry: nct coarse tiles of wc = nw*wf columns; fine tile t covers [t*wf,(t+1)*wf).
 struct Geom { int nct, wc, wf, n_ft, nw; };
+// n tiles of width w, one wave: the tile index behind a packed payload, a slab copy, a column stream, the ELL chunks
+static Geom tiles_geom(int n, int w) { return Geom{n, w, w, n, 1}; }
 static Geom make_geom(const smm_ctx *c, int64_t ncols, const smm_csr *b, bool exact)
 {
     Geom g;
@@ -966,8 +998,7 @@ static int ensure_seg(smm_ctx *c, smm_csr *b, const Geom &g, const int **out)
         LAUNCH_CHECK();
     }
     *out = seg;
-    b->segs.push_back({g.wf, g.n_ft, seg.release()});
-    b->derived_bytes += std::max<int64_t>(total, 1) * (int64_t)sizeof(int);
+    b->segs.push_back({g.wf, g.n_ft, std::move(seg)});
     return SMM_OK;
 }
 
@@ -982,8 +1013,7 @@ static int ensure_idx16(smm_ctx *c, smm_csr *b)
         LAUNCH(c, "smm_idx16", smm_idx16, std::min<int64_t>((b->nnz + 255) / 256, 65536), 256, 0, (int)b->nnz, b->idx, idx16);
         LAUNCH_CHECK();
     }
-    b->idx16 = idx16.release();
-    b->derived_bytes += (std::max<int64_t>(b->nnz, 1) + 2) * (int64_t)sizeof(unsigned short);
+    b->idx16 = std::move(idx16);
     return SMM_OK;
 }
 
@@ -992,15 +1022,14 @@ static int ensure_idx16(smm_ctx *c, smm_csr *b)
 // where the caller's allocation may end, so the walk reads a padded copy of it instead (made once per handle).
 static int idx_with_slack(smm_ctx *c, smm_csr *b, const int **out)
 {
-    if (b->owned) { *out = b->idx; return SMM_OK; }
+    if (b->owned()) { *out = b->idx; return SMM_OK; }
     if (!b->idx_pad) {
         const size_t n = (size_t)std::max<int64_t>(b->nnz, 1) + 2;
         DevBuf<int> pad;
         if (pad.alloc(c, n) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the padded column copy failed");
         HIPCHK(hipMemsetAsync(pad + (n - 2), 0, 2 * sizeof(int), c->stream));
         if (b->nnz > 0) HIPCHK(hipMemcpyAsync(pad, b->idx, (size_t)b->nnz * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-        b->idx_pad = pad.release();
-        b->derived_bytes += (int64_t)(n * sizeof(int));
+        b->idx_pad = std::move(pad);
     }
     *out = b->idx_pad;
     return SMM_OK;
@@ -1018,100 +1047,101 @@ static int ensure_loc(smm_ctx *c, smm_csr *b, const Geom &g, const short **out)
         LAUNCH_CHECK();
     }
     *out = loc;
-    b->locs.push_back({g.wc, loc.release()});
-    b->derived_bytes += std::max<int64_t>(b->nnz, 1) * (int64_t)sizeof(short);
+    b->locs.push_back({g.wc, std::move(loc)});
     return SMM_OK;
 }
 
 // Sliced-ELL re-layout of H for triple-product stage 2 (see smm_triple_stage2); one copy is cached per
 // handle, for one chunk width and one order of the steps (spread = any order inside a segment, the default
 // mode's; otherwise stored order with idle steps, SMM_EXACT's -- smm_ell_fill).
+static EllArgs ell_args(const smm_csr *h, const smm_csr::EllCopy &e)
+{
+    EllArgs E{};
+    E.n = (int)h->rows; E.nchunks = e.nchunks; E.chunk = e.chunk; E.nslices = (int)((h->rows + WAVE - 1) / WAVE);
+    E.h_ptr = h->ptr; E.h_idx = h->idx; E.h_val = h->val; E.hseg = e.seg;
+    E.off = e.off; E.col = e.col; E.val = e.val;
+    return E;
+}
+// The payload of e from h's current values (one wave per (chunk, slice)); queued, not checked.
+static void ell_fill(smm_ctx *c, const smm_csr *h, const smm_csr::EllCopy &e)
+{
+    const EllArgs E = ell_args(h, e);
+    const int64_t items = (int64_t)E.nchunks * E.nslices;
+    auto kern = e.spread ? smm_ell_fill<1> : smm_ell_fill<2>;
+    if (items > 0) LAUNCH(c, "smm_ell_fill", kern, (int)((items + 3) / 4), 256, 0, E);
+}
 static int ensure_ell(smm_ctx *c, smm_csr *h, int nchunks, int chunk, bool spread)
 {
-    if (h->ell_val && h->ell_chunk == chunk && h->ell_nchunks == nchunks && h->ell_spread == spread) return SMM_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(h->ell_off); (void)hipFree(h->ell_col); (void)hipFree(h->ell_val);
-    h->ell_off = nullptr; h->ell_col = nullptr; h->ell_val = nullptr; h->ell_chunk = 0; h->ell_bytes = 0;
-    Geom gh; gh.nw = 1; gh.nct = nchunks; gh.wf = chunk; gh.wc = chunk; gh.n_ft = nchunks;
-    const int *hseg = nullptr;
-    CHK(ensure_seg(c, h, gh, &hseg));
-    const int n = (int)h->rows;
-    const int nslices = (n + WAVE - 1) / WAVE;
-    const int64_t items = (int64_t)nchunks * nslices;
+    if (h->ell.val && h->ell.chunk == chunk && h->ell.nchunks == nchunks && h->ell.spread == spread) return SMM_OK;
+    smm_csr::EllCopy e;                                 // built here, then put in the old copy's place
+    e.chunk = chunk; e.nchunks = nchunks; e.spread = spread;
+    CHK(ensure_seg(c, h, tiles_geom(nchunks, chunk), &e.seg));
+    const int64_t items = (int64_t)nchunks * ((h->rows + WAVE - 1) / WAVE);
     if (items >= 0x7fffffff) return fail(SMM_ERR_INVALID, "H too large for the sliced-ELL index (%lld blocks)", (long long)items);
     PoolBuf<int64_t> cnt(c);
-    DevBuf<int64_t> off;
     CHK(cnt.alloc((size_t)items));
-    if (off.alloc(c, (size_t)items + 1) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the ELL index failed");
-    EllArgs E{};
-    E.n = n; E.nchunks = nchunks; E.chunk = chunk; E.nslices = nslices;
-    E.h_ptr = h->ptr; E.h_idx = h->idx; E.h_val = h->val; E.hseg = hseg;
-    E.cnt = cnt; E.off = off;
-    const int grid = (int)((items + 3) / 4);
-    LAUNCH(c, "smm_ell_count", smm_ell_count, grid, 256, 0, E);
-    LAUNCH(c, "smm_scan", smm_scan<int64_t>, 1, 1024, 0, (int)items, (const int64_t *)cnt, off);
+    if (e.off.alloc(c, (size_t)items + 1) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the ELL index failed");
+    EllArgs E = ell_args(h, e);
+    E.cnt = cnt;
+    LAUNCH(c, "smm_ell_count", smm_ell_count, (int)((items + 3) / 4), 256, 0, E);
+    LAUNCH(c, "smm_scan", smm_scan<int64_t>, 1, 1024, 0, (int)items, (const int64_t *)cnt, e.off.p);
     int64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, off + items, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&total, e.off + items, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     cnt.reset();
     // + one wave of slack: stage 2 requests step 0 of a block before it knows the block is empty
-    DevBuf<short> col; DevBuf<double> val;
-    if (col.alloc(c, total + WAVE) != hipSuccess || val.alloc(c, total + WAVE) != hipSuccess)
+    if (e.col.alloc(c, total + WAVE) != hipSuccess || e.val.alloc(c, total + WAVE) != hipSuccess)
         return fail(SMM_ERR_ALLOC, "hipMalloc of the ELL payload (%lld entries) failed", (long long)total);
-    E.col = col; E.val = val;
-    if (spread) LAUNCH(c, "smm_ell_fill", smm_ell_fill<1>, grid, 256, 0, E);
-    else LAUNCH(c, "smm_ell_fill", smm_ell_fill<2>, grid, 256, 0, E);
+    ell_fill(c, h, e);
     LAUNCH_CHECK();
-    h->ell_off = off.release(); h->ell_col = col.release(); h->ell_val = val.release();
-    h->ell_chunk = chunk; h->ell_nchunks = nchunks; h->ell_spread = spread;
-    h->ell_bytes = (items + 1) * (int64_t)sizeof(int64_t) + (total + WAVE) * (int64_t)(sizeof(short) + sizeof(double));
+    HIPCHK(hipStreamSynchronize(c->stream));            // nothing queued reads the old copy any more
+    h->ell = std::move(e);
     return SMM_OK;
 }
 
 // Scheduled streams of H for the ring kernel of triple-product stage 2 (smm_ring.hpp); one copy cached per handle and
 // order (spread = default mode: a lane picks among its next 8 entries; otherwise stored order, SMM_EXACT).
-static int ring_fill(smm_ctx *c, smm_csr *h, RingBuildArgs &B, bool spread)
+static RingBuildArgs ring_args(smm_ctx *c, const smm_csr *h, const smm_csr::RingCopy &e)
 {
-    if (spread) LAUNCH(c, "smm_ring_build", (smm_ring_build<8, true>), B.nkg, 1024, 0, B);
-    else LAUNCH(c, "smm_ring_build", (smm_ring_build<1, true>), B.nkg, 1024, 0, B);
-    LAUNCH_CHECK();
-    return SMM_OK;
+    RingBuildArgs B{};
+    B.n = (int)h->rows; B.K = (int)h->cols; B.npieces = e.npieces; B.nkg = (int)((h->rows + 16 * WAVE - 1) / (16 * WAVE));
+    B.h_ptr = h->ptr; B.h_idx = h->idx; B.h_val = h->val;
+    B.off = e.off; B.col = e.col; B.val = e.val; B.hdr = e.hdr; B.err = c->d_err;
+    return B;
+}
+// The streams of e from h's current values (the build kernel's second pass); queued, not checked.
+static void ring_fill(smm_ctx *c, const smm_csr *h, const smm_csr::RingCopy &e)
+{
+    const RingBuildArgs B = ring_args(c, h, e);
+    auto kern = e.spread ? smm_ring_build<8, true> : smm_ring_build<1, true>;
+    LAUNCH(c, "smm_ring_build", kern, B.nkg, 1024, 0, B);
 }
 static int ensure_ring(smm_ctx *c, smm_csr *h, bool spread)
 {
     const int npieces = (int)((h->cols + RING_PW - 1) / RING_PW);
-    if (h->ring_val && h->ring_npieces == npieces && h->ring_spread == spread) return SMM_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(h->ring_off); (void)hipFree(h->ring_col); (void)hipFree(h->ring_val); (void)hipFree(h->ring_hdr);
-    h->ring_off = nullptr; h->ring_col = nullptr; h->ring_val = nullptr; h->ring_hdr = nullptr; h->ring_bytes = 0;
-    const int n = (int)h->rows;
-    const int nkg = (n + 16 * WAVE - 1) / (16 * WAVE);
-    const int64_t streams = (int64_t)nkg * 16;
+    if (h->ring.val && h->ring.npieces == npieces && h->ring.spread == spread) return SMM_OK;
+    smm_csr::RingCopy e;                                // built here, then put in the old copy's place
+    e.npieces = npieces; e.spread = spread;
     PoolBuf<int64_t> cnt(c);
-    DevBuf<int64_t> off;
+    RingBuildArgs B = ring_args(c, h, e);
+    const int64_t streams = (int64_t)B.nkg * 16;
     CHK(cnt.alloc((size_t)streams));
-    if (off.alloc(c, (size_t)streams + 1) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the ring stream index failed");
-    RingBuildArgs B{};
-    B.n = n; B.K = (int)h->cols; B.npieces = npieces; B.nkg = nkg;
-    B.h_ptr = h->ptr; B.h_idx = h->idx; B.h_val = h->val;
-    B.cnt = cnt; B.off = off; B.err = c->d_err;
-    if (spread) LAUNCH(c, "smm_ring_build", (smm_ring_build<8, false>), nkg, 1024, 0, B);
-    else LAUNCH(c, "smm_ring_build", (smm_ring_build<1, false>), nkg, 1024, 0, B);
-    LAUNCH(c, "smm_scan", smm_scan<int64_t>, 1, 1024, 0, (int)streams, (const int64_t *)cnt, off);
+    if (e.off.alloc(c, (size_t)streams + 1) != hipSuccess) return fail(SMM_ERR_ALLOC, "hipMalloc of the ring stream index failed");
+    B.cnt = cnt; B.off = e.off;
+    auto count = spread ? smm_ring_build<8, false> : smm_ring_build<1, false>;
+    LAUNCH(c, "smm_ring_build", count, B.nkg, 1024, 0, B);
+    LAUNCH(c, "smm_scan", smm_scan<int64_t>, 1, 1024, 0, (int)streams, (const int64_t *)cnt, e.off.p);
     int64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, off + streams, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&total, e.off + streams, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     cnt.reset();
-    DevBuf<short> col; DevBuf<double> val; DevBuf<unsigned> hdr;
-    if (col.alloc(c, (size_t)(total + 1) * WAVE) != hipSuccess || val.alloc(c, (size_t)(total + 1) * WAVE) != hipSuccess ||
-        hdr.alloc(c, (size_t)(total + streams + 64)) != hipSuccess)
+    if (e.col.alloc(c, (size_t)(total + 1) * WAVE) != hipSuccess || e.val.alloc(c, (size_t)(total + 1) * WAVE) != hipSuccess ||
+        e.hdr.alloc(c, (size_t)(total + streams + 64)) != hipSuccess)
         return fail(SMM_ERR_ALLOC, "hipMalloc of the ring streams (%lld steps) failed", (long long)total);
-    B.col = col; B.val = val; B.hdr = hdr;
-    CHK(ring_fill(c, h, B, spread));
-    h->ring_off = off.release(); h->ring_col = col.release(); h->ring_val = val.release(); h->ring_hdr = hdr.release();
-    h->ring_npieces = npieces; h->ring_spread = spread;
-    h->ring_bytes = (streams + 1) * (int64_t)sizeof(int64_t) + (total + 1) * WAVE * (int64_t)(sizeof(short) + sizeof(double)) +
-                    (total + streams + 64) * (int64_t)sizeof(unsigned);
+    ring_fill(c, h, e);
+    LAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));            // nothing queued reads the old copy any more
+    h->ring = std::move(e);
     return take_plan_error(c, "smm_ring_build");
 }
 
@@ -1255,10 +1285,10 @@ struct smm_plan {
     unsigned char *d_tflag = nullptr;   // nct x m: which (tile, row) units hold entries of C
     const int *seg = nullptr;      // B's tile index and tile-local columns for geometry g (owned by b)
     const short *loc = nullptr;
-    smm_csr::PackCache pack{0, 0, nullptr, nullptr, 0};   // default mode: packed payload of B for geometry g
+    smm_csr::PackView pack{0, 0, nullptr, nullptr, 0};    // default mode: packed payload of B for geometry g
     bool use_slab = false;         // dense-bin rows: smm_dense_slab -> scratch -> emission, instead of the tile kernel
     SlabGeom sg{};
-    smm_csr::SlabCache slab{0, 0, nullptr, nullptr, nullptr};
+    smm_csr::SlabView slab{0, 0, nullptr, nullptr, nullptr};
     int *d_rowcnt = nullptr;       // m
     int64_t total_cap = 0;         // sum of the list capacities (= d_ub_off's last entry)
     int *d_lists = nullptr;        // 5 x m: rows of the small / medium / dense / tiny (16) / tiny (32) bins
@@ -1315,15 +1345,21 @@ static int scan_launch(smm_ctx *c, int64_t n, const T *in, int64_t *out)
 }
 
 // Packed tile-major payload of B for the shared-tile walk (smm_pack_* in smm_kernels.hpp), cached per geometry.
+// pack_fill: the payload of e from b's current values; queued, not checked.
+static void pack_fill(smm_ctx *c, const smm_csr *b, const smm_csr::PackCache &e)
+{
+    if ((int64_t)e.nct * b->rows > 0)
+        LAUNCH(c, "smm_pack_fill", smm_pack_fill, std::min<int64_t>((b->rows + 3) / 4, 65536), 256, 0, (int)b->rows, e.nct, e.wc, b->ptr,
+               b->idx, b->val, e.seg, (const int2 *)e.desc, e.pay.p);
+}
 // (descriptors are handed out BY VALUE: a plan must not point into the operand's vector, which may grow)
-static int ensure_pack(smm_ctx *c, smm_csr *b, const Geom &g, smm_csr::PackCache *out)
+static int ensure_pack(smm_ctx *c, smm_csr *b, const Geom &g, smm_csr::PackView *out)
 {
     for (auto &e : b->packs)
-        if (e.wc == g.wc && e.nct == g.nct) { *out = e; return SMM_OK; }
+        if (e.wc == g.wc && e.nct == g.nct) { *out = e.view(); return SMM_OK; }
     if (g.wc > 32767) return fail(SMM_ERR_INVALID, "coarse tile wider than 32767 columns");
-    Geom gs = g; gs.wf = g.wc; gs.n_ft = g.nct;               // the coarse-tile index (shared walk: one entry per coarse tile)
-    const int *seg = nullptr;
-    CHK(ensure_seg(c, b, gs, &seg));
+    smm_csr::PackCache e{g.wc, g.nct, nullptr, {}, {}, 0};
+    CHK(ensure_seg(c, b, tiles_geom(g.nct, g.wc), &e.seg));   // the coarse-tile index (shared walk: one entry per coarse tile)
     const int64_t cells = (int64_t)g.nct * b->rows;
     if (cells + 1 >= INT32_MAX) return fail(SMM_ERR_INVALID, "too many (tile, row) pieces");
     PoolBuf<int> units(c);
@@ -1332,43 +1368,37 @@ static int ensure_pack(smm_ctx *c, smm_csr *b, const Geom &g, smm_csr::PackCache
     CHK(off64.alloc((size_t)cells + 1));
     int *d_maxlen = (int *)((char *)c->d_flags + 244);
     (void)hipMemsetAsync(d_maxlen, 0, sizeof(int), c->stream);
-    if (cells > 0) LAUNCH(c, "smm_pack_count", smm_pack_count, (cells + 255) / 256, 256, 0, (int)b->rows, g.nct, seg, units, d_maxlen);
+    if (cells > 0) LAUNCH(c, "smm_pack_count", smm_pack_count, (cells + 255) / 256, 256, 0, (int)b->rows, g.nct, e.seg, units, d_maxlen);
     CHK(scan_launch<int>(c, cells, units, off64));
     int64_t total = 0;
-    int maxlen = 0;
     HIPCHK(hipMemcpyAsync(&total, off64 + cells, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&maxlen, d_maxlen, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&e.maxlen, d_maxlen, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (total >= INT32_MAX) return fail(SMM_ERR_INVALID, "operand too large for the packed payload");
     // (+ 4 units of slack: the piece walk's last lane reads up to three 8-byte units past a very short last piece)
-    DevBuf<int2> desc; DevBuf<double> pay;
-    if (desc.alloc(c, (size_t)std::max<int64_t>(cells, 1)) != hipSuccess || pay.alloc(c, (size_t)(std::max<int64_t>(total, 1) + 4)) != hipSuccess)
+    if (e.desc.alloc(c, (size_t)std::max<int64_t>(cells, 1)) != hipSuccess || e.pay.alloc(c, (size_t)(std::max<int64_t>(total, 1) + 4)) != hipSuccess)
         return fail(SMM_ERR_ALLOC, "hipMalloc of the packed payload failed");
     if (cells > 0) {
-        LAUNCH(c, "smm_pack_desc", smm_pack_desc, (cells + 255) / 256, 256, 0, (int)b->rows, g.nct, seg, (const int64_t *)off64, desc);
-        LAUNCH(c, "smm_pack_fill", smm_pack_fill, std::min<int64_t>((b->rows + 3) / 4, 65536), 256, 0, (int)b->rows, g.nct, g.wc, b->ptr,
-               b->idx, b->val, seg, (const int2 *)desc, pay);
+        LAUNCH(c, "smm_pack_desc", smm_pack_desc, (cells + 255) / 256, 256, 0, (int)b->rows, g.nct, e.seg, (const int64_t *)off64, e.desc.p);
+        pack_fill(c, b, e);
         LAUNCH_CHECK();
         HIPCHK(hipStreamSynchronize(c->stream));        // units / off64 go back to the pool
     }
     units.reset(); off64.reset();
-    smm_csr::PackCache e{g.wc, g.nct, desc.release(), pay.release(), maxlen};
-    b->packs.push_back(e);
-    b->derived_bytes += std::max<int64_t>(cells, 1) * (int64_t)sizeof(int2) + (std::max<int64_t>(total, 1) + 4) * (int64_t)sizeof(double);
-    *out = e;
+    *out = e.view();
+    b->packs.push_back(std::move(e));
     return SMM_OK;
 }
 
 // Chunk-padded 16-bit column stream of B for the symbolic walk (smm_ccs_* / smm_symbolic_ccs), cached per slab
 // geometry.  (Handed out BY VALUE, like the packed payload: the operand's vector may grow.)
-static int ensure_ccs(smm_ctx *c, smm_csr *b, int ws, int n_slabs, smm_csr::CcsCache *out)
+static int ensure_ccs(smm_ctx *c, smm_csr *b, int ws, int n_slabs, smm_csr::CcsView *out)
 {
     for (auto &e : b->ccs)
-        if (e.ws == ws && e.n_slabs == n_slabs) { *out = e; return SMM_OK; }
+        if (e.ws == ws && e.n_slabs == n_slabs) { *out = e.view(); return SMM_OK; }
     if (ws > CCS_MAX_WS) return fail(SMM_ERR_INVALID, "column slab wider than %d columns", CCS_MAX_WS);
-    Geom gs; gs.nw = 1; gs.nct = n_slabs; gs.wc = ws; gs.wf = ws; gs.n_ft = n_slabs;
     const int *seg = nullptr;
-    CHK(ensure_seg(c, b, gs, &seg));
+    CHK(ensure_seg(c, b, tiles_geom(n_slabs, ws), &seg));
     const int64_t cells = (int64_t)n_slabs * b->rows;
     if (cells + n_slabs + 1 >= INT32_MAX) return fail(SMM_ERR_INVALID, "too many (slab, row) pieces");
     PoolBuf<int> chunks(c);
@@ -1397,10 +1427,8 @@ static int ensure_ccs(smm_ctx *c, smm_csr *b, int ws, int n_slabs, smm_csr::CcsC
     HIPCHK(hipMemcpyAsync(stat, d_stat, sizeof(stat), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));        // chunks / off64 go back to the pool
     chunks.reset(); off64.reset(); d_stat.reset();
-    smm_csr::CcsCache e{ws, n_slabs, bm_words, (int)total, cptr.release(), stream.release(), stat[1] ? (double)stat[0] / (double)stat[1] : 0.0};
-    b->ccs.push_back(e);
-    b->derived_bytes += ptr_entries * (int64_t)sizeof(int) + (total + 1) * CCS_CHUNK * (int64_t)sizeof(unsigned short);
-    *out = e;
+    b->ccs.push_back({ws, n_slabs, bm_words, (int)total, std::move(cptr), std::move(stream), stat[1] ? (double)stat[0] / (double)stat[1] : 0.0});
+    *out = b->ccs.back().view();
     return SMM_OK;
 }
 
@@ -1435,35 +1463,36 @@ static bool slab_geometry(const smm_ctx *c, const smm_csr *b, int64_t ncols, Sla
     return true;
 }
 
-static int ensure_slab(smm_ctx *c, smm_csr *b, const SlabGeom &g, smm_csr::SlabCache *out)
+// The columns and values of e from b's current arrays; queued, not checked.
+static void slab_fill(smm_ctx *c, const smm_csr *b, const smm_csr::SlabCache &e)
+{
+    if (b->rows > 0)
+        LAUNCH(c, "smm_slab_fill", smm_slab_fill, std::min<int64_t>((b->rows + 3) / 4, 65536), 256, 0, (int)b->rows, e.n_slabs, e.ws,
+               b->ptr, b->idx, b->val, e.seg, (const int *)e.soff, e.scol.p, e.sval.p);
+}
+static int ensure_slab(smm_ctx *c, smm_csr *b, const SlabGeom &g, smm_csr::SlabView *out)
 {
     for (auto &e : b->slabs)
-        if (e.ws == g.ws && e.n_slabs == g.n_slabs) { *out = e; return SMM_OK; }
-    Geom gs; gs.nw = 1; gs.nct = g.n_slabs; gs.wc = g.ws; gs.wf = g.ws; gs.n_ft = g.n_slabs;
-    const int *seg = nullptr;
-    CHK(ensure_seg(c, b, gs, &seg));
+        if (e.ws == g.ws && e.n_slabs == g.n_slabs) { *out = e.view(); return SMM_OK; }
+    smm_csr::SlabCache e{g.ws, g.n_slabs, nullptr, {}, {}, {}};
+    CHK(ensure_seg(c, b, tiles_geom(g.n_slabs, g.ws), &e.seg));
     const int64_t cells = (int64_t)g.n_slabs * b->rows;
     PoolBuf<int> cnt(c);
     PoolBuf<int64_t> off64(c);
     CHK(cnt.alloc((size_t)std::max<int64_t>(cells, 1)));
     CHK(off64.alloc((size_t)cells + 1));
-    DevBuf<int> soff; DevBuf<short> scol; DevBuf<double> sval;
-    if (soff.alloc(c, (size_t)(cells + 1)) != hipSuccess || scol.alloc(c, (size_t)std::max<int64_t>(b->nnz, 1)) != hipSuccess ||
-        sval.alloc(c, (size_t)std::max<int64_t>(b->nnz, 1)) != hipSuccess)
+    if (e.soff.alloc(c, (size_t)(cells + 1)) != hipSuccess || e.scol.alloc(c, (size_t)std::max<int64_t>(b->nnz, 1)) != hipSuccess ||
+        e.sval.alloc(c, (size_t)std::max<int64_t>(b->nnz, 1)) != hipSuccess)
         return fail(SMM_ERR_ALLOC, "hipMalloc of the slab-major copy of B failed");
-    if (cells > 0) LAUNCH(c, "smm_slab_count", smm_slab_count, (cells + 255) / 256, 256, 0, (int)b->rows, g.n_slabs, seg, cnt);
+    if (cells > 0) LAUNCH(c, "smm_slab_count", smm_slab_count, (cells + 255) / 256, 256, 0, (int)b->rows, g.n_slabs, e.seg, cnt);
     CHK(scan_launch<int>(c, cells, cnt, off64));
-    LAUNCH(c, "smm_narrow32", smm_narrow32, std::min<int64_t>((cells + 256) / 256, 65536), 256, 0, cells + 1, (const int64_t *)off64, soff);
-    if (b->rows > 0)
-        LAUNCH(c, "smm_slab_fill", smm_slab_fill, std::min<int64_t>((b->rows + 3) / 4, 65536), 256, 0, (int)b->rows, g.n_slabs, g.ws,
-               b->ptr, b->idx, b->val, seg, (const int *)soff, scol, sval);
+    LAUNCH(c, "smm_narrow32", smm_narrow32, std::min<int64_t>((cells + 256) / 256, 65536), 256, 0, cells + 1, (const int64_t *)off64, e.soff.p);
+    slab_fill(c, b, e);
     LAUNCH_CHECK();
     HIPCHK(hipStreamSynchronize(c->stream));        // cnt / off64 go back to the pool
     cnt.reset(); off64.reset();
-    smm_csr::SlabCache e{g.ws, g.n_slabs, soff.release(), scol.release(), sval.release()};
-    b->slabs.push_back(e);
-    b->derived_bytes += (cells + 1) * (int64_t)sizeof(int) + std::max<int64_t>(b->nnz, 1) * (int64_t)(sizeof(short) + sizeof(double));
-    *out = e;
+    *out = e.view();
+    b->slabs.push_back(std::move(e));
     return SMM_OK;
 }
 
@@ -1474,45 +1503,11 @@ static int ensure_slab(smm_ctx *c, smm_csr *b, const SlabGeom &g, smm_csr::SlabC
 // whatever product is still running there.
 static int refresh_value_copies(smm_ctx *c, smm_csr *m)
 {
-    if (m->trv) { smm_csr_destroy(m->trv); m->trv = nullptr; }     // (rebuilt by the next product that needs it)
-    for (auto &e : m->packs) {
-        Geom gs; gs.nw = 1; gs.nct = e.nct; gs.wc = e.wc; gs.wf = e.wc; gs.n_ft = e.nct;
-        const int *seg = nullptr;
-        CHK(ensure_seg(c, m, gs, &seg));
-        if (m->rows > 0 && m->nnz > 0)
-            LAUNCH(c, "smm_pack_fill", smm_pack_fill, std::min<int64_t>((m->rows + 3) / 4, 65536), 256, 0, (int)m->rows, e.nct, e.wc, m->ptr,
-                   m->idx, m->val, seg, (const int2 *)e.desc, e.pay);
-    }
-    for (auto &e : m->slabs) {
-        Geom gs; gs.nw = 1; gs.nct = e.n_slabs; gs.wc = e.ws; gs.wf = e.ws; gs.n_ft = e.n_slabs;
-        const int *seg = nullptr;
-        CHK(ensure_seg(c, m, gs, &seg));
-        if (m->rows > 0 && m->nnz > 0)
-            LAUNCH(c, "smm_slab_fill", smm_slab_fill, std::min<int64_t>((m->rows + 3) / 4, 65536), 256, 0, (int)m->rows, e.n_slabs, e.ws,
-                   m->ptr, m->idx, m->val, seg, (const int *)e.soff, e.scol, e.sval);
-    }
-    if (m->ring_val) {
-        RingBuildArgs B{};
-        B.n = (int)m->rows; B.K = (int)m->cols; B.npieces = m->ring_npieces; B.nkg = (int)((m->rows + 16 * WAVE - 1) / (16 * WAVE));
-        B.h_ptr = m->ptr; B.h_idx = m->idx; B.h_val = m->val; B.off = m->ring_off; B.err = c->d_err;
-        B.col = m->ring_col; B.val = m->ring_val; B.hdr = m->ring_hdr;
-        CHK(ring_fill(c, m, B, m->ring_spread));
-    }
-    if (m->ell_val) {
-        Geom gh; gh.nw = 1; gh.nct = m->ell_nchunks; gh.wf = m->ell_chunk; gh.wc = m->ell_chunk; gh.n_ft = m->ell_nchunks;
-        const int *hseg = nullptr;
-        CHK(ensure_seg(c, m, gh, &hseg));
-        EllArgs E{};
-        E.n = (int)m->rows; E.nchunks = m->ell_nchunks; E.chunk = m->ell_chunk; E.nslices = (int)((m->rows + WAVE - 1) / WAVE);
-        E.h_ptr = m->ptr; E.h_idx = m->idx; E.h_val = m->val; E.hseg = hseg;
-        E.cnt = nullptr; E.off = m->ell_off; E.col = m->ell_col; E.val = m->ell_val;
-        const int64_t items = (int64_t)E.nchunks * E.nslices;
-        const int grid = (int)((items + 3) / 4);
-        if (items > 0) {
-            if (m->ell_spread) LAUNCH(c, "smm_ell_fill", smm_ell_fill<1>, grid, 256, 0, E);
-            else LAUNCH(c, "smm_ell_fill", smm_ell_fill<2>, grid, 256, 0, E);
-        }
-    }
+    m->trv.reset();                                     // (rebuilt by the next product that needs it)
+    for (auto &e : m->packs) pack_fill(c, m, e);
+    for (auto &e : m->slabs) slab_fill(c, m, e);
+    if (m->ring.val) ring_fill(c, m, m->ring);
+    if (m->ell.val) ell_fill(c, m, m->ell);
     LAUNCH_CHECK();
     return SMM_OK;
 }
@@ -1523,7 +1518,7 @@ extern "C" int smm_csr_update_values(smm_ctx *c, smm_csr *m, const double *data)
     if (m->ctx != c) return fail(SMM_ERR_INVALID, "operand belongs to another context");
     CTX_LOCK(c);
     HIPCHK(hipSetDevice(c->device));
-    if (!m->owned) return fail(SMM_ERR_INVALID, "smm_csr_update_values: the operand borrows its arrays (smm_csr_from_device); "
+    if (!m->owned()) return fail(SMM_ERR_INVALID, "smm_csr_update_values: the operand borrows its arrays (smm_csr_from_device); "
                                                 "rewrite them and call smm_csr_update_values_device");
     if (m->nnz == 0) return SMM_OK;
     if (!data) return fail(SMM_ERR_INVALID, "data is NULL");
@@ -1540,7 +1535,7 @@ extern "C" int smm_csr_update_values_device(smm_ctx *c, smm_csr *m, const double
     HIPCHK(hipSetDevice(c->device));
     if (m->nnz == 0) return SMM_OK;
     if (d_data && d_data != m->val) {
-        if (!m->owned) return fail(SMM_ERR_INVALID, "smm_csr_update_values_device: a borrowed operand is updated by rewriting its "
+        if (!m->owned()) return fail(SMM_ERR_INVALID, "smm_csr_update_values_device: a borrowed operand is updated by rewriting its "
                                                     "own array (pass NULL or that array)");
         HIPCHK(hipMemcpyAsync((void *)m->val, d_data, (size_t)m->nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     }
@@ -1549,7 +1544,7 @@ extern "C" int smm_csr_update_values_device(smm_ctx *c, smm_csr *m, const double
 
 // rows (a row list, or rows 0..m-1 of A) x all slabs -> `out`, rows of the launch ldo apart, column order
 template <bool NEGZERO>
-static int launch_slab(smm_ctx *c, const smm_csr *a, const smm_csr *b, const smm_csr::SlabCache &sl, int rw, int m,
+static int launch_slab(smm_ctx *c, const smm_csr *a, const smm_csr *b, const smm_csr::SlabView &sl, int rw, int m,
                        const int *rowlist, bool sym, int64_t row_offset, double *out, int64_t ldo)
 {
     if (m <= 0) return SMM_OK;
@@ -1641,7 +1636,7 @@ static int launch_symbolic_w(smm_ctx *c, smm_plan *p, int words, unsigned *gbm, 
         HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     LAUNCH(c, MARK == MARK_LDS_HASH ? "smm_symbolic_hash" : "smm_symbolic", kern, grid, wpb * 64, lds, (int)p->m, rowlist,
            d_nrows, p->row_offset, words, p->a->ptr, p->a->idx, p->b->ptr,
-           I16 ? (const void *)p->b->idx16 : (const void *)b_idx32, p->d_ub_off, p->d_tmp, p->d_P,
+           I16 ? (const void *)p->b->idx16.p : (const void *)b_idx32, p->d_ub_off, p->d_tmp, p->d_P,
            p->d_rowcnt, gbm, d_row_counter, rbatch);
     LAUNCH_CHECK();
     return SMM_OK;
@@ -1756,7 +1751,7 @@ static int most_waves_per_cu(size_t wave_bytes, int *per_wg)
 }
 
 // smm_symbolic_ccs over `units` (slab, row) units, or over the listed rows (n_slabs = 1), of the chunked column stream cc
-static int launch_ccs(smm_ctx *c, const smm_plan *p, const smm_csr::CcsCache &cc, int64_t units, int n_slabs, const int *rowlist,
+static int launch_ccs(smm_ctx *c, const smm_plan *p, const smm_csr::CcsView &cc, int64_t units, int n_slabs, const int *rowlist,
                       const int *nrows, int *cnt, int *counter)
 {
     const size_t wave_bytes = (size_t)(cc.bm_words + WAVE) * sizeof(unsigned);
@@ -1862,11 +1857,10 @@ static int sym_slab_walk(smm_ctx *c, smm_plan *p, SymRows &r)
     p->tps = tps; p->ws = tps * p->g.wc; p->n_slabs = (p->g.nct + tps - 1) / tps;
     p->list16 = true;
     const int ns = p->n_slabs;
-    smm_csr::CcsCache cc{};
+    smm_csr::CcsView cc{};
     CHK(ensure_ccs(c, b, p->ws, ns, &cc));
-    Geom gs; gs.nw = 1; gs.nct = ns; gs.wc = p->ws; gs.wf = p->ws; gs.n_ft = ns;
     const int *sseg = nullptr;
-    CHK(ensure_seg(c, b, gs, &sseg));
+    CHK(ensure_seg(c, b, tiles_geom(ns, p->ws), &sseg));
     // capacities and offsets of the (slab, row) lists
     PoolBuf<int64_t> ubs(c);
     CHK(ubs.alloc((size_t)ns * m));
@@ -1978,7 +1972,7 @@ static int sym_row_walk(smm_ctx *c, smm_plan *p, SymRows &r)
     // Round 3: sorted B without repeated columns and 16-bit lists -> the walk over the chunk-padded stream
     const bool use_ccs = c->sym_ccs && p->list16 && !safe && p->ncols <= CCS_MAX_WS && nbm > 0;
     if (use_ccs) {
-        smm_csr::CcsCache cc{};
+        smm_csr::CcsView cc{};
         CHK(ensure_ccs(c, b, (int)p->ncols, 1, &cc));
         CHK(launch_ccs(c, p, cc, nbm, 1, bm_rows, bm_count, p->d_rowcnt, d_rowctr + SB_REST));
     } else if (nbm > 0) {
@@ -2244,14 +2238,14 @@ static int dense_into(smm_ctx *c, smm_csr *a, smm_csr *b, int flags, int64_t row
     if (slab_geometry(c, b, n, &sg) &&
         slab_pays(c, a, sg, (double)m * (double)n, (double)a->nnz * ((double)b->nnz / (double)std::max<int64_t>(b->rows, 1)), -1.0,
                   (double)b->nnz / (double)std::max<int64_t>(b->rows, 1), (double)n)) {
-        smm_csr::SlabCache sl{0, 0, nullptr, nullptr, nullptr};
+        smm_csr::SlabView sl{0, 0, nullptr, nullptr, nullptr};
         CHK(ensure_slab(c, b, sg, &sl));
         return launch_slab<false>(c, a, b, sl, sg.rw, (int)m, nullptr, sym, row_offset, d_c, ldc);
     }
     if (!(b->vflags & CSR_UNSORTED)) {
         Geom g = make_geom(c, n, b, (flags & SMM_EXACT) != 0);
         const int *seg = nullptr; const short *loc = nullptr;
-        smm_csr::PackCache pack{0, 0, nullptr, nullptr, 0};
+        smm_csr::PackView pack{0, 0, nullptr, nullptr, 0};
         if (flags & SMM_EXACT) {
             CHK(ensure_seg(c, b, g, &seg));
             CHK(ensure_loc(c, b, g, &loc));
@@ -2474,10 +2468,10 @@ extern "C" int smm_triple_product(smm_ctx *c, smm_csr *h, smm_csr *q, int flags,
         const bool exact_r = (flags & SMM_EXACT) != 0;
         CHK(ensure_ring(c, h, !exact_r));
         RingArgs A{};
-        A.n = (int)n; A.K = (int)K; A.npieces = h->ring_npieces; A.nslices = (int)((n + WAVE - 1) / WAVE);
+        A.n = (int)n; A.K = (int)K; A.npieces = h->ring.npieces; A.nslices = (int)((n + WAVE - 1) / WAVE);
         A.nib = (int)((nr + R - 1) / R);
         A.row_begin = row_begin; A.row_end = row_end; A.full = full ? 1 : 0;
-        A.off = h->ring_off; A.col = h->ring_col; A.val = h->ring_val; A.hdr = h->ring_hdr;
+        A.off = h->ring.off; A.col = h->ring.col; A.val = h->ring.val; A.hdr = h->ring.hdr;
         A.T = T; A.C = d_c; A.ldc = n; A.err = c->d_err;
         const int64_t nkg = (n + 16 * WAVE - 1) / (16 * WAVE);
         A.nkg = (int)nkg;
@@ -2514,7 +2508,7 @@ extern "C" int smm_triple_product(smm_ctx *c, smm_csr *h, smm_csr *q, int flags,
     A.n = (int)n; A.K = (int)K; A.nchunks = nchunks; A.chunk = chunk; A.nslices = (int)((n + WAVE - 1) / WAVE);
     A.nib = (int)((nr + R - 1) / R);
     A.row_begin = row_begin; A.row_end = row_end; A.full = full ? 1 : 0;
-    A.off = h->ell_off; A.col = h->ell_col; A.val = h->ell_val;
+    A.off = h->ell.off; A.col = h->ell.col; A.val = h->ell.val;
     A.T = T; A.C = d_c; A.ldc = n;
     const size_t lds = (size_t)(R + 2) * chunk * sizeof(double);
     const int64_t nkg = (n + NW * WAVE - 1) / (NW * WAVE);
@@ -2577,14 +2571,11 @@ static int seg_sort(smm_ctx *c, int64_t nseg, const int64_t *off, int *key)
 }
 
 // A^T as a new owned operand; arrays exactly those of scipy's a.tocsc().
-static int transpose_impl(smm_ctx *c, const smm_csr *a, smm_csr **out)
+static int transpose_impl(smm_ctx *c, const smm_csr *a, CsrPtr *out)
 {
-    *out = nullptr;
-    const int64_t rows = a->cols, cols = a->rows, nnz = a->nnz;
-    DevBuf<int> dp, di; DevBuf<double> dv;
-    if (dp.alloc(c, rows + 1) != hipSuccess || di.alloc(c, std::max<int64_t>(nnz, 1) + 2) != hipSuccess ||     // (slack as smm_csr_from_host)
-        dv.alloc(c, std::max<int64_t>(nnz, 1)) != hipSuccess)
-        return fail(SMM_ERR_ALLOC, "hipMalloc of the transposed operand failed");
+    const int64_t rows = a->cols, nnz = a->nnz;
+    CsrPtr m = new_csr(c, rows, a->rows, nnz);
+    CHK(alloc_owned(c, m.get(), "the transposed operand"));
     {
         PoolBuf<int> cnt(c), key(c);
         PoolBuf<int64_t> off(c);
@@ -2600,16 +2591,12 @@ static int transpose_impl(smm_ctx *c, const smm_csr *a, smm_csr **out)
         CHK(seg_sort(c, rows, off, key));
         const int ggrid = (int)std::min<int64_t>(std::max<int64_t>(std::max(nnz, rows + 1) / 256 + 1, 1), (int64_t)c->n_cu * 16);
         LAUNCH(c, "smm_transpose_gather", smm_transpose_gather, ggrid, 256, 0, nnz, (int)a->rows, a->ptr, a->val, (const int *)key, (int)rows,
-               (const int64_t *)off, dp, di, dv);
+               (const int64_t *)off, m->own_ptr.p, m->own_idx.p, m->own_val.p);
         LAUNCH_CHECK();
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    smm_csr *m = new smm_csr();
-    m->ctx = c; m->rows = rows; m->cols = cols; m->nnz = nnz;
-    m->ptr = dp.release(); m->idx = di.release(); m->val = dv.release(); m->owned = true;
-    const int rc = validate(c, m);          // (flags of the new operand: sorted rows, repeated columns where A repeats rows)
-    if (rc != SMM_OK) { smm_csr_destroy(m); return rc; }
-    *out = m;
+    CHK(validate(c, m.get()));              // (flags of the new operand: sorted rows, repeated columns where A repeats rows)
+    *out = std::move(m);
     return SMM_OK;
 }
 
@@ -2622,7 +2609,10 @@ extern "C" int smm_csr_transpose(smm_ctx *c, const smm_csr *a, smm_csr **out)
     CTX_LOCK(c);
     HIPCHK(hipSetDevice(c->device));
     CHK(validate(c, (smm_csr *)a));
-    return transpose_impl(c, a, out);
+    CsrPtr t;
+    CHK(transpose_impl(c, a, &t));
+    *out = t.release();
+    return SMM_OK;
 }
 
 extern "C" int smm_csr_download(smm_ctx *c, const smm_csr *m, int32_t *indptr, int32_t *indices, double *data)
@@ -2769,7 +2759,7 @@ static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, 
     const bool exact = (flags & SMM_EXACT) != 0;
     smm_csr hv = csr_row_view(h, b0, nb);
     PlanPtr p1, p2;
-    std::unique_ptr<smm_csr, Destroyer<smm_csr_destroy>> tb;
+    CsrPtr tb;
     int64_t tnnz = 0, snnz = 0;
     PoolBuf<int64_t> tptr(c), sptr(c);
     PoolBuf<int> tidx(c), tptr32(c), mcnt(c), sidx(c);
@@ -2889,7 +2879,7 @@ static int triple_sparse_impl(smm_ctx *c, smm_csr *h, smm_csr *q, const smm_csr 
         int64_t b1 = b0, acc = 0;
         while (b1 < row_end && (b1 == b0 || acc + prod[(size_t)(b1 - row_begin)] <= c->t3_max_t)) acc += prod[(size_t)(b1++ - row_begin)];
         smm_result::Piece pc{0, 0, nullptr, nullptr, nullptr};
-        CHK(triple_sparse_block(c, h, q, h->tr, mask, flags, b0, b1, &pc));
+        CHK(triple_sparse_block(c, h, q, h->tr.get(), mask, flags, b0, b1, &pc));
         r->pieces.push_back(pc);
         r->nnz += pc.nnz;
         b0 = b1;
@@ -3086,7 +3076,7 @@ extern "C" int smm_ctx_tune_spmm(smm_ctx *c, int mode, int64_t apply_budget_byte
 static int spmm_op(smm_ctx *c, smm_csr *a, bool transpose, const smm_csr **out)
 {
     if (transpose && !a->trv) CHK(transpose_impl(c, a, &a->trv));
-    *out = transpose ? a->trv : a;
+    *out = transpose ? a->trv.get() : a;
     return SMM_OK;
 }
 

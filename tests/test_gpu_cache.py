@@ -137,6 +137,153 @@ def test_values_update_through_the_c_abi_refreshes_every_cached_copy(ctx, oracle
             h.close(); q.close()
 
 
+class _CopySequence:
+    """Fresh handles of A (150 x 180), B (180 x 600, sorted rows), H = A (two handles) and a symmetric Q (180 x 180), and
+    the five products that build every cached copy carrying values, one kind per step: the packed payload of B
+    (default walk, dense LDS tiles for every row), B's tile index and tile-local columns (exact walk), the slab-major
+    copy of B (slab kernels forced), the sliced-ELL copy of H (chunk kernel of stage 2) and the ring streams of the
+    second handle of H (ring kernel).  The triple products run under SMM_EXACT, so that stage 1 keeps no packed payload
+    on Q and the copies of H are the ones an exact product after update_values reads."""
+    STEPS = ("pack", "seg+loc", "slab", "ell", "ring")
+
+    def __init__(self, ctx, A, B, Q):
+        self.ctx = ctx
+        self.a, self.b, self.h, self.q, self.h2 = (ctx.csr_from_scipy(X) for X in (A, B, A, Q, A))
+        self.target = dict(zip(self.STEPS, (self.b, self.b, self.b, self.h, self.h2)))
+
+    def run(self, step):
+        ctx = self.ctx
+        if step == "pack":
+            ctx.tune_hash(0, 0)
+            return ctx.spgemm_host(self.a, self.b)
+        if step == "seg+loc":
+            ctx.tune_hash(0, 0)
+            return ctx.spgemm_host(self.a, self.b, exact=True)
+        if step == "slab":
+            ctx.tune_slab(2, 0, 0)
+            try:
+                return ctx.dense_host(self.a, self.b, exact=True)
+            finally:
+                ctx.tune_slab(0, 0, 0)
+        ctx.tune_stage2(step == "ring")
+        try:
+            return ctx.triple_host(self.h if step == "ell" else self.h2, self.q, exact=True)
+        finally:
+            ctx.tune_stage2(False)
+
+    def bytes(self):
+        return (self.b.device_bytes(), self.h.device_bytes(), self.h2.device_bytes())
+
+    def close(self):
+        for x in (self.a, self.b, self.h, self.q, self.h2):
+            x.close()
+        self.ctx.tune_hash(256, 2048); self.ctx.tune_slab(0, 0, 0); self.ctx.tune_stage2(False)
+
+
+def _copy_sequence_inputs():
+    A, B = rand_csr(150, 180, 0.05, 91), rand_csr(180, 600, 0.05, 92)
+    S = rand_csr(180, 180, 0.015, 93)
+    return A, B, (S + S.T).tocsr()
+
+
+def test_update_values_refills_exactly_the_copies_that_were_built(ctx):
+    """update_values launches one fill per cached copy that carries values -- as many smm_pack_fill / smm_slab_fill /
+    smm_ell_fill as the builds launched smm_pack_count / smm_slab_count / smm_ell_count, and the fill pass of
+    smm_ring_build (a build is a count pass and a fill pass) -- and no kernel of the index side.  Every product on the
+    updated handles is then bit for bit the product on a fresh handle made from the new values."""
+    A, B, Q = _copy_sequence_inputs()
+    seq = _CopySequence(ctx, A, B, Q)
+    fresh = None
+    try:
+        ctx.timing(True); ctx.timing_reset()
+        for step in seq.STEPS:
+            seq.run(step)
+        built = {k: ctx.kernel_time(k)[1] for k in ("smm_pack_count", "smm_slab_count", "smm_ell_count", "smm_ring_build")}
+        print("launches of the builds:", built)
+        assert built["smm_pack_count"] >= 1 and built["smm_slab_count"] >= 1 and built["smm_ell_count"] >= 1
+        assert built["smm_ring_build"] >= 2 and built["smm_ring_build"] % 2 == 0
+        ctx.timing_reset()
+        A2, B2 = signed(A, 94), signed(B, 95)
+        seq.b.update_values(B2.data); seq.h.update_values(A2.data); seq.h2.update_values(A2.data)
+        after = {k: ctx.kernel_time(k)[1] for k in ("smm_pack_fill", "smm_slab_fill", "smm_ell_fill", "smm_ring_build", "smm_segptr",
+                                                    "smm_validate", "smm_scan", "smm_pack_count", "smm_pack_desc", "smm_slab_count",
+                                                    "smm_ell_count", "smm_ccs_fill", "smm_idx16", "smm_loc16")}
+        print("launches of the update:", after)
+        assert after["smm_pack_fill"] == built["smm_pack_count"]
+        assert after["smm_slab_fill"] == built["smm_slab_count"]
+        assert after["smm_ell_fill"] == built["smm_ell_count"]
+        assert after["smm_ring_build"] == built["smm_ring_build"] // 2
+        for k in ("smm_segptr", "smm_validate", "smm_scan", "smm_pack_count", "smm_pack_desc", "smm_slab_count", "smm_ell_count",
+                  "smm_ccs_fill", "smm_idx16", "smm_loc16"):
+            assert after[k] == 0, f"{k} ran during update_values"
+        ctx.timing(False)
+        seq.a.update_values(A2.data)                       # (A as the left operand: no cached copy is read)
+        fresh = _CopySequence(ctx, A2, B2, Q)
+        for step in ("seg+loc", "slab", "ell", "ring"):    # the exact sparse product, the slab-forced dense one, both triples
+            got, want = seq.run(step), fresh.run(step)
+            if step == "seg+loc":
+                assert_csr_equal(got, want, values="bits")
+            else:
+                assert np.array_equal(got.view(np.int64), want.view(np.int64)), f"{step}: the updated handle differs from a fresh one"
+        # the packed payload is read by the default walk only, which sums in no fixed order: within the default mode's bound
+        assert_csr_equal(seq.run("pack"), fresh.run("pack"), values="tol")
+    finally:
+        ctx.timing(False)
+        seq.close()
+        if fresh is not None:
+            fresh.close()
+
+
+def test_device_bytes_follow_what_the_handle_owns(ctx):
+    """smm_csr_device_bytes: the three arrays of an owned operand (idx with two ints of slack), plus every cached copy
+    as it is built, plus the transposes; nothing for a repeated product or a value update, and a value update gives
+    back exactly the valued transpose it drops."""
+    import torch
+    A, B, Q = _copy_sequence_inputs()
+    seqs = [_CopySequence(ctx, A, B, Q) for _ in range(2)]
+    borrowed = None
+    try:
+        own = 4 * (B.shape[0] + 1) + 4 * (max(B.nnz, 1) + 2) + 8 * max(B.nnz, 1)
+        logs = []
+        for seq in seqs:
+            assert seq.b.device_bytes() == own
+            log = [seq.bytes()]
+            for step in seq.STEPS:
+                seq.run(step)
+                log.append(seq.bytes())
+                i = (seq.b, seq.h, seq.h2).index(seq.target[step])
+                assert log[-1][i] > log[-2][i], f"{step}: the copy it builds is not counted"
+                seq.run(step)
+                assert seq.bytes() == log[-1], f"{step}: a repeated product changed the byte count"
+            logs.append(log)
+        print("device_bytes of (B, H, H') at the start and after each step:", logs[0])
+        assert logs[0] == logs[1], "two handles taken through the same products report different bytes"
+        seq = seqs[0]
+        before = seq.bytes()
+        A2, B2 = signed(A, 96), signed(B, 97)
+        seq.b.update_values(B2.data); seq.h.update_values(A2.data); seq.h2.update_values(A2.data)
+        assert seq.bytes() == before, "update_values changed the byte count of a handle without a valued transpose"
+        ctx.spmm_host(seq.b, np.ones((B.shape[0], 3)), transpose=True)          # what sparse_dense_multiply(transpose=True) calls
+        added = seq.b.device_bytes() - before[0]
+        assert added > 0
+        seq.b.update_values(B.data)
+        assert seq.b.device_bytes() == before[0], "update_values did not give back exactly the valued transpose"
+        # a borrowed operand: the same derived copies as the owned one after the default product, and no term of its own
+        dev = torch.device("cuda", ctx.device)
+        tb = [torch.from_numpy(x).to(dev) for x in arrays(B)]
+        torch.cuda.synchronize()
+        borrowed = ctx.csr_from_torch(B.shape[0], B.shape[1], *tb)
+        assert borrowed.device_bytes() == 0
+        ctx.tune_hash(0, 0)
+        ctx.spgemm_host(seq.a, borrowed)
+        assert borrowed.device_bytes() == logs[0][1][0] - own
+    finally:
+        if borrowed is not None:
+            borrowed.close()
+        for seq in seqs:
+            seq.close()
+
+
 def test_borrowed_operand_values_rewritten_in_place(ctx, oracle):
     import torch
     A, B = rand_csr(200, 300, 0.05, 41), rand_csr(300, 400, 0.05, 42)
