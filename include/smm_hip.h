@@ -182,6 +182,9 @@ int  smm_csr_update_values_device(smm_ctx *ctx, smm_csr *m, const double *d_data
 int  smm_csr_transpose(smm_ctx *ctx, const smm_csr *a, smm_csr **out);
 /* Host copy of an operand's own arrays: indptr (rows+1 int32), indices (nnz int32), data (nnz float64). */
 int  smm_csr_download(smm_ctx *ctx, const smm_csr *m, int32_t *indptr, int32_t *indices, double *data);
+/* The same three arrays copied into caller-owned DEVICE buffers of those sizes (a NULL destination is skipped): the
+ * pattern of a library-owned operand for a caller that keeps its results in HBM.  Synchronises the context's stream. */
+int  smm_csr_copy_device(smm_ctx *ctx, const smm_csr *m, int32_t *d_indptr, int32_t *d_indices, double *d_data);
 /* HBM held by the handle: its arrays (when owned) plus every cached copy. */
 int64_t smm_csr_device_bytes(const smm_csr *m);
 /* 64-bit content hash of a HOST buffer (no GPU involved): a chain of bijective mixing steps, so changing any
@@ -382,6 +385,42 @@ int  smm_sddmm_host(smm_ctx *ctx, smm_csr *mask, int flags, int64_t k, const dou
  * neighbouring entries, 2 = every lane group walks a run of consecutive entries and keeps X[i,:] in registers (tests).
  * Results never depend on it, bit for bit, in either mode. */
 int  smm_ctx_tune_sddmm(smm_ctx *ctx, int mode);
+
+/* ------------------------------------------------------------------ localisation taper from point coordinates
+ * L[i,j] = w(|a_i - b_j|) for every pair of points closer than `cutoff`, as a new operand (na x nb) owned by the caller
+ * (smm_csr_destroy), as smm_csr_transpose returns one -- the mask / weight matrix L of smm_triple_product_sparse_masked,
+ * smm_spgemm_masked and smm_sddmm, built where it is used instead of on the host.  a: na x dim, b: nb x dim, both
+ * row-major float64 with leading dimensions lda, ldb >= dim; dim is 1, 2 or 3; 64-bit offsets.  d_b may be d_a's own
+ * buffer: the square, symmetric case.  Distances are Euclidean: for points on a sphere pass unit-sphere xyz and a chord
+ * cutoff.  No periodic domains.
+ *   Distance    d2 = +0.0; for t = 0 .. dim-1: df = a[i,t] - b[j,t]; d2 = d2 + df * df, every product rounded before its
+ *               add.  The sign of df cannot matter, so the square case is symmetric bit for bit.
+ *   Membership  (i, j) is stored iff d2 < cutoff * cutoff: a strict comparison against a right-hand side rounded once.
+ *               Nothing else decides the pattern; the cell search that finds the candidates never loses a pair that
+ *               passes this test (csrc/smm_taper.hpp has the argument).  Columns are strictly ascending in every row, so
+ *               smm_csr_is_canonical holds; pairs at distance 0 (and i == j of the square case) are stored.
+ *   Value       SMM_TAPER_BOXCAR: 1.0.
+ *               SMM_TAPER_GASPARI_COHN: Gaspari & Cohn (1999), eq. 4.10, with half-width c = 0.5 * cutoff and
+ *               z = sqrt(d2) / c (IEEE square root and division), every multiply rounded before its add:
+ *                 z <= 1:    p = -0.25 * z + 0.5;  p = p * z + 0.625;  p = p * z - (5.0 / 3.0);  p = p * z;  p = p * z + 1.0
+ *                 otherwise: p = (1.0 / 12.0) * z - 0.5;  p = p * z + 0.625;  p = p * z + (5.0 / 3.0);  p = p * z - 5.0;
+ *                            p = p * z + 4.0;  p = p - 2.0 / (3.0 * z)
+ *                 w = p < 0.0 ? +0.0 : p          (this order gives down to -1.6e-15 just inside z = 2; exactly 1.0 at z = 0)
+ *   One mode: there is no SMM_EXACT flag and no other order -- a dozen flops per 12-byte entry.  Pattern and values are
+ *   bit-identical to that recipe carried out in IEEE double, and two calls give the same bits.  No float atomics.
+ * The candidates come from a uniform grid over b's bounding box with cell edge cutoff * (1 + 2^-20), grown by factors of
+ * 1.25 while the box would hold more than max(4096, 2 nb) cells (at most 2^30); a point x has cell coordinate
+ * trunc((x - lo) * (1 / edge)), clamped to the grid, in every dimension.
+ * SMM_ERR_INVALID, before any launch that depends on the value: dim outside 1..3, unknown kind, cutoff not finite or
+ * <= 0, lda or ldb < dim, a NULL buffer with rows > 0, na or nb < 0 or >= 2^31 - 1 (an operand's dimension); also a
+ * coordinate that is NaN or +-inf (counted in the pass that takes the bounding box).  More than 2^31 - 2 entries:
+ * SMM_ERR_OVERFLOW (operand row pointers are int32).  na == 0 or nb == 0: an operand without entries, no launch. */
+enum smm_taper_kind { SMM_TAPER_BOXCAR = 0, SMM_TAPER_GASPARI_COHN = 1 };
+int  smm_taper_build(smm_ctx *ctx, int dim, int kind, double cutoff, int64_t na, const double *d_a, int64_t lda,
+                     int64_t nb, const double *d_b, int64_t ldb, smm_csr **out);
+/* Same with a and b in host memory (uploaded through pool temporaries; b == a with ldb == lda and nb == na once). */
+int  smm_taper_build_host(smm_ctx *ctx, int dim, int kind, double cutoff, int64_t na, const double *a, int64_t lda,
+                          int64_t nb, const double *b, int64_t ldb, smm_csr **out);
 
 /* ------------------------------------------------------------------ conjugate gradients on (H Q H^T + R) Z = D
  * S = H Q H^T is never formed (H: n x K, Q: K x K, R: n x n sparse or NULL for S alone; the system is expected to be

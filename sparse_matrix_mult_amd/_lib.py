@@ -22,7 +22,11 @@ SMM_EXACT = 4
 SMM_MIRROR = 8
 SMM_TRANSPOSE = 16
 SMM_SCALE_BY_MASK = 32
+SMM_TAPER_BOXCAR = 0
+SMM_TAPER_GASPARI_COHN = 1
+SMM_ERR_INVALID = -2
 SMM_ERR_ALLOC = -3
+SMM_ERR_OVERFLOW = -5
 SMM_ERR_UNSUPPORTED = -6
 SMM_ERR_INTERNAL = -7
 
@@ -86,6 +90,7 @@ V2_PROTOTYPES = {
     "smm_triple_product_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _c_i64, _vp]),
     "smm_csr_transpose": (ctypes.c_int, [_vp, _vp, _pp]),
     "smm_csr_download": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "smm_csr_copy_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "smm_triple_product_sparse": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _c_i64, _pp]),
     "smm_result_nnz": (_c_i64, [_vp]),
     "smm_result_rows": (_c_i64, [_vp]),
@@ -105,6 +110,9 @@ V2_PROTOTYPES = {
     "smm_sddmm": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp]),
     "smm_sddmm_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp]),
     "smm_ctx_tune_sddmm": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "smm_taper_build": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64, _pp]),
+    "smm_taper_build_host": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64,
+                                            _pp]),
     "smm_innovation_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_double,
                                             _c_i64, _vp, _vp, _vp, _vp]),
     "smm_innovation_solve_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_double,

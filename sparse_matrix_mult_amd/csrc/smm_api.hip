@@ -10,6 +10,7 @@
 #include "smm_spmm.hpp"
 #include "smm_cg.hpp"
 #include "smm_sddmm.hpp"
+#include "smm_taper.hpp"
 #include "../../include/smm_hip.h"
 
 #include <sys/mman.h>
@@ -2626,6 +2627,229 @@ extern "C" int smm_csr_download(smm_ctx *c, const smm_csr *m, int32_t *indptr, i
     CHK(download(c, indices, m->idx, (size_t)m->nnz * sizeof(int)));
     CHK(download(c, data, m->val, (size_t)m->nnz * sizeof(double)));
     return SMM_OK;
+}
+
+// Device-to-device copy of an operand's own arrays (NULL skips one): how a caller that keeps results in HBM gets the
+// pattern of a library-owned operand without the host.
+extern "C" int smm_csr_copy_device(smm_ctx *c, const smm_csr *m, int32_t *d_indptr, int32_t *d_indices, double *d_data)
+{
+    if (!c || !m) return fail(SMM_ERR_INVALID, "NULL argument");
+    if (m->ctx != c) return fail(SMM_ERR_INVALID, "operand belongs to another context");
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    if (d_indptr) HIPCHK(hipMemcpyAsync(d_indptr, m->ptr, ((size_t)m->rows + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+    if (d_indices && m->nnz > 0) HIPCHK(hipMemcpyAsync(d_indices, m->idx, (size_t)m->nnz * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+    if (d_data && m->nnz > 0) HIPCHK(hipMemcpyAsync(d_data, m->val, (size_t)m->nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SMM_OK;
+}
+
+// ------------------------------------------------------------------------------ localisation taper from coordinates
+// (kernels and the cell-search argument: smm_taper.hpp; contract: include/smm_hip.h)
+static int upload_rows(smm_ctx *c, double *d, const double *h, int64_t rows, int64_t k, int64_t ld);
+
+// Most cells the grid over b may have: two per point (more cells than points only add empty ones; 12 bytes each),
+// at least 4096, at most 2^30 (cell ids are int).
+static double taper_cell_cap(int64_t nb)
+{
+    return (double)std::min<int64_t>(std::max<int64_t>(2 * nb, 4096), (int64_t)1 << 30);
+}
+
+// The grid over b's bounding box: edge = cutoff * (1 + 2^-20), grown by steps of 1.25 until the cells fit the cap.
+// A dimension whose extent is not finite (coordinates near +-DBL_MAX) gets one cell.  Correctness of the search does
+// not depend on anything chosen here (smm_taper.hpp): only the number of candidates does.
+static TaperGrid taper_grid(int dim, double cutoff, const double *lo, const double *hi, int64_t nb)
+{
+    TaperGrid g{};
+    g.cutoff = cutoff; g.cut2 = cutoff * cutoff; g.half = 0.5 * cutoff;
+    double ext[3] = {0.0, 0.0, 0.0};
+    for (int t = 0; t < 3; ++t) {
+        g.nc[t] = 1;
+        g.lo[t] = t < dim ? lo[t] : 0.0;
+        g.hi[t] = t < dim ? hi[t] : 0.0;
+        if (t < dim && std::isfinite(hi[t] - lo[t]) && hi[t] > lo[t]) ext[t] = hi[t] - lo[t];
+    }
+    const double cap = taper_cell_cap(nb);
+    double h = cutoff * (1.0 + 0x1p-20);
+    if (!(h >= cutoff) || !std::isfinite(h)) h = cutoff;
+    for (;;) {
+        const double inv = 1.0 / h;
+        double n[3], total = 1.0;
+        for (int t = 0; t < 3; ++t) { n[t] = std::floor(ext[t] * inv) + 1.0; total *= n[t]; }
+        if (total <= cap || !std::isfinite(h * 1.25)) {
+            if (total <= cap && inv > 0.0) { for (int t = 0; t < 3; ++t) g.nc[t] = (int)n[t]; g.inv_h = inv; }
+            else g.inv_h = 0.0;                                     // (one cell: every nc stays 1)
+            return g;
+        }
+        h *= 1.25;
+    }
+}
+
+// Cell-order permutation of n points (order; with `sorted` also their coordinates in that order) and, with `start`, the
+// first sorted position of every cell.  cell_of / cnt / scratch64: caller's temporaries (n, ncells + 1, ncells + 1).
+template <int DIM>
+static int taper_bin(smm_ctx *c, const TaperGrid &g, int ncells, int64_t n, const double *pts, int64_t ld, int *cell_of, int *cnt,
+                     int64_t *start, int *order, double *sorted)
+{
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)c->n_cu * 16);
+    HIPCHK(hipMemsetAsync(cnt, 0, ((size_t)ncells + 1) * sizeof(int), c->stream));
+    LAUNCH(c, "smm_taper_bin", smm_taper_cell_count<DIM>, grid, 256, 0, g, n, pts, ld, ncells, cell_of, cnt);
+    CHK(scan_launch<int>(c, ncells, cnt, start));
+    HIPCHK(hipMemsetAsync(cnt, 0, ((size_t)ncells + 1) * sizeof(int), c->stream));           // (cursor of the scatter)
+    LAUNCH(c, "smm_taper_bin", smm_taper_cell_scatter<DIM>, grid, 256, 0, n, pts, ld, ncells, (const int *)cell_of, (const int64_t *)start, cnt,
+           order, sorted, c->d_err);
+    LAUNCH_CHECK();
+    return SMM_OK;
+}
+
+// Bounding box (box[0..2] min, box[3..5] max) and the number of non-finite coordinates of n > 0 points.
+template <int DIM>
+static int taper_bbox(smm_ctx *c, int64_t n, const double *pts, int64_t ld, double *box, double *bad)
+{
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)c->n_cu * 4);
+    PoolBuf<double> part(c);
+    CHK(part.alloc((size_t)grid * TP_PART));
+    LAUNCH(c, "smm_taper_bbox", smm_taper_bbox<DIM>, grid, 256, 0, n, pts, ld, part.p);
+    LAUNCH_CHECK();
+    std::vector<double> h((size_t)grid * TP_PART);
+    HIPCHK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int t = 0; t < 3; ++t) { box[t] = DBL_MAX; box[3 + t] = -DBL_MAX; }
+    *bad = 0.0;
+    for (int b = 0; b < grid; ++b) {
+        const double *p = h.data() + (size_t)b * TP_PART;
+        for (int t = 0; t < 3; ++t) { box[t] = std::min(box[t], p[t]); box[3 + t] = std::max(box[3 + t], p[3 + t]); }
+        *bad += p[6];
+    }
+    return SMM_OK;
+}
+
+// An operand of rows x cols without entries: no launch (its flags are those smm_validate would find).
+static int empty_csr(smm_ctx *c, int64_t rows, int64_t cols, CsrPtr *out)
+{
+    CsrPtr m = new_csr(c, rows, cols, 0);
+    CHK(alloc_owned(c, m.get(), "an empty operand"));
+    HIPCHK(hipMemsetAsync(m->own_ptr, 0, ((size_t)rows + 1) * sizeof(int), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    m->validated = true;
+    m->vflags = 0;
+    *out = std::move(m);
+    return SMM_OK;
+}
+
+template <int DIM>
+static int taper_impl(smm_ctx *c, int kind, double cutoff, int64_t na, const double *a, int64_t lda, int64_t nb, const double *b,
+                      int64_t ldb, CsrPtr *out)
+{
+    const bool same = a == b && lda == ldb && na == nb;
+    double box[6], bad = 0.0, abox[6], abad = 0.0;
+    CHK(taper_bbox<DIM>(c, nb, b, ldb, box, &bad));
+    if (!same) CHK(taper_bbox<DIM>(c, na, a, lda, abox, &abad));
+    if (bad + abad > 0.0)
+        return fail(SMM_ERR_INVALID, "smm_taper_build: %.0f coordinates are not finite (NaN or inf)", bad + abad);
+    const TaperGrid g = taper_grid(DIM, cutoff, box, box + 3, nb);
+    const int ncells = g.nc[0] * g.nc[1] * g.nc[2];
+
+    PoolBuf<int> cell_of(c), cnt(c), order_b(c), order_a(c), rowcnt(c);
+    PoolBuf<int64_t> start(c), start_a(c), rowoff(c);
+    PoolBuf<double> sorted_b(c);
+    CHK(cell_of.alloc((size_t)std::max(na, nb)));
+    CHK(cnt.alloc((size_t)ncells + 1));
+    CHK(start.alloc((size_t)ncells + 1));
+    CHK(order_b.alloc((size_t)nb));
+    CHK(sorted_b.alloc((size_t)nb * DIM));
+    CHK(taper_bin<DIM>(c, g, ncells, nb, b, ldb, cell_of, cnt, start, order_b, sorted_b));
+    if (!same) {                                                     // queries in cell order too: a's own counting sort
+        CHK(order_a.alloc((size_t)na));
+        CHK(start_a.alloc((size_t)ncells + 1));
+        CHK(taper_bin<DIM>(c, g, ncells, na, a, lda, cell_of, cnt, start_a, order_a, nullptr));
+    }
+    CHK(rowcnt.alloc((size_t)na + 1));
+    CHK(rowoff.alloc((size_t)na + 1));
+
+    TaperSearch S{};
+    S.g = g; S.na = na; S.nb = nb; S.ncells = ncells; S.a = a; S.lda = lda;
+    S.order_a = same ? order_b.p : order_a.p;
+    S.start = start; S.sorted_b = sorted_b; S.order_b = order_b; S.rowcnt = rowcnt; S.err = c->d_err;
+    const int64_t waves = (na + WAVE / TP_G - 1) / (WAVE / TP_G);
+    const int sgrid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)c->n_cu * 32));
+    LAUNCH(c, "smm_taper_count", (smm_taper_search<DIM, false>), sgrid, 256, 0, S);
+    CHK(scan_launch<int>(c, na, rowcnt, rowoff));
+    int64_t nnz = 0;
+    HIPCHK(hipMemcpyAsync(&nnz, rowoff.p + na, sizeof(nnz), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (nnz < 0 || nnz >= INT32_MAX)
+        return fail(SMM_ERR_OVERFLOW, "smm_taper_build: %lld entries do not fit an operand (int32 row pointers, nnz < 2^31 - 1)", (long long)nnz);
+
+    CsrPtr m = new_csr(c, na, nb, nnz);
+    CHK(alloc_owned(c, m.get(), "the taper operand"));
+    S.rowoff = rowoff; S.idx = m->own_idx;
+    LAUNCH(c, "smm_taper_fill", (smm_taper_search<DIM, true>), sgrid, 256, 0, S);
+    CHK(seg_sort(c, na, rowoff, m->own_idx));
+    const int64_t vthreads = std::max<int64_t>(na * TP_G, na + 1);
+    const int vgrid = (int)std::max<int64_t>(1, std::min<int64_t>((vthreads + 255) / 256, (int64_t)c->n_cu * 32));
+    LAUNCH(c, "smm_taper_values", smm_taper_values<DIM>, vgrid, 256, 0, kind, g.half, na, a, lda, nb, b, ldb, (const int64_t *)rowoff,
+           (const int *)m->own_idx.p, m->own_ptr.p, m->own_val.p, c->d_err);
+    LAUNCH_CHECK();
+    CHK(take_plan_error(c, "smm_taper_build"));              // (synchronises: the temporaries may go back to the pool)
+    CHK(validate(c, m.get()));                               // (flags of the new operand: rows strictly ascending)
+    *out = std::move(m);
+    return SMM_OK;
+}
+
+// Everything smm_taper_build[_host] refuse before any launch.
+static int taper_args(smm_ctx *c, int dim, int kind, double cutoff, int64_t na, const double *a, int64_t lda, int64_t nb,
+                      const double *b, int64_t ldb, smm_csr **out, const char *where)
+{
+    if (!out) return fail(SMM_ERR_INVALID, "%s: out is NULL", where);
+    *out = nullptr;
+    if (!c) return fail(SMM_ERR_INVALID, "%s: ctx is NULL", where);
+    if (dim < 1 || dim > 3) return fail(SMM_ERR_INVALID, "%s: dim must be 1, 2 or 3, got %d", where, dim);
+    if (kind != SMM_TAPER_BOXCAR && kind != SMM_TAPER_GASPARI_COHN) return fail(SMM_ERR_INVALID, "%s: unknown taper kind %d", where, kind);
+    if (!(cutoff > 0.0) || !std::isfinite(cutoff)) return fail(SMM_ERR_INVALID, "%s: cutoff must be finite and positive, got %g", where, cutoff);
+    if (na < 0 || nb < 0 || na >= INT32_MAX || nb >= INT32_MAX)
+        return fail(SMM_ERR_INVALID, "%s: point counts must be in [0, 2^31 - 1) (na %lld, nb %lld)", where, (long long)na, (long long)nb);
+    if (lda < dim || ldb < dim) return fail(SMM_ERR_INVALID, "%s: need lda, ldb >= dim (dim %d, lda %lld, ldb %lld)", where, dim,
+                                            (long long)lda, (long long)ldb);
+    if ((na > 0 && !a) || (nb > 0 && !b)) return fail(SMM_ERR_INVALID, "%s: a or b is NULL", where);
+    HIPCHK(hipSetDevice(c->device));
+    return SMM_OK;
+}
+
+static int taper_dispatch(smm_ctx *c, int dim, int kind, double cutoff, int64_t na, const double *a, int64_t lda, int64_t nb,
+                          const double *b, int64_t ldb, smm_csr **out)
+{
+    CsrPtr m;
+    if (na == 0 || nb == 0) CHK(empty_csr(c, na, nb, &m));
+    else if (dim == 1) CHK(taper_impl<1>(c, kind, cutoff, na, a, lda, nb, b, ldb, &m));
+    else if (dim == 2) CHK(taper_impl<2>(c, kind, cutoff, na, a, lda, nb, b, ldb, &m));
+    else CHK(taper_impl<3>(c, kind, cutoff, na, a, lda, nb, b, ldb, &m));
+    *out = m.release();
+    return SMM_OK;
+}
+
+extern "C" int smm_taper_build(smm_ctx *c, int dim, int kind, double cutoff, int64_t na, const double *d_a, int64_t lda, int64_t nb,
+                               const double *d_b, int64_t ldb, smm_csr **out)
+{
+    CHK(taper_args(c, dim, kind, cutoff, na, d_a, lda, nb, d_b, ldb, out, "smm_taper_build"));
+    CTX_LOCK(c);
+    return taper_dispatch(c, dim, kind, cutoff, na, d_a, lda, nb, d_b, ldb, out);
+}
+
+// Same with host coordinates; b == a with ldb == lda and nb == na is uploaded once.
+extern "C" int smm_taper_build_host(smm_ctx *c, int dim, int kind, double cutoff, int64_t na, const double *a, int64_t lda, int64_t nb,
+                                    const double *b, int64_t ldb, smm_csr **out)
+{
+    CHK(taper_args(c, dim, kind, cutoff, na, a, lda, nb, b, ldb, out, "smm_taper_build_host"));
+    CTX_LOCK(c);
+    if (na == 0 || nb == 0) return taper_dispatch(c, dim, kind, cutoff, na, nullptr, dim, nb, nullptr, dim, out);
+    const bool same = a == b && lda == ldb && na == nb;
+    PoolBuf<double> da(c), db(c);
+    CHK(da.alloc((size_t)na * dim));
+    if (!same) CHK(db.alloc((size_t)nb * dim));
+    CHK(upload_rows(c, da, a, na, dim, lda));
+    if (!same) CHK(upload_rows(c, db, b, nb, dim, ldb));
+    return taper_dispatch(c, dim, kind, cutoff, na, da, dim, nb, same ? (const double *)da : (const double *)db, dim, out);
 }
 
 // ------------------------------------------------------------------------------ triple product, sparse output

@@ -9,11 +9,23 @@ import threading
 
 import numpy as np
 
-from ._lib import (SMM_EXACT, SMM_FULL_MATRIX, SMM_MIRROR, SMM_SCALE_BY_MASK, SMM_SYMMETRIC, SMM_TRANSPOSE, SmmError, SmmLibrary,
-                   check)
+from ._lib import (SMM_EXACT, SMM_FULL_MATRIX, SMM_MIRROR, SMM_SCALE_BY_MASK, SMM_SYMMETRIC, SMM_TAPER_BOXCAR, SMM_TAPER_GASPARI_COHN,
+                   SMM_TRANSPOSE, SmmError, SmmLibrary, check)
 
 __all__ = ["Context", "DeviceCSR", "default_context", "SmmError",
-           "SMM_SYMMETRIC", "SMM_FULL_MATRIX", "SMM_EXACT", "SMM_MIRROR", "SMM_TRANSPOSE", "SMM_SCALE_BY_MASK"]
+           "SMM_SYMMETRIC", "SMM_FULL_MATRIX", "SMM_EXACT", "SMM_MIRROR", "SMM_TRANSPOSE", "SMM_SCALE_BY_MASK",
+           "SMM_TAPER_BOXCAR", "SMM_TAPER_GASPARI_COHN", "TAPER_KINDS"]
+
+TAPER_KINDS = {"boxcar": SMM_TAPER_BOXCAR, "gaspari_cohn": SMM_TAPER_GASPARI_COHN}
+
+
+def _taper_kind(kind):
+    """SMM_TAPER_* for a name of TAPER_KINDS or the number itself."""
+    if isinstance(kind, str):
+        if kind not in TAPER_KINDS:
+            raise ValueError(f"unknown taper {kind!r}: expected one of {sorted(TAPER_KINDS)}")
+        return TAPER_KINDS[kind]
+    return int(kind)
 
 
 def _flags(symmetric=False, exact=False, full=False, mirror=False):
@@ -478,6 +490,47 @@ class Context:
                                            ctypes.c_void_p(_dptr(d_y)), int(ldy), ctypes.c_void_p(_dptr(d_c))))
         self.synchronize()
 
+    # ------------------------------------------------------------------ localisation taper from coordinates
+    @staticmethod
+    def _host_points(x, name):
+        """(points, dim): a C-contiguous float64 n x dim numpy array; a 1-D array is n points on a line."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim == 1:
+            x = x.reshape(-1, 1)
+        if x.ndim != 2:
+            raise ValueError(f"{name} must be 1-D or 2-D, got {x.ndim} dimensions")
+        return np.ascontiguousarray(x), int(x.shape[1])
+
+    def taper_host(self, a, b, cutoff, kind="gaspari_cohn"):
+        """The taper matrix of the numpy points a (na x dim, or na on a line) against b (nb x dim; None means b = a, the
+        square symmetric case): entry (i, j) iff |a_i - b_j| < cutoff, boxcar or Gaspari-Cohn weights, rows strictly
+        ascending, as a new DeviceCSR (smm_taper_build_host)."""
+        kind = _taper_kind(kind)
+        a, dim = self._host_points(a, "a")
+        if b is None:
+            b = a
+        else:
+            b, dim_b = self._host_points(b, "b")
+            if dim_b != dim:
+                raise ValueError(f"a has {dim} coordinates per point, b has {dim_b}")
+        h = ctypes.c_void_p()
+        check(self.lib, self.lib.smm_taper_build_host(self.handle, dim, kind, float(cutoff), a.shape[0], _ptr(a), dim, b.shape[0],
+                                                      _ptr(b), dim, ctypes.byref(h)))
+        return DeviceCSR(self, h, a.shape[0], b.shape[0], int(self.lib.smm_csr_nnz(h)))
+
+    def taper_into(self, d_a, lda, d_b, ldb, na, nb, dim, cutoff, kind="gaspari_cohn"):
+        """taper_host on device buffers: a (na x dim, leading dimension lda) at d_a, b (nb x dim, leading dimension ldb) at
+        d_b -- the same buffer for the square case (smm_taper_build).  Ints (device addresses) or torch tensors; stream
+        rules as spmm_into.  Returns the DeviceCSR, which the library owns: nothing of the caller's is kept."""
+        kind = _taper_kind(kind)
+        for t in (d_a, d_b):
+            if hasattr(t, "data_ptr"):
+                self._sync_torch(t)
+        h = ctypes.c_void_p()
+        check(self.lib, self.lib.smm_taper_build(self.handle, int(dim), kind, float(cutoff), int(na), ctypes.c_void_p(_dptr(d_a)), int(lda),
+                                                 int(nb), ctypes.c_void_p(_dptr(d_b)), int(ldb), ctypes.byref(h)))
+        return DeviceCSR(self, h, int(na), int(nb), int(self.lib.smm_csr_nnz(h)))
+
     # ------------------------------------------------------------------ CG on (H Q H^T + R) Z = D
     def _solve(self, entry, h, q, r, k, b, ldb, x, ldx, tol, maxiter, exact):
         info = SolveInfo(k)
@@ -566,6 +619,18 @@ class DeviceCSR:
         data = np.empty(self.nnz, dtype=np.float64)
         check(self.ctx.lib, self.ctx.lib.smm_csr_download(self.ctx.handle, self.handle, _ptr(indptr), _ptr(indices), _ptr(data)))
         return indptr, indices, data
+
+    def pattern_torch(self):
+        """The operand's row pointer and columns copied into new int32 CUDA tensors (device to device,
+        smm_csr_copy_device): (indptr, indices)."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        indptr = torch.empty(self.rows + 1, dtype=torch.int32, device=dev)
+        indices = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        check(self.ctx.lib, self.ctx.lib.smm_csr_copy_device(self.ctx.handle, self.handle, ctypes.c_void_p(indptr.data_ptr()),
+                                                             ctypes.c_void_p(indices.data_ptr()), None))
+        return indptr, indices
 
     def device_bytes(self):
         return int(self.ctx.lib.smm_csr_device_bytes(self.handle)) if self.handle else 0

@@ -22,7 +22,7 @@ import numpy as np
 from scipy.sparse import csr_matrix, isspmatrix_csr
 
 from ._lib import SMM_ERR_ALLOC, SmmError, SmmLibrary
-from .engine import SolveInfo, default_context
+from .engine import TAPER_KINDS, SolveInfo, default_context
 
 _INT32_MAX = np.iinfo(np.int32).max
 
@@ -404,9 +404,34 @@ class PinnedOperand:
         self._handle = ctx.csr_from_scipy(matrix) if self.nnz else None
         self._entry = _Entry(self._handle, ("pinned", id(self)), None)
 
+    @classmethod
+    def _adopt(cls, ctx, handle, shape=None):
+        """The second way of making one: around an operand that is in HBM already (a DeviceCSR the library owns, or one
+        that borrows device tensors and keeps them alive).  No copy, no hash; the handle belongs to the PinnedOperand
+        from here on.  handle None (with shape): an operand without entries, which holds nothing."""
+        self = cls.__new__(cls)
+        if handle is not None and handle.nnz == 0:
+            shape = (handle.rows, handle.cols)
+            handle.close()
+            handle = None
+        self.shape = (handle.rows, handle.cols) if handle is not None else tuple(int(n) for n in shape)
+        self.nnz = handle.nnz if handle is not None else 0
+        self._ctx = ctx
+        self._handle = handle
+        self._entry = _Entry(handle, ("pinned", id(self)), None)
+        return self
+
     def update_values(self, data):
         if self._handle is not None:
             self._handle.update_values(data)
+
+    def to_scipy(self):
+        """The operand's own arrays downloaded as a scipy CSR (int32 indices), whatever it was made from."""
+        if self._handle is None or not self._handle.handle:
+            if self.nnz:
+                raise ValueError("PinnedOperand: unpinned")
+            return csr_matrix(self.shape, dtype=np.float64)
+        return _result_csr(*self._handle.to_host(), self.shape)
 
     def _lease(self, ctx):
         if ctx is not self._ctx or self._handle is None or not self._handle.handle:
@@ -440,8 +465,122 @@ class PinnedOperand:
 
 
 def pin_operand(matrix):
-    """Upload `matrix` once and keep it (and everything derived from it) in HBM until unpin()."""
+    """Upload `matrix` once and keep it (and everything derived from it) in HBM until unpin().  A DeviceCSRResult -- a
+    result left in HBM under set_result_device(True) -- is pinned where it is: its row pointer is narrowed to int32 on the
+    device and the three tensors are borrowed (and kept alive) by the operand; nothing is copied to the host or hashed."""
+    if isinstance(matrix, DeviceCSRResult):
+        return _pin_device_result(matrix)
     return PinnedOperand(default_context(), matrix)
+
+
+def _pin_device_result(res):
+    rows, cols = res.shape
+    nnz = res.nnz
+    if nnz >= _INT32_MAX or rows >= _INT32_MAX or cols >= _INT32_MAX:
+        raise ValueError(f"pin_operand: a {rows} x {cols} result with {nnz} entries does not fit an operand "
+                         "(int32 row pointers and columns: dimensions and nnz must be below 2^31 - 1)")
+    ctx = default_context()
+    if nnz == 0:
+        return PinnedOperand._adopt(ctx, None, (rows, cols))
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    if res.indices.device != dev:
+        raise ValueError(f"pin_operand: the result is on {res.indices.device}, the library works on {dev}")
+    indptr = res.indptr.to(torch.int32)                  # (on the device; csr_from_torch waits for torch's stream)
+    return PinnedOperand._adopt(ctx, ctx.csr_from_torch(rows, cols, indptr, res.indices.contiguous(), res.data.contiguous()))
+
+
+# ------------------------------------------------------------------ localisation taper from coordinates
+def _taper_points(x, what, name):
+    """(points, n, dim, is_torch): a C-contiguous float64 n x dim numpy array, or a float64 CUDA tensor (1-D, or 2-D with
+    unit column stride).  1-D means points on a line.  ValueError before any device work."""
+    is_torch = type(x).__module__.split(".")[0] == "torch"
+    if is_torch:
+        import torch
+        if x.dtype != torch.float64 or not x.is_cuda:
+            raise ValueError(f"{what}: a torch {name} must be a float64 CUDA tensor")
+        ndim = x.dim()
+    else:
+        x = np.asarray(x, dtype=np.float64)
+        ndim = x.ndim
+    if ndim not in (1, 2):
+        raise ValueError(f"{what}: {name} must be 1-D (points on a line) or 2-D (n x dim), got {ndim} dimensions")
+    n, dim = int(x.shape[0]), (1 if ndim == 1 else int(x.shape[1]))
+    if dim < 1 or dim > 3:
+        raise ValueError(f"{what}: {name} has {dim} coordinates per point, expected 1, 2 or 3")
+    if not is_torch:
+        x = np.ascontiguousarray(x.reshape(n, dim))
+    return x, n, dim, is_torch
+
+
+def _taper_result(handle, shape, pin):
+    if pin:
+        return PinnedOperand._adopt(handle.ctx, handle)
+    try:
+        return _result_csr(*handle.to_host(), shape)
+    finally:
+        handle.close()
+
+
+def localization_taper(coords, cutoff, coords_b=None, taper="gaspari_cohn", pin=False):
+    """The localisation matrix L of a set of points, built on the GPU: L[i, j] = w(|coords[i] - coords_b[j]|) for every
+    pair closer than `cutoff` -- the `mask` of sparse_triple_product and masked_matrix_multiply and the weights of
+    sampled_dense_product(..., scale_by_mask=True).
+
+    coords   : n x dim (dim 1, 2 or 3) or 1-D (n points on a line); a numpy array (cast to float64) or a float64 CUDA
+               tensor on the library's device with unit column stride (a column slice of a wider tensor is used in place).
+    coords_b : the same kinds, nb x dim; None means coords itself: L is square and symmetric bit for bit.
+    cutoff   : finite and positive.  Entry (i, j) is stored iff the squared distance, summed coordinate by coordinate in
+               float64, is < cutoff * cutoff (strict).  Distances are Euclidean: for a sphere pass unit-sphere xyz and a
+               chord cutoff.
+    taper    : "gaspari_cohn" (Gaspari & Cohn 1999, eq. 4.10, half-width cutoff / 2: 1 at distance 0, 0 at the cutoff;
+               a correlation function in up to three dimensions) or "boxcar" (1.0 everywhere).
+    pin      : False returns a scipy CSR (int32 indices, canonical).  True returns a PinnedOperand that adopts the
+               library's operand where it is -- no copy to the host: pass it wherever a matrix is accepted.
+    Pattern and values are bit-identical to the order written out in include/smm_hip.h, whatever the grid of cells that
+    finds the candidates.  Argument errors are ValueError before any device call; NaN or infinite coordinates are refused
+    by the library (SmmError).  Without points the result is empty and no device is touched.  Nothing is printed.
+    """
+    what = "localization_taper"
+    if not isinstance(taper, str) or taper not in TAPER_KINDS:
+        raise ValueError(f"{what}: unknown taper {taper!r}, expected one of {sorted(TAPER_KINDS)}")
+    try:
+        cutoff = float(cutoff)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: cutoff must be a finite positive number") from None
+    if not (cutoff > 0.0 and np.isfinite(cutoff)):
+        raise ValueError(f"{what}: cutoff must be a finite positive number, got {cutoff}")
+    a, na, dim, a_torch = _taper_points(coords, what, "coords")
+    if coords_b is None:
+        b, nb, b_torch = a, na, a_torch
+    else:
+        b, nb, dim_b, b_torch = _taper_points(coords_b, what, "coords_b")
+        if dim_b != dim:
+            raise ValueError(f"{what}: coords has {dim} coordinates per point, coords_b has {dim_b}")
+    if na >= _INT32_MAX or nb >= _INT32_MAX:
+        raise ValueError(f"{what}: at most 2^31 - 2 points on either side, got {na} and {nb}")
+    if na == 0 or nb == 0:
+        return PinnedOperand._adopt(None, None, (na, nb)) if pin else csr_matrix((na, nb), dtype=np.float64)
+    ctx = default_context()
+    if not (a_torch or b_torch):
+        return _taper_result(ctx.taper_host(a, None if b is a else b, cutoff, taper), (na, nb), pin)
+    import torch
+    dev = torch.device("cuda", ctx.device)
+
+    def on_dev(t, is_torch, name):
+        if not is_torch:
+            return torch.from_numpy(t).to(dev)
+        if t.device != dev:
+            raise ValueError(f"{what}: {name} is on {t.device}, the library works on {dev}")
+        if t.dim() == 2 and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+            t = t.contiguous()
+        return t
+
+    da = on_dev(a, a_torch, "coords")
+    db = da if b is a else on_dev(b, b_torch, "coords_b")
+    handle = _on_device(ctx, lambda: ctx.taper_into(da, max(int(da.stride(0)), dim), db, max(int(db.stride(0)), dim), na, nb, dim,
+                                                    cutoff, taper))
+    return _taper_result(handle, (na, nb), pin)
 
 
 def _device_zeros(ctx, shape, sparse):
@@ -938,7 +1077,9 @@ def sampled_dense_product(x, y, mask, scale_by_mask=False):
     mask = _canonical_mask(mask)
 
     def body(lm):
-        indptr, indices = _mask_pattern(mask)
+        # a pinned mask whose result stays in HBM hands its pattern over on the device; every other case as before
+        on_device_pattern = _result_device and isinstance(mask, PinnedOperand)
+        indptr, indices = (None, None) if on_device_pattern else _mask_pattern(mask)
         if not (x_torch or y_torch or _result_device):
             data = ctx.sddmm_host(lm.handle, x, None if y is x else y, scale=scale_by_mask, exact=_exact)
             return _result_csr(indptr, indices, data, out_shape)
@@ -961,6 +1102,9 @@ def sampled_dense_product(x, y, mask, scale_by_mask=False):
             return data
 
         data = _on_device(ctx, call)
+        if on_device_pattern:
+            d_indptr, d_indices = lm.handle.pattern_torch()
+            return DeviceCSRResult(d_indptr.to(torch.int64), d_indices, data, out_shape)
         if _result_device:
             return _pattern_result(ctx, indptr, indices, data, out_shape)
         return _result_csr(indptr, indices, data.cpu().numpy(), out_shape)
