@@ -1163,8 +1163,16 @@ __global__ __launch_bounds__(256) void smm_symbolic_ccs(int m, int n_slabs, cons
 // its own (positions in the list ARE positions in the result).  tail[row] = {e0, P[e0]}.
 // tail_min is a kernel argument (round 4): 32 for the default walk (interleaved A/B in both orders at configs[1]: 8: 31.63,
 // 16: 31.38, 32: 31.13-31.22, 64: 31.26-31.47, 128: 31.37, 256: 31.92 ms per step), 64 for SMM_EXACT (8 waves share the
-// tail: 39.1 against 39.5 ms with 32).
-constexpr int TAIL_MIN_DEFAULT = 32, TAIL_MIN_EXACT = 64;
+// tail: 39.1 against 39.5 ms with 32).  Re-swept with one index writer per tail (SMM_EPI_OWNER; interleaved, six runs per
+// build, profiles/epi_owner_ab.txt): default walk 16: 31.14, 32: 30.87, 64: 30.80 ms per step with run-to-run spreads of
+// 0.18-0.32 -- 32 and 64 are not told apart, 32 stays.  -DSMM_TAIL_MIN_DEFAULT / _EXACT build a diagnostic variant.
+#ifndef SMM_TAIL_MIN_DEFAULT
+#define SMM_TAIL_MIN_DEFAULT 32
+#endif
+#ifndef SMM_TAIL_MIN_EXACT
+#define SMM_TAIL_MIN_EXACT 64
+#endif
+constexpr int TAIL_MIN_DEFAULT = SMM_TAIL_MIN_DEFAULT, TAIL_MIN_EXACT = SMM_TAIL_MIN_EXACT;
 constexpr int RUNS_WIN = 2048;
 template <typename LT>
 __global__ __launch_bounds__(256) void smm_runs(int m, int nct, int wc, const int *__restrict__ rowlist,
@@ -1820,6 +1828,31 @@ template <typename T> __device__ __forceinline__ T ld_stream(const T *p) {
 #endif
 }
 constexpr int EPI_UNROLL = SMM_EPI_UNROLL;
+// Index ownership in the CSR epilogue (non-slab lists).  The units of a row interleave their sub-runs in the row of
+// C and run far apart in time (tile-major), so a sector at a sub-run boundary used to be written by two units and a
+// tail sector by up to nct.  But c_idx[rs + p] IS list[p] -- global columns, one list per row -- so a unit can store
+// the indices of positions whose values belong to a neighbour.  With S = EPI_S entries per granule, k = rs mod S,
+//     up(x) = smallest y >= x with (rs + y) mod S == 0,      f(x) = x == 0 ? 0 : min(up(x), row length),
+// a non-empty sub-run [r0, r1) stores the indices of [f(r0), f(r1)) (and the values of [r0, r1), as ever), an empty
+// one nothing; the tail [tail0, row length) has ONE index owner, the first tile that runs for a non-empty row (tile 0;
+// under SYM the tile that holds the diagonal column), which stores [f(tail0), row length).  f is monotone, f(0) = 0:
+// the owned ranges partition the row, every index granule is stored whole by one workgroup (but for the two a row
+// shares with its neighbours).  The rule is stated and checked in plain Python in tests/epilogue_owner_restatement.py.
+// -DSMM_EPI_OWNER=0 builds the stores as they were (every unit stores the indices of exactly its own positions), and so
+// does the SMM_EXACT walk in every build (it loses there, see the epilogue).
+#ifndef SMM_EPI_OWNER
+#define SMM_EPI_OWNER 1
+#endif
+#ifndef SMM_EPI_S
+#define SMM_EPI_S 16        // 16 x 4 B = 64 B: whole for 32- and 64-byte granules, at most 15 list entries over-read
+#endif
+constexpr unsigned EPI_S = SMM_EPI_S;
+static_assert(EPI_S == 8 || EPI_S == 16, "ownership granule: 8 or 16 indices");
+__device__ __forceinline__ unsigned epi_owned_from(const unsigned x, const unsigned k, const unsigned rowlen)
+{
+    const unsigned up = ((x + k + EPI_S - 1u) & ~(EPI_S - 1u)) - k;
+    return x == 0u ? 0u : (up < rowlen ? up : rowlen);
+}
 
 // SCR: the tile is not accumulated here but loaded from the dense scratch rows smm_dense_slab left
 // in column order (A.c_dense / A.ldc, one scratch row per row of the launch); the kernel is then only
@@ -1964,6 +1997,10 @@ __device__ __forceinline__ void smm_numeric_unit(const NumericArgs &A, double *_
             tail0 = rowlen;
         }
 #endif
+        // index ownership (SMM_EPI_OWNER above).  Not under SMM_EXACT: measured there it LOSES (39.4 -> 42.0 ms per step at
+        // configs[1], 41.4 with a tail threshold of 128; profiles/epi_owner_ab.txt), so the exact walk keeps the old stores.
+        constexpr bool OWN = SMM_EPI_OWNER != 0 && !EXACT;
+        [[maybe_unused]] const unsigned own_k = (unsigned)rs & (EPI_S - 1u);
         for (int rb = a0; rb < e0; rb += NW * WAVE) {
             const int e = rb + wave + NW * lane;
             const bool ev = e < e0;
@@ -1973,12 +2010,21 @@ __device__ __forceinline__ void smm_numeric_unit(const NumericArgs &A, double *_
 #if SMM_CLAMPS
             if (r1 < r0 || r1 > rowlen) { plan_err(A.err, PLAN_ERR_RUNS, row); r1 = r0; }
 #endif
-            const int nch = (int)((r1 - r0 + WAVE - 1) >> 6);
+            // (r0 < r1 <= rowlen for a non-empty sub-run, clamped above or not: f0 <= f1 <= rowlen, and the chunks
+            // reach at most EPI_S - 1 entries past r1 -- the neighbours' entries of the same list)
+            [[maybe_unused]] unsigned f0 = r0, f1 = r0;
+            unsigned rend = r1;
+            if constexpr (OWN) {
+                if (r1 > r0) { f0 = epi_owned_from(r0, own_k, rowlen); f1 = epi_owned_from(r1, own_k, rowlen); }
+                rend = f1 > r1 ? f1 : r1;
+            }
+            const int nch = (int)((rend - r0 + WAVE - 1) >> 6);
             const int incl = wave_scan_incl(nch);
             const int total = rl(incl, WAVE - 1);
             for (int t0 = 0; t0 < total; t0 += EPI_UNROLL) {
                 int c[EPI_UNROLL];
                 unsigned sl[EPI_UNROLL];
+                [[maybe_unused]] unsigned own[EPI_UNROLL];      // bit 0 / 1: this lane stores the index / the value of its position
 #pragma unroll
                 for (int u = 0; u < EPI_UNROLL; ++u) {          // all chunk loads of the round first
                     const int t = t0 + u;
@@ -1987,18 +2033,31 @@ __device__ __forceinline__ void smm_numeric_unit(const NumericArgs &A, double *_
                     const int first = rl(incl, i) - rl(nch, i);
                     const unsigned s0 = rl(r0, i), s1 = rl(r1, i);
                     sl[u] = s0 + ((unsigned)(t - first) << 6) + (unsigned)lane;
-                    const bool p = t < total && sl[u] < s1;
+                    bool p = t < total && sl[u] < s1;
+                    if constexpr (OWN) {
+                        own[u] = (t < total && sl[u] >= rl(f0, i) && sl[u] < rl(f1, i) ? 1u : 0u) | (p ? 2u : 0u);
+                        p = t < total && sl[u] < rl(rend, i);
+                    }
                     const LT *ip = p ? list + sl[u] : (const LT *)A.dummy_idx;
                     c[u] = (int)ld_stream(ip);
                 }
 #pragma unroll
-                for (int u = 0; u < EPI_UNROLL; ++u)        // idle lanes read the dummy word: -1, or 0xffff as uint16 (no column: B has < 65 535)
-                    if (L16 ? c[u] != 0xffff : c[u] >= 0) { st_stream(&oi[sl[u]], c[u]); st_stream(&ov[sl[u]], acc[c[u] - lo_c]); }
+                for (int u = 0; u < EPI_UNROLL; ++u) {
+                    if constexpr (OWN) {
+                        if (own[u] & 1u) st_stream(&oi[sl[u]], c[u]);
+                        if (own[u] & 2u) st_stream(&ov[sl[u]], acc[c[u] - lo_c]);
+                    } else {        // idle lanes read the dummy word: -1, or 0xffff as uint16 (no column: B has < 65 535)
+                        if (L16 ? c[u] != 0xffff : c[u] >= 0) { st_stream(&oi[sl[u]], c[u]); st_stream(&ov[sl[u]], acc[c[u] - lo_c]); }
+                    }
+                }
             }
         }
         // the tail (see TAIL_MIN): list positions [tl.y, row length) 64 at a time, this tile's columns kept.
         // (the dummy word of idle lanes, -1 or 0xffff, lies in no tile: B has < 65 535 columns when lists are 16-bit)
         const unsigned ntc = rowlen > tail0 ? (rowlen - tail0 + WAVE - 1) >> 6 : 0u;
+        // one unit stores the tail's indices, all of them: the first tile that is not skipped above for this row
+        [[maybe_unused]] const bool tail_owner = SYM ? (int64_t)lo_c <= gi : tc == 0;
+        [[maybe_unused]] const unsigned ft0 = tail_owner ? epi_owned_from(tail0, own_k, rowlen) : rowlen;
         for (unsigned q0 = (unsigned)wave; q0 < ntc; q0 += NW * EPI_UNROLL) {
             int c[EPI_UNROLL];
             unsigned ps[EPI_UNROLL];
@@ -2013,7 +2072,12 @@ __device__ __forceinline__ void smm_numeric_unit(const NumericArgs &A, double *_
 #pragma unroll
             for (int u = 0; u < EPI_UNROLL; ++u) {
                 const unsigned cc = (unsigned)(c[u] - lo_c);
-                if (cc < (unsigned)w) { st_stream(&oi[ps[u]], c[u]); st_stream(&ov[ps[u]], acc[cc]); }
+                if constexpr (OWN) {
+                    if (ps[u] >= ft0 && ps[u] < rowlen) st_stream(&oi[ps[u]], c[u]);    // (q >= ntc puts ps past the row)
+                    if (cc < (unsigned)w) st_stream(&ov[ps[u]], acc[cc]);
+                } else {
+                    if (cc < (unsigned)w) { st_stream(&oi[ps[u]], c[u]); st_stream(&ov[ps[u]], acc[cc]); }
+                }
             }
         }
     }
