@@ -139,6 +139,9 @@ int  smm_ctx_tune_dense_runs(smm_ctx *ctx, int mode);
  * chunk kernel.  Results are identical (bit for bit under SMM_EXACT); the ring is the slower of the two on MI355X
  *  and is kept as a tested alternative.  Also: env SMM_S2_RING=1 when the context is created. */
 int  smm_ctx_tune_stage2(smm_ctx *ctx, int ring);
+/* B's packed payload for the CSR product's piece walk: 1 = 1.5-byte columns ("pack12") where that is smaller (default),
+   0 = 16-bit columns always, 2 = pack12 wherever the four-entries-per-lane walk applies.  Results never depend on it. */
+int  smm_ctx_tune_pack(smm_ctx *ctx, int mode);
 /* Run-time guard of SMM_EXACT.  The exact walk adds the products of one wave-instruction that fall on the same
  * accumulator in ascending lane order (the reference's order, src/sparsework.cpp:59-76) -- a property of
  * gfx950's ds_add_f64 that was measured, not one the ISA promises.  This runs a sub-millisecond kernel that

@@ -76,6 +76,8 @@ struct smm_ctx {
     int sym_wide = 1;        // symbolic phase on 16-bit columns: chunks of 128 entries (env SMM_SYM_WIDE=0: 64)
     int sym_ccs = 1;         // symbolic phase over the chunk-padded column stream (smm_symbolic_ccs; env SMM_SYM_CCS=0: smm_symbolic)
     int piece_walk = 1;      // default mode: one piece of B per wave iteration where every piece has <= 256 entries (env SMM_PIECE_WALK=0: chunk walk)
+    int pack12 = 1;          // pack12 payload of B (1.5-byte columns, smm_pack12_*) for the CSR product's four-entries-per-lane piece walk: 1 = where it is
+                             // smaller than the 16-bit payload, 0 never, 2 wherever that walk applies (env SMM_PACK12, smm_ctx_tune_pack)
     int sym_max_ws = 0;      // widest column slab of that walk (0 = CCS_MAX_WS); B with more columns is walked slab by slab
                              // (smm_ctx_tune_symbolic; tests set it small to reach the slab path with small matrices)
     int sym_dense = 1;       // symbolic walk over operands with dense runs of columns: 0 never, 1 chosen from B (>= 80 % of the neighbouring
@@ -279,6 +281,7 @@ extern "C" int smm_ctx_create(int device, void *hip_stream, smm_ctx **out)
     if (const char *e = getenv("SMM_SYM_WIDE")) c->sym_wide = atoi(e) != 0;
     if (const char *e = getenv("SMM_SYM_CCS")) c->sym_ccs = atoi(e) != 0;
     if (const char *e = getenv("SMM_PIECE_WALK")) c->piece_walk = atoi(e);
+    if (const char *e = getenv("SMM_PACK12")) c->pack12 = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("SMM_SYM_MAX_WS")) c->sym_max_ws = std::max(0, std::min(atoi(e), (int)CCS_MAX_WS));
     if (const char *e = getenv("SMM_CHECK")) c->check = atoi(e) != 0;
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -518,6 +521,14 @@ extern "C" int smm_ctx_tune_stage2(smm_ctx *c, int ring)
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
     c->s2_ring = ring != 0;
+    return SMM_OK;
+}
+extern "C" int smm_ctx_tune_pack(smm_ctx *c, int mode)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    if (mode < 0 || mode > 2) return fail(SMM_ERR_INVALID, "mode must be 0 (never), 1 (where smaller) or 2 (wherever the walk applies)");
+    c->pack12 = mode;
     return SMM_OK;
 }
 extern "C" int smm_ctx_tune_shared(smm_ctx *c, int lds_cols, int waves)
@@ -792,11 +803,13 @@ struct smm_csr {
         int ws, n_slabs; const int *seg; DevBuf<int> soff; DevBuf<short> scol; DevBuf<double> sval;
         SlabView view() const { return {ws, n_slabs, soff, scol, sval}; }
     };
-    // packed tile-major payload (smm_pack_*); maxlen: longest piece
-    struct PackView { int wc, nct; int2 *desc; double *pay; int maxlen; };
+    // packed tile-major payload (smm_pack_*), one entry per (tile geometry, format); maxlen: longest piece (fmt 0: entries;
+    // PACK_FMT_12: slots n).  A pack12 entry always holds the counts it was judged by (units16 / units12: the operand as
+    // either format, in 8-byte units) and its arrays only once a product chose it.
+    struct PackView { int wc, nct; int2 *desc; double *pay; int maxlen; int fmt; };
     struct PackCache {
-        int wc, nct; const int *seg; DevBuf<int2> desc; DevBuf<double> pay; int maxlen;
-        PackView view() const { return {wc, nct, desc, pay, maxlen}; }
+        int wc, nct; const int *seg; DevBuf<int2> desc; DevBuf<double> pay; int maxlen; int fmt; int64_t units16, units12;
+        PackView view() const { return {wc, nct, desc, pay, maxlen, fmt}; }
     };
     // chunk-padded 16-bit column stream per column slab (smm_ccs_*): the symbolic phase's gather stream
     // (same_word: share of neighbouring entries in one bitmap word)
@@ -1286,7 +1299,7 @@ struct smm_plan {
     unsigned char *d_tflag = nullptr;   // nct x m: which (tile, row) units hold entries of C
     const int *seg = nullptr;      // B's tile index and tile-local columns for geometry g (owned by b)
     const short *loc = nullptr;
-    smm_csr::PackView pack{0, 0, nullptr, nullptr, 0};    // default mode: packed payload of B for geometry g
+    smm_csr::PackView pack{0, 0, nullptr, nullptr, 0, 0}; // default mode: packed payload of B for geometry g
     bool use_slab = false;         // dense-bin rows: smm_dense_slab -> scratch -> emission, instead of the tile kernel
     SlabGeom sg{};
     smm_csr::SlabView slab{0, 0, nullptr, nullptr, nullptr};
@@ -1345,21 +1358,84 @@ static int scan_launch(smm_ctx *c, int64_t n, const T *in, int64_t *out)
     return SMM_OK;
 }
 
-// Packed tile-major payload of B for the shared-tile walk (smm_pack_* in smm_kernels.hpp), cached per geometry.
-// pack_fill: the payload of e from b's current values; queued, not checked.
+// Packed tile-major payload of B for the shared-tile walk (smm_pack_* / smm_pack12_* in smm_kernels.hpp), cached per
+// (geometry, format).
+// pack_fill: the payload of e from b's current values (pack12: +0.0 into the mid-piece pads as well); queued, not checked.
 static void pack_fill(smm_ctx *c, const smm_csr *b, const smm_csr::PackCache &e)
 {
-    if ((int64_t)e.nct * b->rows > 0)
+    const int64_t cells = (int64_t)e.nct * b->rows;
+    if (cells <= 0 || !e.pay) return;
+    if (e.fmt == PACK_FMT_12)
+        LAUNCH(c, "smm_pack12_fill", smm_pack12_fill, std::min<int64_t>((cells + 3) / 4, 65536), 256, 0, (int)b->rows, e.nct, e.wc, b->idx, b->val, e.seg,
+               (const int2 *)e.desc, e.pay.p);
+    else
         LAUNCH(c, "smm_pack_fill", smm_pack_fill, std::min<int64_t>((b->rows + 3) / 4, 65536), 256, 0, (int)b->rows, e.nct, e.wc, b->ptr,
                b->idx, b->val, e.seg, (const int2 *)e.desc, e.pay.p);
 }
-// (descriptors are handed out BY VALUE: a plan must not point into the operand's vector, which may grow)
-static int ensure_pack(smm_ctx *c, smm_csr *b, const Geom &g, smm_csr::PackView *out)
+// The pack12 rule: the walk that reads it runs four entries per lane (longest n in (128, 256]) and, unless forced
+// (mode 2), the operand is smaller that way.
+static bool pack12_chosen(const smm_ctx *c, const smm_csr::PackCache &e)
 {
-    for (auto &e : b->packs)
-        if (e.wc == g.wc && e.nct == g.nct) { *out = e.view(); return SMM_OK; }
+    if (c->pack12 == 0 || !c->piece_walk || e.maxlen <= 128 || e.maxlen > 256) return false;
+    return c->pack12 == 2 || e.units12 < e.units16;
+}
+// Count b's pieces as pack12 into e (a new entry, or one that holds no arrays yet) and build its arrays where the rule chooses it.
+static int pack12_prepare(smm_ctx *c, smm_csr *b, smm_csr::PackCache &e)
+{
+    const int64_t cells = (int64_t)e.nct * b->rows;
+    if (cells + 1 >= INT32_MAX) return fail(SMM_ERR_INVALID, "too many (tile, row) pieces");
+    PoolBuf<int> units(c), n12(c);
+    PoolBuf<int64_t> off64(c);
+    PoolBuf<unsigned long long> d_stat(c);
+    CHK(units.alloc((size_t)std::max<int64_t>(cells, 1)));
+    CHK(n12.alloc((size_t)std::max<int64_t>(cells, 1)));
+    CHK(off64.alloc((size_t)cells + 1));
+    CHK(d_stat.alloc(4));
+    HIPCHK(hipMemsetAsync(d_stat, 0, 4 * sizeof(unsigned long long), c->stream));
+    if (cells > 0)
+        LAUNCH(c, "smm_pack12_count", smm_pack12_count, (cells + 255) / 256, 256, 0, (int)b->rows, e.nct, e.wc, b->idx, e.seg, units.p, n12.p, d_stat.p);
+    LAUNCH_CHECK();
+    unsigned long long stat[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(stat, d_stat, sizeof(stat), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    e.maxlen = (int)stat[0]; e.units16 = (int64_t)stat[1]; e.units12 = (int64_t)stat[2];
+    if (pack12_chosen(c, e)) {
+        if (e.units12 >= INT32_MAX) return fail(SMM_ERR_INVALID, "operand too large for the packed payload");
+        CHK(scan_launch<int>(c, cells, units, off64));
+        // (+ 4 units of slack, as for the 16-bit payload)
+        if (e.desc.alloc(c, (size_t)std::max<int64_t>(cells, 1)) != hipSuccess || e.pay.alloc(c, (size_t)(std::max<int64_t>(e.units12, 1) + 4)) != hipSuccess)
+            return fail(SMM_ERR_ALLOC, "hipMalloc of the packed payload failed");
+        LAUNCH(c, "smm_pack12_desc", smm_pack12_desc, (cells + 255) / 256, 256, 0, cells, (const int64_t *)off64, (const int *)n12, e.desc.p);
+        pack_fill(c, b, e);
+        LAUNCH_CHECK();
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));            // units / n12 / off64 go back to the pool
+    units.reset(); n12.reset(); off64.reset(); d_stat.reset();
+    return SMM_OK;
+}
+// fmt: what the caller's walk can read -- PACK_FMT_12 asks for pack12 where the rule chooses it and gets the 16-bit
+// payload otherwise (out->fmt says which).
+// (descriptors are handed out BY VALUE: a plan must not point into the operand's vector, which may grow)
+static int ensure_pack(smm_ctx *c, smm_csr *b, const Geom &g, int fmt, smm_csr::PackView *out)
+{
     if (g.wc > 32767) return fail(SMM_ERR_INVALID, "coarse tile wider than 32767 columns");
-    smm_csr::PackCache e{g.wc, g.nct, nullptr, {}, {}, 0};
+    if (fmt == PACK_FMT_12 && c->pack12 != 0 && c->piece_walk) {
+        size_t at = b->packs.size();
+        for (size_t i = 0; i < b->packs.size(); ++i)
+            if (b->packs[i].wc == g.wc && b->packs[i].nct == g.nct && b->packs[i].fmt == PACK_FMT_12) at = i;
+        if (at == b->packs.size()) {
+            smm_csr::PackCache e{g.wc, g.nct, nullptr, {}, {}, 0, PACK_FMT_12, 0, 0};
+            CHK(ensure_seg(c, b, tiles_geom(g.nct, g.wc), &e.seg));
+            CHK(pack12_prepare(c, b, e));
+            b->packs.push_back(std::move(e));
+        } else if (!b->packs[at].pay && pack12_chosen(c, b->packs[at])) {
+            CHK(pack12_prepare(c, b, b->packs[at]));       // (judged under another SMM_PACK12 mode before)
+        }
+        if (b->packs[at].pay && pack12_chosen(c, b->packs[at])) { *out = b->packs[at].view(); return SMM_OK; }
+    }
+    for (auto &e : b->packs)
+        if (e.wc == g.wc && e.nct == g.nct && e.fmt == PACK_FMT_16) { *out = e.view(); return SMM_OK; }
+    smm_csr::PackCache e{g.wc, g.nct, nullptr, {}, {}, 0, PACK_FMT_16, 0, 0};
     CHK(ensure_seg(c, b, tiles_geom(g.nct, g.wc), &e.seg));   // the coarse-tile index (shared walk: one entry per coarse tile)
     const int64_t cells = (int64_t)g.nct * b->rows;
     if (cells + 1 >= INT32_MAX) return fail(SMM_ERR_INVALID, "too many (tile, row) pieces");
@@ -1376,6 +1452,7 @@ static int ensure_pack(smm_ctx *c, smm_csr *b, const Geom &g, smm_csr::PackView 
     HIPCHK(hipMemcpyAsync(&e.maxlen, d_maxlen, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (total >= INT32_MAX) return fail(SMM_ERR_INVALID, "operand too large for the packed payload");
+    e.units16 = total;
     // (+ 4 units of slack: the piece walk's last lane reads up to three 8-byte units past a very short last piece)
     if (e.desc.alloc(c, (size_t)std::max<int64_t>(cells, 1)) != hipSuccess || e.pay.alloc(c, (size_t)(std::max<int64_t>(total, 1) + 4)) != hipSuccess)
         return fail(SMM_ERR_ALLOC, "hipMalloc of the packed payload failed");
@@ -1896,7 +1973,7 @@ static int sym_slab_walk(smm_ctx *c, smm_plan *p, SymRows &r)
             CHK(ensure_seg(c, b, p->g, &p->seg));
             CHK(ensure_loc(c, b, p->g, &p->loc));
         } else {
-            CHK(ensure_pack(c, b, p->g, &p->pack));
+            CHK(ensure_pack(c, b, p->g, PACK_FMT_16, &p->pack));
         }
         CHK(pool_get(c, (size_t)a->nnz, &p->d_dst0));
         CHK(pool_get(c, (size_t)a->nnz * p->g.nct, &p->d_runs2));
@@ -2021,7 +2098,8 @@ static int sym_runs(smm_ctx *c, smm_plan *p, SymRows &r)
         CHK(ensure_seg(c, b, p->g, &p->seg));
         CHK(ensure_loc(c, b, p->g, &p->loc));
     } else {
-        CHK(ensure_pack(c, b, p->g, &p->pack));
+        // (pack12 where the rule chooses it, the 16-bit payload otherwise; the slab path's fall-back keeps 16 bits)
+        CHK(ensure_pack(c, b, p->g, p->use_slab ? PACK_FMT_16 : PACK_FMT_12, &p->pack));
     }
     CHK(pool_get(c, (size_t)a->nnz * (p->g.nct + 1), &p->d_runs));
     CHK(pool_get(c, (size_t)m, &p->d_tail));
@@ -2142,6 +2220,8 @@ extern "C" int smm_spgemm_numeric(smm_ctx *c, smm_plan *p, int64_t *d_c_indptr, 
         A.kmax = (int)std::max<int64_t>(p->b->nnz - 1, 0);
         A.tdesc = p->pack.desc; A.tpay = p->pack.pay;
         A.piece_epl = !c->piece_walk || !p->pack.pay ? 0 : (p->pack.maxlen <= 128 ? 2 : (p->pack.maxlen <= 256 ? 4 : 0));
+        A.piece_fmt = p->pack.fmt;
+        if (A.piece_fmt == PACK_FMT_12 && A.piece_epl != 4) return fail(SMM_ERR_INTERNAL, "pack12 payload without the four-entries-per-lane walk");
         A.rowsB = (int)p->b->rows;
         A.c_ptr = p->d_cptr; A.c_idx = d_c_indices; A.c_val = d_c_data;
         A.ub_off = p->d_ub_off; A.tmp_idx = p->d_tmp; A.list16 = p->list16 ? 1 : 0; A.runs = p->d_runs; A.tail = p->d_tail;
@@ -2246,12 +2326,12 @@ static int dense_into(smm_ctx *c, smm_csr *a, smm_csr *b, int flags, int64_t row
     if (!(b->vflags & CSR_UNSORTED)) {
         Geom g = make_geom(c, n, b, (flags & SMM_EXACT) != 0);
         const int *seg = nullptr; const short *loc = nullptr;
-        smm_csr::PackView pack{0, 0, nullptr, nullptr, 0};
+        smm_csr::PackView pack{0, 0, nullptr, nullptr, 0, 0};
         if (flags & SMM_EXACT) {
             CHK(ensure_seg(c, b, g, &seg));
             CHK(ensure_loc(c, b, g, &loc));
         } else {
-            CHK(ensure_pack(c, b, g, &pack));
+            CHK(ensure_pack(c, b, g, PACK_FMT_16, &pack));
         }
         NumericArgs A{};
         A.m = (int)m; A.ncols = (int)n; A.nct = g.nct; A.wc = g.wc; A.wf = g.wf; A.n_ft = g.n_ft;

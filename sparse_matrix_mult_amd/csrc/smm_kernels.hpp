@@ -386,6 +386,144 @@ __global__ __launch_bounds__(256) void smm_pack_fill(int rows, int nct, int wc, 
     }
 }
 
+// "pack12": the same payload with 1.5 bytes of column per entry, for pieces the piece walk takes four entries per
+// lane.  A piece is laid out as SLOTS in groups of four; lane l of the walk owns group l.
+//   slot 0 of a group: always a real entry, its tile-local column as a 15-bit absolute value (wc <= 32 767);
+//   slots 1-3: an 11-bit field d.  d <= PACK12_MAXGAP: the next real entry, column = previous column of the group + d;
+//              d == PACK12_PAD: a pad -- the slot goes to the tile's sink accumulator.
+// Slots are assigned greedily: an entry more than PACK12_MAXGAP columns behind its predecessor in the same group turns
+// that slot and the rest of the group into pads and opens the next group (at d = 0.01 about 0.02 such pads in all of
+// a 50k x 50k operand).  Pads behind the last real entry fill up the last group.
+// In memory, n = slot of the last real entry + 1 and G = ceil(n / 4):
+//   n doubles (a mid-piece pad holds +0.0; trailing pads have no value: the lane multiplies what follows into the sink),
+//   plane D, G dwords:      bits 0-14 the absolute column, 15-25 field 1, 26-31 the low 6 bits of field 2;
+//   plane H, G 16-bit words: bits 0-4 the high 5 bits of field 2, 5-15 field 3;
+// both planes together rounded up to 8 bytes, pieces on SMM_PACK_ALIGN units, desc = {first unit, n}.  Every load of
+// the walk is scalar base + lane * 4 / lane * 2: naturally aligned, no cross-lane decode, no per-piece metadata.
+// 6 bytes per group instead of 8: a piece of ~167 entries is 13 lines instead of 14.  The format is restated and
+// checked in plain Python in tests/pack12_restatement.py.
+constexpr int PACK_FMT_16 = 0, PACK_FMT_12 = 1;            // (NumericArgs::piece_fmt, the operand cache)
+constexpr int PACK12_PAD = 2047, PACK12_MAXGAP = 2046;
+// One thread per piece walks it in slot order: f(slot, column or -1 for a mid-piece pad, position in idx / val).
+// Returns n.
+template <typename F>
+__device__ __forceinline__ int pack12_walk(const int *__restrict__ idx, const int k0, const int k1, const int lo_c, F f)
+{
+    int slot = 0, prev = 0;
+    for (int k = k0; k < k1; ++k) {
+        const int c = idx[k] - lo_c;
+        if ((slot & 3) && c - prev > PACK12_MAXGAP)
+            for (; slot & 3; ++slot) f(slot, -1, k);
+        f(slot, c, k);
+        prev = c;
+        ++slot;
+    }
+    return slot;
+}
+__device__ __forceinline__ int pack12_units(const int n) {
+    const int g = (n + 3) >> 2;
+    return (n + ((6 * g + 7) >> 3) + (SMM_PACK_ALIGN - 1)) & ~(SMM_PACK_ALIGN - 1);
+}
+// per piece: units and n of pack12; stat[0] = longest n, stat[1] / stat[2] = the operand's units as 16-bit payload / pack12
+__global__ __launch_bounds__(256) void smm_pack12_count(int rows, int nct, int wc, const int *__restrict__ idx, const int *__restrict__ seg,
+                                                        int *__restrict__ units, int *__restrict__ n12, unsigned long long *__restrict__ stat)
+{
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int n = 0;
+    unsigned long long u16 = 0, u12 = 0;
+    if (gid < (int64_t)rows * nct) {
+        const int t = (int)(gid / rows), j = (int)(gid % rows);
+        const int *sp = seg + (size_t)j * (nct + 1) + t;
+        const int len = sp[1] - sp[0];
+        n = pack12_walk(idx, sp[0], sp[1], t * wc, [](int, int, int) {});
+        units[gid] = pack12_units(n);
+        n12[gid] = n;
+        u12 = (unsigned long long)pack12_units(n);
+        u16 = (unsigned long long)((len + ((len + 3) >> 2) + (SMM_PACK_ALIGN - 1)) & ~(SMM_PACK_ALIGN - 1));
+    }
+    int mx = n;
+    for (int o = 32; o > 0; o >>= 1) {
+        const int y = __shfl_xor(mx, o); mx = y > mx ? y : mx;
+        u16 += __shfl_xor(u16, o); u12 += __shfl_xor(u12, o);
+    }
+    if (lane_id() == 0 && mx > 0) {
+        atomicMax((unsigned long long *)stat, (unsigned long long)mx);
+        atomicAdd(stat + 1, u16); atomicAdd(stat + 2, u12);
+    }
+}
+__global__ __launch_bounds__(256) void smm_pack12_desc(int64_t cells, const int64_t *__restrict__ off, const int *__restrict__ n12,
+                                                       int2 *__restrict__ desc)
+{
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid < cells) desc[gid] = make_int2((int)off[gid], n12[gid]);
+}
+// One wave per piece, 64 entries at a time; writes every value slot (mid-piece pads: +0.0) and every field of both
+// planes (trailing pads included): nothing relies on what the buffer held.  A window starts at a group's slot 0, so its
+// slots depend on nothing before it; lane l takes entry l, slot = first slot + l, and every entry that comes more than
+// PACK12_MAXGAP behind its predecessor inside a group pushes itself and the lanes after it to the next group (a
+// wave-uniform loop over those entries: there are next to none).  The lane that holds a group's slot 0 builds the
+// group's two words from the three lanes after it, so only groups whose slot 0 sits in lanes 0..60 are written in this
+// window and the next one starts at the first group that was not.
+__global__ __launch_bounds__(256) void smm_pack12_fill(int rows, int nct, int wc, const int *__restrict__ idx, const double *__restrict__ val,
+                                                       const int *__restrict__ seg, const int2 *__restrict__ desc, double *__restrict__ pay)
+{
+    const int lane = lane_id();
+    const int wpb = blockDim.x / WAVE;
+    const int64_t cells = (int64_t)rows * nct;
+    for (int64_t cell = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); cell < cells; cell += (int64_t)gridDim.x * wpb) {
+        const int t = (int)(cell / rows), j = (int)(cell % rows);
+        const int *sp = seg + (size_t)j * (nct + 1) + t;
+        const int k0 = sp[0], k1 = sp[1], lo_c = t * wc;
+        const int2 d = desc[cell];
+        const int n = d.y, ng = (d.y + 3) >> 2;
+        if (n <= 0 || k1 <= k0) continue;
+        double *__restrict__ v = pay + d.x;
+        unsigned *__restrict__ pd = (unsigned *)(pay + d.x + n);
+        unsigned short *__restrict__ ph = (unsigned short *)(pd + ng);
+        int e0 = k0, s0 = 0;                                // first entry and first slot of the window (a group's slot 0)
+        while (e0 < k1) {
+            const int k = e0 + lane;
+            const bool valid = k < k1;
+            const int c = valid ? idx[k] - lo_c : 0;
+            const double x = valid ? val[k] : 0.0;
+            const int prev = __shfl_up(c, 1);
+            int slot = s0 + lane;
+            unsigned long long big = __ballot(valid && lane > 0 && c - prev > PACK12_MAXGAP);
+            while (big) {
+                const int l = (int)__builtin_ctzll(big);
+                big &= big - 1ull;
+                const int s = rl(slot, l);
+                if ((s & 3) && lane >= l) slot += 4 - (s & 3);
+            }
+            const bool last = e0 + WAVE >= k1;
+            const bool head = valid && (slot & 3) == 0;
+            const unsigned long long late = __ballot(head) & ~((1ull << 61) - 1ull);
+            const int L = last ? WAVE : (late ? (int)__builtin_ctzll(late) : WAVE);      // entries written in this window
+            // the three lanes behind a group's slot 0: members of the group while their slots follow on
+            const int c1 = __shfl_down(c, 1), c2 = __shfl_down(c, 2), c3 = __shfl_down(c, 3);
+            const int t1 = __shfl_down(slot, 1), t2 = __shfl_down(slot, 2), t3 = __shfl_down(slot, 3);
+            const bool m1 = lane + 1 < WAVE && k + 1 < k1 && t1 == slot + 1;
+            const bool m2 = m1 && lane + 2 < WAVE && k + 2 < k1 && t2 == slot + 2;
+            const bool m3 = m2 && lane + 3 < WAVE && k + 3 < k1 && t3 == slot + 3;
+            if (lane < L && valid && slot < n) v[slot] = x;
+            if (lane < L && head && (slot >> 2) < ng) {
+                const unsigned f1 = m1 ? (unsigned)(c1 - c) : (unsigned)PACK12_PAD;
+                const unsigned f2 = m2 ? (unsigned)(c2 - c1) : (unsigned)PACK12_PAD;
+                const unsigned f3 = m3 ? (unsigned)(c3 - c2) : (unsigned)PACK12_PAD;
+                pd[slot >> 2] = (unsigned)c | (f1 << 15) | ((f2 & 63u) << 26);
+                ph[slot >> 2] = (unsigned short)((f2 >> 6) | (f3 << 5));
+                const int real = 1 + (m1 ? 1 : 0) + (m2 ? 1 : 0) + (m3 ? 1 : 0);
+                if (k + real < k1)                                                      // an entry follows: the pads are mid-piece
+                    for (int q = real; q < 4; ++q)
+                        if (slot + q < n) v[slot + q] = 0.0;
+            }
+            // (L == 64 before the last window: lane 60 opened a group and lanes 61..63 filled it)
+            s0 = L < WAVE ? rl(slot, L) : rl(slot, WAVE - 1) + 1;
+            e0 += L;
+        }
+    }
+}
+
 // 16-bit copy of an operand's column indices (operands with < 65 535 columns): the symbolic phase gathers
 // these 2 bytes per product instead of 4 -- half of its fabric traffic.
 __global__ __launch_bounds__(256) void smm_idx16(int nnz, const int *__restrict__ idx, unsigned short *__restrict__ out)
@@ -1445,6 +1583,7 @@ struct NumericArgs {
     const short *b_loc;             // tile-local columns (smm_loc16): the exact walk
     const int2 *tdesc; const double *tpay; int rowsB;   // packed tile-major payload (smm_pack_*): the shared-tile walk
     int piece_epl;                  // 2 / 4: every piece of the payload has <= 128 / 256 entries -> smm_accumulate_pieces; 0: chunk walk
+    int piece_fmt;                  // 0: 16-bit tile-local columns; 1: pack12 planes (piece_epl == 4, CSR output only)
     const int *seg;                 // [rowsB][n_ft+1]
     int kmax;                       // last valid position of b_loc / b_val (exact walk: lanes past a stream's end read it)
     const int *dummy_idx;           // one int  = -1   (read by inactive lanes; its low half is the int16 -1)
@@ -1719,18 +1858,22 @@ __device__ __forceinline__ void wait_vm_n(int n) {
     }
 #undef SMM_W
 }
-template <bool SYM, int NW, int EPL, int U>
+// FMT 1 (EPL 4 only): the piece's columns are pack12 planes (see smm_pack12_fill) -- four loads per piece, the columns
+// decoded per lane: one mask, three field extracts, three adds, three pad selects.
+template <bool SYM, int NW, int EPL, int U, int FMT = 0>
 __device__ __forceinline__ void smm_accumulate_pieces(const NumericArgs &A, double *__restrict__ acc, const int thresh,
                                                       const int a0, const int a1, const int tc, const int wave)
 {
     static_assert(EPL == 2 || EPL == 4, "entries per lane");
-    constexpr int LPP = EPL == 4 ? 3 : 2;                   // loads per piece
+    static_assert(FMT == 0 || EPL == 4, "pack12 pieces are walked four entries per lane");
+    constexpr int LPP = FMT ? 4 : (EPL == 4 ? 3 : 2);       // loads per piece
     const int lane = lane_id();
     const int2 *__restrict__ desc = A.tdesc + (size_t)tc * A.rowsB;
     const double *__restrict__ pay = A.tpay;
     const unsigned acc_a = lds_addr(acc);
     const int sink = (A.wc + 1) & ~1;
-    const int voff = lane * (EPL * 8), coff = lane * (EPL * 2);
+    const int voff = lane * (EPL * 8), coff = FMT ? lane * 4 : lane * (EPL * 2);
+    const int hoff = lane * 2;                              // (pack12: plane D at coff, plane H at hoff)
     for (int rb = a0; rb < a1; rb += NW * WAVE) {
         const int e = rb + wave + NW * lane;
         const bool ev = e < a1;
@@ -1757,7 +1900,17 @@ __device__ __forceinline__ void smm_accumulate_pieces(const NumericArgs &A, doub
                 const unsigned long long lm = mk[u] | 1ull;
                 const double *vb = pay + sp;
                 const void *cb = (const void *)(pay + sp + n);
-                if constexpr (EPL == 4)
+                if constexpr (FMT == 1) {
+                    const int hoff_u = hoff + 4 * nl;       // plane H behind the G = nl dwords of plane D (a vector offset: one scalar base less per piece)
+                    asm volatile("s_mov_b64 exec, %9\n\t"
+                                 "global_load_dwordx4 %0, %4, %7\n\t"
+                                 "global_load_dwordx4 %1, %4, %7 offset:16\n\t"
+                                 "global_load_dword %2, %5, %8\n\t"
+                                 "global_load_ushort %3, %6, %8\n\t"
+                                 "s_mov_b64 exec, -1"
+                                 : "=&v"(v0[u]), "=&v"(v1[u]), "=&v"(cc[u].x), "=&v"(cc[u].y)
+                                 : "v"(voff), "v"(coff), "v"(hoff_u), "s"(vb), "s"(cb), "s"(lm) : "memory");
+                } else if constexpr (EPL == 4)
                     asm volatile("s_mov_b64 exec, %7\n\t"
                                  "global_load_dwordx4 %0, %3, %5\n\t"
                                  "global_load_dwordx4 %1, %3, %5 offset:16\n\t"
@@ -1776,10 +1929,29 @@ __device__ __forceinline__ void smm_accumulate_pieces(const NumericArgs &A, doub
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 wait_vm_n(LPP * (U - 1 - u));
-                if constexpr (EPL == 4) asm volatile("" : "+v"(v0[u]), "+v"(v1[u]), "+v"(cc[u]));
+                if constexpr (FMT == 1) asm volatile("" : "+v"(v0[u]), "+v"(v1[u]), "+v"(cc[u].x), "+v"(cc[u].y));
+                else if constexpr (EPL == 4) asm volatile("" : "+v"(v0[u]), "+v"(v1[u]), "+v"(cc[u]));
                 else asm volatile("" : "+v"(v0[u]), "+v"(cc[u].x));
                 const int i = i0 + u < cnt ? i0 + u : cnt - 1;
                 const double a = rl(av, i);
+                if constexpr (FMT == 1) {
+                    const unsigned dw = (unsigned)cc[u].x, hw = (unsigned)cc[u].y & 0xffffu;
+                    const unsigned f1 = (dw >> 15) & 0x7ffu, f2 = (dw >> 26) | ((hw & 31u) << 6), f3 = hw >> 5;
+                    int c0 = (int)(dw & 0x7fffu);
+                    int c1 = c0 + (int)f1, c2 = c1 + (int)f2, c3 = c2 + (int)f3;    // (behind a pad the sums mean nothing: every later field is a pad too)
+                    c1 = f1 == (unsigned)PACK12_PAD ? sink : c1;
+                    c2 = f2 == (unsigned)PACK12_PAD ? sink : c2;
+                    c3 = f3 == (unsigned)PACK12_PAD ? sink : c3;
+                    if (SYM) { c0 = c0 >= thresh ? c0 : sink; c1 = c1 >= thresh ? c1 : sink; c2 = c2 >= thresh ? c2 : sink; c3 = c3 >= thresh ? c3 : sink; }
+                    const unsigned d0 = acc_a + 8u * (unsigned)c0, d1 = acc_a + 8u * (unsigned)c1;
+                    const unsigned d2 = acc_a + 8u * (unsigned)c2, d3 = acc_a + 8u * (unsigned)c3;
+                    const double p0 = a * v0[u].x, p1 = a * v0[u].y, p2 = a * v1[u].x, p3 = a * v1[u].y;
+                    asm volatile("s_mov_b64 exec, %8\n\t"
+                                 "ds_add_f64 %0, %1\n\tds_add_f64 %2, %3\n\tds_add_f64 %4, %5\n\tds_add_f64 %6, %7\n\t"
+                                 "s_mov_b64 exec, -1"
+                                 :: "v"(d0), "v"(p0), "v"(d1), "v"(p1), "v"(d2), "v"(p2), "v"(d3), "v"(p3), "s"(mk[u]) : "memory");
+                    continue;
+                }
                 int c0 = (int)(short)(cc[u].x & 0xffff), c1 = cc[u].x >> 16;
                 if (SYM) { c0 = c0 >= thresh ? c0 : sink; c1 = c1 >= thresh ? c1 : sink; }
                 const unsigned d0 = acc_a + 8u * (unsigned)c0, d1 = acc_a + 8u * (unsigned)c1;
@@ -1915,6 +2087,7 @@ __device__ __forceinline__ void smm_numeric_unit(const NumericArgs &A, double *_
                 smm_accumulate<SYM>(A, acc, scr + wave, (double *)(scr + NW), thresh, a0, a1, tc * NW + wave);
                 wait_lgkm0();                   // its hand-issued ds_add's (the compiler does not count them)
             }
+            else if (OUT == OUT_SPARSE && A.piece_epl == 4 && A.piece_fmt == 1) smm_accumulate_pieces<SYM, NW, 4, SMM_PIECE_U_SPARSE, 1>(A, acc, thresh, a0, a1, tc, wave);
             else if (A.piece_epl == 4) smm_accumulate_pieces<SYM, NW, 4, (OUT == OUT_DENSE ? SMM_PIECE_U_DENSE : SMM_PIECE_U_SPARSE)>(A, acc, thresh, a0, a1, tc, wave);
             else if (A.piece_epl == 2) smm_accumulate_pieces<SYM, NW, 2, (OUT == OUT_DENSE ? SMM_PIECE_U_DENSE : SMM_PIECE_U_SPARSE)>(A, acc, thresh, a0, a1, tc, wave);
             else       smm_accumulate_shared<SYM, NW, (OUT == OUT_DENSE ? CH_UNROLL_DENSE : CH_UNROLL_SPARSE)>(A, acc, lo_c, thresh, a0, a1, tc, wave);

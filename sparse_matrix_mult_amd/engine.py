@@ -106,6 +106,11 @@ class Context:
         """Triple product, stage 2: the ring kernel of round 4 (True) or the chunk kernel (False, default)."""
         check(self.lib, self.lib.smm_ctx_tune_stage2(self.handle, 1 if ring else 0))
 
+    def tune_pack(self, mode=1):
+        """B's packed payload for the CSR product's piece walk: 1 = 1.5-byte columns ("pack12") where smaller (default),
+        0 = 16-bit columns always, 2 = pack12 wherever the four-entries-per-lane walk applies."""
+        check(self.lib, self.lib.smm_ctx_tune_pack(self.handle, int(mode)))
+
     def exact_selftest(self, inject_fault=False):
         """Run the SMM_EXACT guard now (every context runs it by itself before its first exact product):
         raises SmmError (code SMM_ERR_UNSUPPORTED) where the device does not add same-address lanes of one
