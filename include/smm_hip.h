@@ -463,6 +463,59 @@ int  smm_innovation_solve_host(smm_ctx *ctx, smm_csr *h, smm_csr *q, smm_csr *r,
                                int64_t ldb, double *x, int64_t ldx, double tol, int64_t maxiter, int *iterations,
                                int *status, double *residual_sq, double *rhs_sq);
 
+/* ------------------------------------------------------------------ Kronecker operand Q = D (x) E
+ * The prior covariance of a space-time inverse problem: a temporal factor D (p x p') times a spatial factor E (r x r').
+ * D (x) E is (p r) x (p' r'); row t r + j is the pair (t, j), column t' r' + j' the pair (t', j').  Both factors may be any
+ * legal CSR (unsorted rows, repeated columns, empty rows).  p r and p' r' must be < 2^31 - 1 (SMM_ERR_INVALID) in every call
+ * of this section.
+ *
+ * smm_kron_build: the explicit matrix as a new operand owned by the caller (smm_csr_destroy), as smm_taper_build returns one.
+ *   Row (t, j) holds, for a over row t of D in stored order and b over row j of E in stored order, column
+ *   D.idx[a] r' + E.idx[b] with value D.val[a] * E.val[b]: one rounded multiply (inf * 0 is stored as NaN; explicit zeros
+ *   stay entries).  One mode: there is no SMM_EXACT flag and no other order.  The row pointer is the closed form
+ *   ptr[t r + j] = D.ptr[t] nnz(E) + len_D(t) E.ptr[j]: no count pass, no scan, no atomics.  For canonical D and E the result
+ *   is canonical (smm_csr_is_canonical) and its three arrays are those of scipy.sparse.kron(D, E, format="csr"), bit for bit.
+ *   Refused before any allocation or launch: a dimension as above (SMM_ERR_INVALID); nnz(D) nnz(E) > 2^31 - 2
+ *   (SMM_ERR_OVERFLOW: operand row pointers are int32 -- such a Q is used through its factors, below).  A factor without
+ *   entries gives an operand without entries and no launch.
+ *
+ * smm_kron_apply: Y = (D (x) E) X without forming it.  X: (p' r') x k, Y: (p r) x k, row-major float64 with leading
+ *   dimensions ldx, ldy >= k, 64-bit offsets, no overlap of X and Y, every element of Y's k columns written and its padding
+ *   not, k = 0 valid -- all as smm_spmm.  The order is part of the contract, E first:
+ *       U[(t', j), :] = sum over row j of E, in stored order b, of E.val[b] * X[(t', E.idx[b]), :]      for every t' < p'
+ *       Y[(t, j), :]  = sum over row t of D, in stored order a, of D.val[a] * U[(D.idx[a], j), :]
+ *   SMM_EXACT (the only flag): every element starts at +0.0 and adds one rounded product at a time -- scipy's
+ *   U[t'] = E @ X[t'] followed by D @ U.reshape(p', r k), bit for bit, for any legal CSR factors and any row length.  This
+ *   is deliberately NOT the bits of scipy.sparse.kron(D, E) @ X, whose association differs (the two differ in the last bit).
+ *   Without it: the same order with fused multiply-adds, within 1e-10 ((|D| (x) |E|) |X|)[i, c] of the exact value.  No float
+ *   atomics, and in both kernels a lane owns its elements of U and Y for every k, k = 1 included: two runs give the same
+ *   bits, and neither the column blocking below nor k can change a bit, in either mode.
+ *   A pair that a factor does not store is never multiplied (an inf in X[(t', j'), :] reaches Y[(t, j), :] only through a
+ *   stored D[t, t'] and a stored E[j, j']).
+ *   U is a pool temporary of (p' r) x kb: X is taken in blocks of kb columns when U exceeds the apply budget
+ *   (smm_ctx_tune_spmm).  There is no transpose flag: (D (x) E)^T = D^T (x) E^T, so callers pass transposed factors.
+ *
+ * smm_triple_apply_kron / smm_innovation_solve_kron: smm_triple_apply / smm_innovation_solve with Q = D (x) E (D and E square,
+ *   p r == H.cols, else SMM_ERR_INVALID) and "Q Z1" replaced by the apply above; everything else -- flags, buffers, the CG
+ *   recipe, the outputs -- is that call's contract.  The column block counts three K x kb intermediates (H^T P, U, Q H^T P)
+ *   where the CSR form counts two.  The factors' kernels bin no rows and nothing new synchronises with the host inside a CG
+ *   iteration.  Under SMM_EXACT blocking changes no bit; in default mode the k = 1 caveat of smm_innovation_solve remains,
+ *   through H, H^T and R only. */
+int  smm_kron_build(smm_ctx *ctx, smm_csr *d, smm_csr *e, smm_csr **out);
+int  smm_kron_apply(smm_ctx *ctx, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *d_x, int64_t ldx, double *d_y, int64_t ldy);
+/* Same with host X and Y (uploaded / downloaded through pool temporaries). */
+int  smm_kron_apply_host(smm_ctx *ctx, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy);
+int  smm_triple_apply_kron(smm_ctx *ctx, smm_csr *h, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *d_x, int64_t ldx,
+                           double *d_y, int64_t ldy);
+int  smm_triple_apply_kron_host(smm_ctx *ctx, smm_csr *h, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *x, int64_t ldx,
+                                double *y, int64_t ldy);
+int  smm_innovation_solve_kron(smm_ctx *ctx, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k, const double *d_b,
+                               int64_t ldb, double *d_x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
+                               double *residual_sq, double *rhs_sq);
+int  smm_innovation_solve_kron_host(smm_ctx *ctx, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k, const double *b,
+                                    int64_t ldb, double *x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
+                                    double *residual_sq, double *rhs_sq);
+
 /* ------------------------------------------------------------------ device memory helpers
  * (so that hosts without torch can still hold results in HBM) */
 int  smm_device_malloc(smm_ctx *ctx, int64_t bytes, void **d_ptr);

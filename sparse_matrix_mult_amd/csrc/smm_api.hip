@@ -8,6 +8,7 @@
 #include "smm_triple_sparse.hpp"
 #include "smm_masked.hpp"
 #include "smm_spmm.hpp"
+#include "smm_kron.hpp"
 #include "smm_cg.hpp"
 #include "smm_sddmm.hpp"
 #include "smm_taper.hpp"
@@ -3546,22 +3547,188 @@ extern "C" int smm_spmm_host(smm_ctx *c, smm_csr *a, int flags, int64_t k, const
     return download_rows(c, y, dy, m, k, ldy);
 }
 
-// Y = H (Q (H^T X)): H^T X through H's cached transpose, two pool intermediates of K x kb, X taken in column blocks of kb
-// columns so that both fit the context's apply budget (columns are independent: blocking changes no bit).
-static int triple_apply_impl(smm_ctx *c, smm_csr *h, smm_csr *q, bool exact, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy)
+// ------------------------------------------------------------------------------ Kronecker operand Q = D (x) E
+// Kernels: smm_kron.hpp; the contract is in include/smm_hip.h.
+static KronArgs kron_args(smm_ctx *c, const smm_csr *d, const smm_csr *e)
+{
+    KronArgs A{};
+    A.p = (int)d->rows; A.pc = (int)d->cols; A.r = (int)e->rows; A.rc = (int)e->cols;
+    A.nnz_d = (int)d->nnz; A.nnz_e = (int)e->nnz;
+    A.dptr = d->ptr; A.didx = d->idx; A.dval = d->val;
+    A.eptr = e->ptr; A.eidx = e->idx; A.eval = e->val;
+    A.err = c->d_err;
+    return A;
+}
+
+// The two factors of a call: present, of this context, validated, with a product whose dimensions fit an operand's.
+static int kron_factors(smm_ctx *c, smm_csr *d, smm_csr *e, const char *where)
+{
+    if (!d || !e) return fail(SMM_ERR_INVALID, "%s: NULL factor", where);
+    if (d->ctx != c || e->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
+    if (d->rows * e->rows >= INT32_MAX || d->cols * e->cols >= INT32_MAX)
+        return fail(SMM_ERR_INVALID, "%s: D (x) E would be %lld x %lld, dimensions must be < 2^31 - 1", where,
+                    (long long)(d->rows * e->rows), (long long)(d->cols * e->cols));
+    return SMM_OK;
+}
+
+extern "C" int smm_kron_build(smm_ctx *c, smm_csr *d, smm_csr *e, smm_csr **out)
+{
+    if (!out) return fail(SMM_ERR_INVALID, "smm_kron_build: out is NULL");
+    *out = nullptr;
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(kron_factors(c, d, e, "smm_kron_build"));
+    const int64_t rows = d->rows * e->rows, cols = d->cols * e->cols;
+    if (d->nnz > 0 && e->nnz > (int64_t)(INT32_MAX - 1) / d->nnz)
+        return fail(SMM_ERR_OVERFLOW, "smm_kron_build: nnz(D) * nnz(E) = %lld * %lld entries do not fit an operand (int32 row pointers, "
+                                      "nnz <= 2^31 - 2); use the factors through smm_kron_apply", (long long)d->nnz, (long long)e->nnz);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(validate(c, d));
+    CHK(validate(c, e));
+    CsrPtr m;
+    if (d->nnz == 0 || e->nnz == 0) {
+        CHK(empty_csr(c, rows, cols, &m));
+        *out = m.release();
+        return SMM_OK;
+    }
+    m = new_csr(c, rows, cols, d->nnz * e->nnz);
+    CHK(alloc_owned(c, m.get(), "the Kronecker operand"));
+    KronArgs A = kron_args(c, d, e);
+    A.optr = m->own_ptr; A.oidx = m->own_idx; A.oval = m->own_val;
+    const int64_t cap = (int64_t)c->n_cu * 64;
+    if (m->nnz / rows < 128) {                                   // short rows: 16 lanes (64 entries a pass), four rows per wave
+        LAUNCH(c, "smm_kron_fill", smm_kron_fill<16>, std::max<int64_t>(1, std::min<int64_t>((rows + 15) / 16, cap)), 256, 0, A);
+    } else {
+        LAUNCH(c, "smm_kron_fill", smm_kron_fill<64>, std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, cap)), 256, 0, A);
+    }
+    LAUNCH_CHECK();
+    CHK(take_plan_error(c, "smm_kron_build"));
+    CHK(validate(c, m.get()));                                   // (flags of the new operand: canonical iff both factors are)
+    *out = m.release();
+    return SMM_OK;
+}
+
+// Y = (D (x) E) X for one column block on the context's stream, through u ((pc * r) x k, packed): the E-step and the
+// D-step, nothing binned, nothing synchronised.  Every element of Y's k columns is written.
+static int kron_apply_launch(smm_ctx *c, const smm_csr *d, const smm_csr *e, bool exact, int64_t k, const double *x, int64_t ldx, double *u,
+                             double *y, int64_t ldy)
+{
+    if (k == 0) return SMM_OK;
+    KronArgs A = kron_args(c, d, e);
+    A.k = k; A.ldx = ldx; A.ldy = ldy; A.x = x; A.u = u; A.y = y;
+    const int64_t cap = (int64_t)c->n_cu * 32;
+    if ((int64_t)A.pc * A.r > 0) {
+        const int vec = (k % 2 == 0 && ldx % 2 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)u % 16 == 0) ? 2 : 1;
+        const int64_t w = (int64_t)A.pc * k;                     // virtual columns of a row of E
+        const int g = w <= 4 * vec ? 4 : (w <= 16 * vec ? 16 : WAVE);
+        const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(((int64_t)A.r + 4 * (WAVE / g) - 1) / (4 * (WAVE / g)), cap));
+#define KRON_INNER(G_, V_)                                                                                                    \
+    if (g == G_ && vec == V_) {                                                                                               \
+        if (exact) LAUNCH(c, "smm_kron_inner", (smm_kron_inner<G_, V_, true>), grid, 256, 0, A);                              \
+        else       LAUNCH(c, "smm_kron_inner", (smm_kron_inner<G_, V_, false>), grid, 256, 0, A);                             \
+    }
+        KRON_INNER(4, 1) KRON_INNER(16, 1) KRON_INNER(64, 1) KRON_INNER(4, 2) KRON_INNER(16, 2) KRON_INNER(64, 2)
+#undef KRON_INNER
+    }
+    if ((int64_t)A.p * A.r > 0) {
+        const int vec = (k % 2 == 0 && ldy % 2 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)u % 16 == 0) ? 2 : 1;
+        const int64_t chunks = ((int64_t)A.r * k + 256 * vec - 1) / (256 * vec);
+        const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((int64_t)A.p * chunks, cap * 8));
+        if (vec == 2) { if (exact) LAUNCH(c, "smm_kron_outer", (smm_kron_outer<2, true>), grid, 256, 0, A, chunks);
+                        else       LAUNCH(c, "smm_kron_outer", (smm_kron_outer<2, false>), grid, 256, 0, A, chunks); }
+        else          { if (exact) LAUNCH(c, "smm_kron_outer", (smm_kron_outer<1, true>), grid, 256, 0, A, chunks);
+                        else       LAUNCH(c, "smm_kron_outer", (smm_kron_outer<1, false>), grid, 256, 0, A, chunks); }
+    }
+    LAUNCH_CHECK();
+    return SMM_OK;
+}
+
+// Y = (D (x) E) X, X taken in column blocks whose U fits the context's apply budget (lanes own elements in both kernels,
+// so the blocking changes no bit in either mode).
+static int kron_apply_impl(smm_ctx *c, const smm_csr *d, const smm_csr *e, bool exact, int64_t k, const double *x, int64_t ldx, double *y,
+                           int64_t ldy)
+{
+    const int64_t m = d->rows * e->rows, urows = d->cols * e->rows;
+    if (m == 0 || k == 0) return SMM_OK;
+    const int64_t kb = std::max<int64_t>(1, std::min<int64_t>(k, c->apply_budget / std::max<int64_t>(urows * (int64_t)sizeof(double), 1)));
+    PoolBuf<double> u(c);
+    CHK(u.alloc((size_t)std::max<int64_t>(urows * kb, 1)));
+    for (int64_t j0 = 0; j0 < k; j0 += kb) {
+        const int64_t b = std::min(kb, k - j0);
+        CHK(kron_apply_launch(c, d, e, exact, b, x + j0, ldx, u, y + j0, ldy));
+    }
+    return SMM_OK;
+}
+
+static int kron_apply_args(smm_ctx *c, smm_csr *d, smm_csr *e, int flags, int64_t k, int64_t ldx, int64_t ldy, const char *where)
+{
+    if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call ((D (x) E)^T is D^T (x) E^T: pass "
+                                                         "transposed factors)", where);
+    CHK(kron_factors(c, d, e, where));
+    if (k < 0 || ldx < k || ldy < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldx, ldy (k %lld, ldx %lld, ldy %lld)", where,
+                                                 (long long)k, (long long)ldx, (long long)ldy);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(validate(c, d));
+    CHK(validate(c, e));
+    return SMM_OK;
+}
+
+extern "C" int smm_kron_apply(smm_ctx *c, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *d_x, int64_t ldx, double *d_y,
+                              int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(kron_apply_args(c, d, e, flags, k, ldx, ldy, "smm_kron_apply"));
+    CHK(spmm_buffers(d->rows * e->rows, d->cols * e->cols, k, d_x, ldx, d_y, ldy, "smm_kron_apply"));
+    CHK(kron_apply_impl(c, d, e, (flags & SMM_EXACT) != 0, k, d_x, ldx, d_y, ldy));
+    return take_plan_error(c, "smm_kron_apply");
+}
+
+extern "C" int smm_kron_apply_host(smm_ctx *c, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *x, int64_t ldx, double *y,
+                                   int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(kron_apply_args(c, d, e, flags, k, ldx, ldy, "smm_kron_apply_host"));
+    const int64_t m = d->rows * e->rows, kx = d->cols * e->cols;
+    if ((span_bytes(kx, k, ldx) > 0 && !x) || (span_bytes(m, k, ldy) > 0 && !y)) return fail(SMM_ERR_INVALID, "smm_kron_apply_host: X or Y is NULL");
+    if (m == 0 || k == 0) return SMM_OK;
+    PoolBuf<double> dx(c), dy(c);
+    CHK(dx.alloc((size_t)std::max<int64_t>(kx * k, 1)));
+    CHK(dy.alloc((size_t)(m * k)));
+    CHK(upload_rows(c, dx, x, kx, k, ldx));
+    CHK(kron_apply_impl(c, d, e, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
+    CHK(take_plan_error(c, "smm_kron_apply_host"));
+    return download_rows(c, y, dy, m, k, ldy);
+}
+
+// The K x K operator in the middle of H Q H^T as the host code sees it: one CSR, or a pair of factors D (x) E (square, with
+// p * r == K) that is applied without being formed.
+struct QOp {
+    const smm_csr *q = nullptr, *d = nullptr, *e = nullptr;
+    bool pair() const { return d != nullptr; }
+};
+
+// Y = H (Q (H^T X)): H^T X through H's cached transpose, two pool intermediates of K x kb (three when Q is a pair of factors:
+// the U of its E-step), X taken in column blocks of kb columns so that they fit the context's apply budget (columns are
+// independent: blocking changes no bit).
+static int triple_apply_impl(smm_ctx *c, smm_csr *h, const QOp &q, bool exact, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy)
 {
     const int64_t n = h->rows, K = h->cols;
     if (n == 0 || k == 0) return SMM_OK;
     const smm_csr *ht = nullptr;
     CHK(spmm_op(c, h, true, &ht));
-    const int64_t kb = std::max<int64_t>(1, std::min<int64_t>(k, c->apply_budget / std::max<int64_t>(2 * K * (int64_t)sizeof(double), 1)));
-    PoolBuf<double> z1(c), z2(c);
+    const int64_t nz = q.pair() ? 3 : 2;
+    const int64_t kb = std::max<int64_t>(1, std::min<int64_t>(k, c->apply_budget / std::max<int64_t>(nz * K * (int64_t)sizeof(double), 1)));
+    PoolBuf<double> z1(c), z2(c), u(c);
     CHK(z1.alloc((size_t)std::max<int64_t>(K * kb, 1)));
     CHK(z2.alloc((size_t)std::max<int64_t>(K * kb, 1)));
+    if (q.pair()) CHK(u.alloc((size_t)std::max<int64_t>(K * kb, 1)));
     for (int64_t j0 = 0; j0 < k; j0 += kb) {
         const int64_t b = std::min(kb, k - j0);
         CHK(spmm_impl(c, ht, exact, b, x + j0, ldx, z1, b));      // Z1 = H^T X[:, j0 .. j0 + b)
-        CHK(spmm_impl(c, q, exact, b, z1, b, z2, b));             // Z2 = Q Z1
+        if (q.pair()) CHK(kron_apply_launch(c, q.d, q.e, exact, b, z1, b, u, z2, b));
+        else          CHK(spmm_impl(c, q.q, exact, b, z1, b, z2, b));             // Z2 = Q Z1
         CHK(spmm_impl(c, h, exact, b, z2, b, y + j0, ldy));       // Y[:, j0 .. j0 + b) = H Z2
     }
     return SMM_OK;
@@ -3584,7 +3751,7 @@ extern "C" int smm_triple_apply(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, i
     CTX_LOCK(c);
     CHK(triple_apply_args(c, h, q, flags, k, ldx, ldy, "smm_triple_apply"));
     CHK(spmm_buffers(h->rows, h->rows, k, d_x, ldx, d_y, ldy, "smm_triple_apply"));
-    CHK(triple_apply_impl(c, h, q, (flags & SMM_EXACT) != 0, k, d_x, ldx, d_y, ldy));
+    CHK(triple_apply_impl(c, h, QOp{q}, (flags & SMM_EXACT) != 0, k, d_x, ldx, d_y, ldy));
     return take_plan_error(c, "smm_triple_apply");
 }
 
@@ -3601,8 +3768,65 @@ extern "C" int smm_triple_apply_host(smm_ctx *c, smm_csr *h, smm_csr *q, int fla
     CHK(dx.alloc((size_t)(n * k)));
     CHK(dy.alloc((size_t)(n * k)));
     CHK(upload_rows(c, dx, x, n, k, ldx));
-    CHK(triple_apply_impl(c, h, q, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
+    CHK(triple_apply_impl(c, h, QOp{q}, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
     CHK(take_plan_error(c, "smm_triple_apply_host"));
+    return download_rows(c, y, dy, n, k, ldy);
+}
+
+// H and the factors of Q = D (x) E: D and E square with p * r == H.cols.
+static int kron_q_args(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, const char *where)
+{
+    if (!c || !h) return fail(SMM_ERR_INVALID, "%s: NULL argument", where);
+    if (h->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
+    CHK(kron_factors(c, d, e, where));
+    if (d->rows != d->cols || e->rows != e->cols)
+        return fail(SMM_ERR_INVALID, "%s: D and E must be square, got %lld x %lld and %lld x %lld", where, (long long)d->rows,
+                    (long long)d->cols, (long long)e->rows, (long long)e->cols);
+    if (d->rows * e->rows != h->cols)
+        return fail(SMM_ERR_INVALID, "Matrix dimensions are incompatible for multiplication (%lld x %lld times (%lld * %lld) squared)",
+                    (long long)h->rows, (long long)h->cols, (long long)d->rows, (long long)e->rows);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(validate(c, h));
+    CHK(validate(c, d));
+    CHK(validate(c, e));
+    return SMM_OK;
+}
+
+static int triple_apply_kron_args(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, int flags, int64_t k, int64_t ldx, int64_t ldy, const char *where)
+{
+    if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call", where);
+    CHK(kron_q_args(c, h, d, e, where));
+    if (k < 0 || ldx < k || ldy < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldx, ldy (k %lld, ldx %lld, ldy %lld)", where,
+                                                 (long long)k, (long long)ldx, (long long)ldy);
+    return SMM_OK;
+}
+
+extern "C" int smm_triple_apply_kron(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *d_x, int64_t ldx,
+                                     double *d_y, int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(triple_apply_kron_args(c, h, d, e, flags, k, ldx, ldy, "smm_triple_apply_kron"));
+    CHK(spmm_buffers(h->rows, h->rows, k, d_x, ldx, d_y, ldy, "smm_triple_apply_kron"));
+    CHK(triple_apply_impl(c, h, QOp{nullptr, d, e}, (flags & SMM_EXACT) != 0, k, d_x, ldx, d_y, ldy));
+    return take_plan_error(c, "smm_triple_apply_kron");
+}
+
+extern "C" int smm_triple_apply_kron_host(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *x, int64_t ldx,
+                                          double *y, int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(triple_apply_kron_args(c, h, d, e, flags, k, ldx, ldy, "smm_triple_apply_kron_host"));
+    const int64_t n = h->rows;
+    if (span_bytes(n, k, std::max(ldx, ldy)) > 0 && (!x || !y)) return fail(SMM_ERR_INVALID, "smm_triple_apply_kron_host: X or Y is NULL");
+    if (n == 0 || k == 0) return SMM_OK;
+    PoolBuf<double> dx(c), dy(c);
+    CHK(dx.alloc((size_t)(n * k)));
+    CHK(dy.alloc((size_t)(n * k)));
+    CHK(upload_rows(c, dx, x, n, k, ldx));
+    CHK(triple_apply_impl(c, h, QOp{nullptr, d, e}, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
+    CHK(take_plan_error(c, "smm_triple_apply_kron_host"));
     return download_rows(c, y, dy, n, k, ldy);
 }
 
@@ -3721,15 +3945,15 @@ static int cg_host_words(smm_ctx *c)
 // One column block of the solve (smm_cg.hpp; the contract is in include/smm_hip.h).  b / x point at the block's first column.
 // The host enqueues iteration it, then waits for the live count that iteration it - 1 left: the device always has one
 // iteration queued, and at most one runs after the last column froze -- on frozen columns, which no kernel writes.
-static int cg_block(smm_ctx *c, const smm_csr *ht, const smm_csr *q, const smm_csr *h, const smm_csr *r, bool exact, int64_t k,
+static int cg_block(smm_ctx *c, const smm_csr *ht, const QOp &q, const smm_csr *h, const smm_csr *r, bool exact, int64_t k,
                     const double *b, int64_t ldb, double *x, int64_t ldx, double tol, int64_t maxiter, double *rv, double *pv, double *wv,
-                    double *rpv, double *z1, double *z2, double *part, double *sc, int *iterations, int *status, double *residual_sq,
-                    double *rhs_sq)
+                    double *rpv, double *z1, double *z2, double *zu, double *part, double *sc, int *iterations, int *status,
+                    double *residual_sq, double *rhs_sq)
 {
     const int64_t n = h->rows;
     ClassLists bht(c), bq(c), bh(c), br(c);
     CHK(spmm_bin(c, ht, k, bht));
-    CHK(spmm_bin(c, q, k, bq));
+    if (!q.pair()) CHK(spmm_bin(c, q.q, k, bq));                  // (the kernels of a pair of factors bin nothing)
     CHK(spmm_bin(c, h, k, bh));
     if (r) CHK(spmm_bin(c, r, k, br));
     int *st = reinterpret_cast<int *>(sc + CG_NSC * k);
@@ -3759,7 +3983,8 @@ static int cg_block(smm_ctx *c, const smm_csr *ht, const smm_csr *q, const smm_c
     bool live = c->cg_live[0] > 0;
     for (int64_t it = 1; live && it <= maxiter; ++it) {
         CHK(spmm_launch(c, ht, bht, exact, k, pv, k, z1, k));         // Z1 = H^T P
-        CHK(spmm_launch(c, q, bq, exact, k, z1, k, z2, k));           // Z2 = Q Z1
+        if (q.pair()) CHK(kron_apply_launch(c, q.d, q.e, exact, k, z1, k, zu, z2, k));
+        else          CHK(spmm_launch(c, q.q, bq, exact, k, z1, k, z2, k));           // Z2 = Q Z1
         CHK(spmm_launch(c, h, bh, exact, k, z2, k, wv, k));           // W = H Z2
         if (r) {
             CHK(spmm_launch(c, r, br, exact, k, pv, k, rpv, k));      // R P, added to W on the way to dot(p, w)
@@ -3793,8 +4018,9 @@ static int cg_block(smm_ctx *c, const smm_csr *ht, const smm_csr *q, const smm_c
     return SMM_OK;
 }
 
-// Vectors of one column block: r, p, w, R p (n x kb), the two intermediates (K x kb), the dot partials and the scalars.
-static int innovation_impl(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, bool exact, int64_t k, const double *b, int64_t ldb, double *x,
+// Vectors of one column block: r, p, w, R p (n x kb), the two intermediates (K x kb; three for a pair of factors), the dot
+// partials and the scalars.
+static int innovation_impl(smm_ctx *c, smm_csr *h, const QOp &q, smm_csr *r, bool exact, int64_t k, const double *b, int64_t ldb, double *x,
                            int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status, double *residual_sq, double *rhs_sq)
 {
     const int64_t n = h->rows, K = h->cols;
@@ -3802,22 +4028,23 @@ static int innovation_impl(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, bool 
     const smm_csr *ht = nullptr;
     CHK(spmm_op(c, h, true, &ht));
     CHK(cg_host_words(c));
-    const int64_t per_col = (5 * n + 2 * K) * (int64_t)sizeof(double);
+    const int64_t per_col = (5 * n + (q.pair() ? 3 : 2) * K) * (int64_t)sizeof(double);
     int64_t kb = std::max<int64_t>(1, std::min<int64_t>(k, c->apply_budget / std::max<int64_t>(per_col, 1)));
     const int64_t nblocks = (k + kb - 1) / kb, even = (k + nblocks - 1) / nblocks;      // blocks of one size (64 = 32 + 32, not 44 + 20),
     kb = (even % 2 && even < kb) ? even + 1 : even;                                      // of an even width where the budget allows
-    PoolBuf<double> rv(c), pv(c), wv(c), rpv(c), z1(c), z2(c), part(c), sc(c);
+    PoolBuf<double> rv(c), pv(c), wv(c), rpv(c), z1(c), z2(c), zu(c), part(c), sc(c);
     CHK(rv.alloc((size_t)(n * kb)));
     CHK(pv.alloc((size_t)(n * kb)));
     CHK(wv.alloc((size_t)(n * kb)));
     if (r) CHK(rpv.alloc((size_t)(n * kb)));
     CHK(z1.alloc((size_t)std::max<int64_t>(K * kb, 1)));
     CHK(z2.alloc((size_t)std::max<int64_t>(K * kb, 1)));
+    if (q.pair()) CHK(zu.alloc((size_t)std::max<int64_t>(K * kb, 1)));
     CHK(part.alloc((size_t)CG_T * kb));
     CHK(sc.alloc((size_t)(CG_NSC * kb + (3 * kb + 2) / 2 + 1)));
     for (int64_t j0 = 0; j0 < k; j0 += kb) {
         const int64_t w = std::min(kb, k - j0);
-        CHK(cg_block(c, ht, q, h, r, exact, w, b + j0, ldb, x + j0, ldx, tol, maxiter, rv, pv, wv, rpv, z1, z2, part, sc, iterations + j0,
+        CHK(cg_block(c, ht, q, h, r, exact, w, b + j0, ldb, x + j0, ldx, tol, maxiter, rv, pv, wv, rpv, z1, z2, zu, part, sc, iterations + j0,
                      status + j0, residual_sq + j0, rhs_sq + j0));
     }
     return SMM_OK;
@@ -3855,7 +4082,7 @@ extern "C" int smm_innovation_solve(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr 
     const int64_t n = h->rows, bb = span_bytes(n, k, ldb), xb = span_bytes(n, k, ldx);
     if ((bb > 0 && !d_b) || (xb > 0 && !d_x)) return fail(SMM_ERR_INVALID, "smm_innovation_solve: B or X is NULL");
     if (ranges_overlap(d_b, bb, d_x, xb)) return fail(SMM_ERR_INVALID, "smm_innovation_solve: the device ranges of B and X overlap");
-    CHK(innovation_impl(c, h, q, r, (flags & SMM_EXACT) != 0, k, d_b, ldb, d_x, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq));
+    CHK(innovation_impl(c, h, QOp{q}, r, (flags & SMM_EXACT) != 0, k, d_b, ldb, d_x, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq));
     return take_plan_error(c, "smm_innovation_solve");
 }
 
@@ -3873,8 +4100,67 @@ extern "C" int smm_innovation_solve_host(smm_ctx *c, smm_csr *h, smm_csr *q, smm
     CHK(db.alloc((size_t)(n * k)));
     CHK(dx.alloc((size_t)(n * k)));
     CHK(upload_rows(c, db, b, n, k, ldb));
-    CHK(innovation_impl(c, h, q, r, (flags & SMM_EXACT) != 0, k, db, k, dx, k, tol, maxiter, iterations, status, residual_sq, rhs_sq));
+    CHK(innovation_impl(c, h, QOp{q}, r, (flags & SMM_EXACT) != 0, k, db, k, dx, k, tol, maxiter, iterations, status, residual_sq, rhs_sq));
     CHK(take_plan_error(c, "smm_innovation_solve_host"));
+    return download_rows(c, x, dx, n, k, ldx);
+}
+
+// The same solve with Q = D (x) E applied through its factors (smm_kron.hpp), never formed.
+static int innovation_kron_args(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k, int64_t ldb, int64_t ldx,
+                                double tol, int64_t maxiter, const int *iterations, const int *status, const double *residual_sq,
+                                const double *rhs_sq, const char *where)
+{
+    if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call", where);
+    CHK(kron_q_args(c, h, d, e, where));
+    if (r) {
+        if (r->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
+        if (r->rows != h->rows || r->cols != h->rows)
+            return fail(SMM_ERR_INVALID, "%s: R must be %lld x %lld, got %lld x %lld", where, (long long)h->rows, (long long)h->rows,
+                        (long long)r->rows, (long long)r->cols);
+        CHK(validate(c, r));
+    }
+    if (k < 0 || ldb < k || ldx < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldb, ldx (k %lld, ldb %lld, ldx %lld)", where,
+                                                 (long long)k, (long long)ldb, (long long)ldx);
+    if (!(tol > 0.0) || !std::isfinite(tol)) return fail(SMM_ERR_INVALID, "%s: tol must be a finite positive number", where);
+    if (maxiter < 0 || maxiter > INT32_MAX) return fail(SMM_ERR_INVALID, "%s: need 0 <= maxiter < 2^31", where);
+    if (k > 0 && (!iterations || !status || !residual_sq || !rhs_sq)) return fail(SMM_ERR_INVALID, "%s: a per-column output is NULL", where);
+    return SMM_OK;
+}
+
+extern "C" int smm_innovation_solve_kron(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k, const double *d_b,
+                                         int64_t ldb, double *d_x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
+                                         double *residual_sq, double *rhs_sq)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(innovation_kron_args(c, h, d, e, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq,
+                             "smm_innovation_solve_kron"));
+    const int64_t n = h->rows, bb = span_bytes(n, k, ldb), xb = span_bytes(n, k, ldx);
+    if ((bb > 0 && !d_b) || (xb > 0 && !d_x)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_kron: B or X is NULL");
+    if (ranges_overlap(d_b, bb, d_x, xb)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_kron: the device ranges of B and X overlap");
+    CHK(innovation_impl(c, h, QOp{nullptr, d, e}, r, (flags & SMM_EXACT) != 0, k, d_b, ldb, d_x, ldx, tol, maxiter, iterations, status,
+                        residual_sq, rhs_sq));
+    return take_plan_error(c, "smm_innovation_solve_kron");
+}
+
+extern "C" int smm_innovation_solve_kron_host(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k, const double *b,
+                                              int64_t ldb, double *x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
+                                              double *residual_sq, double *rhs_sq)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(innovation_kron_args(c, h, d, e, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq,
+                             "smm_innovation_solve_kron_host"));
+    const int64_t n = h->rows;
+    if (span_bytes(n, k, std::max(ldb, ldx)) > 0 && (!b || !x)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_kron_host: B or X is NULL");
+    if (n == 0 || k == 0) return SMM_OK;
+    PoolBuf<double> db(c), dx(c);
+    CHK(db.alloc((size_t)(n * k)));
+    CHK(dx.alloc((size_t)(n * k)));
+    CHK(upload_rows(c, db, b, n, k, ldb));
+    CHK(innovation_impl(c, h, QOp{nullptr, d, e}, r, (flags & SMM_EXACT) != 0, k, db, k, dx, k, tol, maxiter, iterations, status, residual_sq,
+                        rhs_sq));
+    CHK(take_plan_error(c, "smm_innovation_solve_kron_host"));
     return download_rows(c, x, dx, n, k, ldx);
 }
 

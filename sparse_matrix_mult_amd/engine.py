@@ -536,6 +536,81 @@ class Context:
                                                  int(nb), ctypes.c_void_p(_dptr(d_b)), int(ldb), ctypes.byref(h)))
         return DeviceCSR(self, h, int(na), int(nb), int(self.lib.smm_csr_nnz(h)))
 
+    # ------------------------------------------------------------------ Kronecker operand Q = D (x) E
+    def kron_build(self, d, e):
+        """D (x) E as a new DeviceCSR the library owns (smm_kron_build): row t * e.rows + j holds D.val[a] * E.val[b] at
+        column D.idx[a] * e.cols + E.idx[b], a over row t of D and b over row j of E in stored order."""
+        h = ctypes.c_void_p()
+        check(self.lib, self.lib.smm_kron_build(self.handle, d.handle, e.handle, ctypes.byref(h)))
+        return DeviceCSR(self, h, d.rows * e.rows, d.cols * e.cols, int(self.lib.smm_csr_nnz(h)))
+
+    def kron_apply_host(self, d, e, x, exact=False):
+        """Y = (D (x) E) X without forming it, X a numpy array (1-D or 2-D, cast to C-contiguous float64): a numpy array of
+        the same number of dimensions (smm_kron_apply_host)."""
+        x, k = self._host_x(x)
+        m, kx = d.rows * e.rows, d.cols * e.cols
+        if x.shape[0] != kx:
+            raise ValueError(f"X has {x.shape[0]} rows, D (x) E has {kx} columns")
+        y = np.empty((m,) if x.ndim == 1 else (m, k), dtype=np.float64)
+        check(self.lib, self.lib.smm_kron_apply_host(self.handle, d.handle, e.handle, _flags(exact=exact), k, _ptr(x), k, _ptr(y), k))
+        return y
+
+    def kron_apply_into(self, d, e, d_x, ldx, k, d_y, ldy, exact=False):
+        """Y = (D (x) E) X on device buffers (smm_kron_apply): X ((d.cols * e.cols) x k, leading dimension ldx) at d_x, Y
+        ((d.rows * e.rows) x k, leading dimension ldy) at d_y; stream rules as spmm_into."""
+        for t in (d_x, d_y):
+            if hasattr(t, "data_ptr"):
+                self._sync_torch(t)
+        check(self.lib, self.lib.smm_kron_apply(self.handle, d.handle, e.handle, _flags(exact=exact), int(k), ctypes.c_void_p(_dptr(d_x)),
+                                                int(ldx), ctypes.c_void_p(_dptr(d_y)), int(ldy)))
+        self.synchronize()
+
+    def triple_apply_kron_host(self, h, d, e, x, exact=False):
+        """Y = H ((D (x) E) (H^T X)) with numpy X (n x k or n): the same shape back (smm_triple_apply_kron_host)."""
+        x, k = self._host_x(x)
+        if x.shape[0] != h.rows:
+            raise ValueError(f"X has {x.shape[0]} rows, H has {h.rows}")
+        y = np.empty(x.shape, dtype=np.float64)
+        check(self.lib, self.lib.smm_triple_apply_kron_host(self.handle, h.handle, d.handle, e.handle, _flags(exact=exact), k, _ptr(x), k,
+                                                            _ptr(y), k))
+        return y
+
+    def triple_apply_kron_into(self, h, d, e, d_x, ldx, k, d_y, ldy, exact=False):
+        """triple_apply_kron_host on device buffers (smm_triple_apply_kron); stream rules as spmm_into."""
+        for t in (d_x, d_y):
+            if hasattr(t, "data_ptr"):
+                self._sync_torch(t)
+        check(self.lib, self.lib.smm_triple_apply_kron(self.handle, h.handle, d.handle, e.handle, _flags(exact=exact), int(k),
+                                                       ctypes.c_void_p(_dptr(d_x)), int(ldx), ctypes.c_void_p(_dptr(d_y)), int(ldy)))
+        self.synchronize()
+
+    def _solve_kron(self, entry, h, d, e, r, k, b, ldb, x, ldx, tol, maxiter, exact):
+        info = SolveInfo(k)
+        check(self.lib, entry(self.handle, h.handle, d.handle, e.handle, r.handle if r is not None else None, _flags(exact=exact), int(k),
+                              b, int(ldb), x, int(ldx), float(tol), int(maxiter), _ptr(info.iterations), _ptr(info.status),
+                              _ptr(info.residual_sq), _ptr(info.rhs_sq)))
+        return info
+
+    def innovation_solve_kron_host(self, h, d, e, r, rhs, tol=1e-8, maxiter=None, exact=False):
+        """innovation_solve_host with Q = D (x) E applied through its factors (smm_innovation_solve_kron_host): (Z, info)."""
+        rhs, k = self._host_x(rhs)
+        if rhs.shape[0] != h.rows:
+            raise ValueError(f"D has {rhs.shape[0]} rows, H has {h.rows}")
+        z = np.zeros(rhs.shape, dtype=np.float64)
+        info = self._solve_kron(self.lib.smm_innovation_solve_kron_host, h, d, e, r, k, _ptr(rhs), k, _ptr(z), k, tol,
+                                h.rows if maxiter is None else maxiter, exact)
+        return z, info
+
+    def innovation_solve_kron_into(self, h, d, e, r, d_b, ldb, k, d_x, ldx, tol=1e-8, maxiter=None, exact=False):
+        """The same on device buffers (smm_innovation_solve_kron); stream rules as spmm_into.  Returns info."""
+        for t in (d_b, d_x):
+            if hasattr(t, "data_ptr"):
+                self._sync_torch(t)
+        info = self._solve_kron(self.lib.smm_innovation_solve_kron, h, d, e, r, k, ctypes.c_void_p(_dptr(d_b)), ldb,
+                                ctypes.c_void_p(_dptr(d_x)), ldx, tol, h.rows if maxiter is None else maxiter, exact)
+        self.synchronize()
+        return info
+
     # ------------------------------------------------------------------ CG on (H Q H^T + R) Z = D
     def _solve(self, entry, h, q, r, k, b, ldb, x, ldx, tol, maxiter, exact):
         info = SolveInfo(k)
@@ -636,6 +711,11 @@ class DeviceCSR:
         check(self.ctx.lib, self.ctx.lib.smm_csr_copy_device(self.ctx.handle, self.handle, ctypes.c_void_p(indptr.data_ptr()),
                                                              ctypes.c_void_p(indices.data_ptr()), None))
         return indptr, indices
+
+    def values_into(self, d_data):
+        """The operand's values copied into a float64 CUDA tensor (or device address) of nnz entries, device to device
+        (smm_csr_copy_device)."""
+        check(self.ctx.lib, self.ctx.lib.smm_csr_copy_device(self.ctx.handle, self.handle, None, None, ctypes.c_void_p(_dptr(d_data))))
 
     def device_bytes(self):
         return int(self.ctx.lib.smm_csr_device_bytes(self.handle)) if self.handle else 0

@@ -470,6 +470,8 @@ def pin_operand(matrix):
     device and the three tensors are borrowed (and kept alive) by the operand; nothing is copied to the host or hashed."""
     if isinstance(matrix, DeviceCSRResult):
         return _pin_device_result(matrix)
+    if isinstance(matrix, KroneckerOperand):
+        _as_csr(matrix)                                   # (refused, with the pointer to kronecker_product)
     return PinnedOperand(default_context(), matrix)
 
 
@@ -583,6 +585,89 @@ def localization_taper(coords, cutoff, coords_b=None, taper="gaspari_cohn", pin=
     return _taper_result(handle, (na, nb), pin)
 
 
+# ------------------------------------------------------------------ Kronecker operand Q = D (x) E
+def _kron_shape(d, e, what):
+    """((p r, p' r'), nnz(D) nnz(E)) of D (x) E; ValueError where a dimension does not fit an operand."""
+    shape = (int(d.shape[0]) * int(e.shape[0]), int(d.shape[1]) * int(e.shape[1]))
+    if shape[0] >= _INT32_MAX or shape[1] >= _INT32_MAX:
+        raise ValueError(f"{what}: D (x) E would be {shape[0]} x {shape[1]}; both dimensions must be below 2^31 - 1")
+    return shape, int(d.nnz) * int(e.nnz)
+
+
+class KroneckerOperand:
+    """Q = D (x) E held as its two factors and never formed: D is p x p' (the temporal covariance), E is r x r' (the spatial
+    one); row t * r + j of Q is the pair (t, j), column t' * r' + j' the pair (t', j').  Accepted as matrix_a of
+    sparse_dense_multiply (transpose=False) and as matrix_q of triple_product_apply and innovation_solve; every other call
+    wants the explicit matrix of kronecker_product(D, E).
+
+    D, E : scipy CSR, anything csr_matrix() accepts, or PinnedOperands.
+    .shape, .nnz (of the explicit matrix), .factors == (D, E), .to_scipy() (scipy.sparse.kron of the factors, on the host).
+    """
+    __slots__ = ("factors", "shape", "nnz")
+
+    def __init__(self, D, E):
+        d, e = _as_csr(D), _as_csr(E)
+        self.factors = (d, e)
+        self.shape, self.nnz = _kron_shape(d, e, "KroneckerOperand")
+
+    def to_scipy(self):
+        from scipy.sparse import kron
+        d, e = (f.to_scipy() if isinstance(f, PinnedOperand) else f for f in self.factors)
+        return csr_matrix(kron(d, e, format="csr"))
+
+    def _square(self, what):
+        for name, f in zip("DE", self.factors):
+            if f.shape[0] != f.shape[1]:
+                raise ValueError(f"{what}: Q must be square, but its factor {name} is {f.shape[0]} x {f.shape[1]}")
+
+
+def kronecker_product(D, E, pin=False):
+    """The explicit Kronecker product D (x) E as one CSR matrix, built on the GPU from the two factors.
+
+    D : p x p', E : r x r' (scipy CSR, anything csr_matrix() accepts, or a PinnedOperand).  The result is (p r) x (p' r'):
+    row t * r + j holds, for a over row t of D and b over row j of E in stored order, column D.idx[a] * r' + E.idx[b] with
+    value D.val[a] * E.val[b] (one rounded multiply; explicitly stored zeros stay entries).  For canonical factors this is
+    scipy.sparse.kron(D, E, format="csr") bit for bit in indptr, indices and data.
+    pin : False returns a scipy CSR (int32 indices), or a DeviceCSRResult under set_result_device(True).  True returns a
+          PinnedOperand that adopts the library's operand where it is -- no copy to the host: pass it wherever a matrix is
+          accepted.
+    ValueError before any device call: a result dimension of 2^31 - 1 or more, or more than 2^31 - 2 entries (operand row
+    pointers are int32) -- a Q that large is used through KroneckerOperand(D, E), which never forms it.  A factor without
+    entries gives the empty matrix and no device is touched.  Nothing is printed.
+    """
+    what = "kronecker_product"
+    D, E = _as_csr(D), _as_csr(E)
+    shape, nnz = _kron_shape(D, E, what)
+    if nnz > _INT32_MAX - 1:
+        raise ValueError(f"{what}: nnz(D) * nnz(E) = {D.nnz} * {E.nnz} = {nnz} entries do not fit one operand (int32 row "
+                         "pointers, at most 2^31 - 2); use KroneckerOperand(D, E), which applies the factors without forming Q")
+    if nnz == 0:
+        return PinnedOperand._adopt(None, None, shape) if pin else _zero_result(shape)
+    ctx = default_context()
+
+    def body(ld, le):
+        if pin:
+            return PinnedOperand._adopt(ctx, ctx.kron_build(ld.handle, le.handle))
+        if not _result_device:
+            return _taper_result(ctx.kron_build(ld.handle, le.handle), shape, False)
+        import torch
+        dev = torch.device("cuda", ctx.device)
+
+        def call():
+            handle = ctx.kron_build(ld.handle, le.handle)
+            try:
+                indptr, indices = handle.pattern_torch()
+                data = torch.empty(handle.nnz, dtype=torch.float64, device=dev)
+                handle.values_into(data)
+                return DeviceCSRResult(indptr.to(torch.int64), indices, data, shape)
+            finally:
+                handle.close()
+
+        return _on_device(ctx, call)
+
+    return _with_leases(ctx, (D, E), body)
+
+
 def _device_zeros(ctx, shape, sparse):
     import torch
     dev = torch.device("cuda", ctx.device)
@@ -644,6 +729,9 @@ def _product_on_device(ctx, la, lb, triple, output_format, symmetric, compute_fu
 
 def _as_csr(x):
     # reference :307-310: anything csr_matrix() accepts; no sort, no dedup
+    if isinstance(x, KroneckerOperand):
+        raise ValueError("a KroneckerOperand is accepted as matrix_a of sparse_dense_multiply and as matrix_q of "
+                         "triple_product_apply and innovation_solve only; build the explicit matrix with kronecker_product(D, E)")
     return x if (isspmatrix_csr(x) or isinstance(x, PinnedOperand)) else csr_matrix(x)
 
 
@@ -966,7 +1054,9 @@ def _dense_zeros(shape, on_device):
 def sparse_dense_multiply(matrix_a, x, transpose=False):
     """Y = A @ X, or A.T @ X with transpose=True, for a sparse A and a dense X, on the GPU.
 
-    matrix_a : scipy CSR, anything csr_matrix() accepts, or a PinnedOperand (the operand cache applies).
+    matrix_a : scipy CSR, anything csr_matrix() accepts, or a PinnedOperand (the operand cache applies); or a
+               KroneckerOperand(D, E): Y = (D (x) E) X through the factors, E first (transpose=False only; under
+               set_exact(True) bit-identical to scipy's D @ (E @ X[t]) stacked over t, not to kron(D, E) @ X).
     x        : a numpy array (cast to float64, C-contiguous) or a float64 CUDA tensor on the library's device; 1-D or
                2-D.  A 1-D X gives a 1-D result.
     Returns numpy for numpy input; a torch tensor on the device for torch input or under set_result_device(True).
@@ -974,7 +1064,12 @@ def sparse_dense_multiply(matrix_a, x, transpose=False):
     the row's products in stored order); otherwise within 1e-10 of (|A| |X|)[i, j].  A pair that row i does not store is
     never multiplied.  A.T comes from a transpose built on the device once and kept with the operand.
     """
-    matrix_a = _as_csr(matrix_a)
+    kron = isinstance(matrix_a, KroneckerOperand)
+    if kron and transpose:
+        raise ValueError("sparse_dense_multiply: a KroneckerOperand has no transpose flag: (D (x) E)^T = D^T (x) E^T, so pass "
+                         "KroneckerOperand(D.T, E.T)")
+    if not kron:
+        matrix_a = _as_csr(matrix_a)
     m, kx = matrix_a.shape[::-1] if transpose else matrix_a.shape
     x, k, is_torch = _dense_operand(x, kx, "sparse_dense_multiply")
     out_shape = (m,) if len(x.shape) == 1 else (m, k)
@@ -988,6 +1083,14 @@ def sparse_dense_multiply(matrix_a, x, transpose=False):
                             lambda xh: ctx.spmm_host(a, xh, transpose=transpose, exact=_exact),
                             lambda dx, ldx, dy, ldy: ctx.spmm_into(a, dx, ldx, k, dy, ldy, transpose=transpose, exact=_exact))
 
+    def body_kron(ld, le):
+        d, e = ld.handle, le.handle
+        return _dense_apply(ctx, x, k, is_torch, m,
+                            lambda xh: ctx.kron_apply_host(d, e, xh, exact=_exact),
+                            lambda dx, ldx, dy, ldy: ctx.kron_apply_into(d, e, dx, ldx, k, dy, ldy, exact=_exact))
+
+    if kron:
+        return _with_leases(ctx, matrix_a.factors, body_kron)
     return _with_leases(ctx, (matrix_a,), body)
 
 
@@ -995,13 +1098,18 @@ def triple_product_apply(matrix_h, matrix_q, x):
     """Y = H @ (Q @ (H.T @ X)) = S X with S = H Q H^T never formed, on the GPU.
 
     matrix_h : n x K, matrix_q : K x K (need not be symmetric); scipy CSR, anything csr_matrix() accepts, or a
-    PinnedOperand.  x : n x k or n, as in sparse_dense_multiply (numpy or a float64 CUDA tensor).  Returns the same kind
+    PinnedOperand.  matrix_q may be a KroneckerOperand(D, E) with square factors and p * r == K: Q = D (x) E is then applied
+    through its factors (sparse_dense_multiply's order) and never formed.  x : n x k or n, as in sparse_dense_multiply (numpy or a float64 CUDA tensor).  Returns the same kind
     and shape as x (a torch tensor under set_result_device(True)).  Under set_exact(True) bit-identical to scipy's
     H @ (Q @ (H.T @ X)); otherwise within rounding.  X is processed in column blocks whose two K x block intermediates fit
     the context's budget (Context.tune_spmm; blocking changes no bit).
     """
     matrix_h = _as_csr(matrix_h)
-    matrix_q = _as_csr(matrix_q)
+    kron = isinstance(matrix_q, KroneckerOperand)
+    if kron:
+        matrix_q._square("triple_product_apply")
+    else:
+        matrix_q = _as_csr(matrix_q)
     if matrix_q.shape[0] != matrix_q.shape[1]:
         raise ValueError(f"triple_product_apply: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
     if matrix_h.shape[1] != matrix_q.shape[0]:
@@ -1013,13 +1121,17 @@ def triple_product_apply(matrix_h, matrix_q, x):
         return _dense_zeros(out_shape, is_torch or _result_device)
     ctx = default_context()
 
-    def body(lh, lq):
-        h, q = lh.handle, lq.handle
+    def body(lh, *lq):
+        h, q = lh.handle, [lease.handle for lease in lq]
+        if kron:
+            return _dense_apply(ctx, x, k, is_torch, n,
+                                lambda xh: ctx.triple_apply_kron_host(h, q[0], q[1], xh, exact=_exact),
+                                lambda dx, ldx, dy, ldy: ctx.triple_apply_kron_into(h, q[0], q[1], dx, ldx, k, dy, ldy, exact=_exact))
         return _dense_apply(ctx, x, k, is_torch, n,
-                            lambda xh: ctx.triple_apply_host(h, q, xh, exact=_exact),
-                            lambda dx, ldx, dy, ldy: ctx.triple_apply_into(h, q, dx, ldx, k, dy, ldy, exact=_exact))
+                            lambda xh: ctx.triple_apply_host(h, q[0], xh, exact=_exact),
+                            lambda dx, ldx, dy, ldy: ctx.triple_apply_into(h, q[0], dx, ldx, k, dy, ldy, exact=_exact))
 
-    return _with_leases(ctx, (matrix_h, matrix_q), body)
+    return _with_leases(ctx, (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)), body)
 
 
 # ------------------------------------------------------------------ (X Y^T) on a pattern
@@ -1169,7 +1281,8 @@ def _cg_on_host(apply, d, tol, maxiter):
 def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
     """(Z, info) with (H Q H^T + R) Z = D by conjugate gradients on the GPU; S = H Q H^T is never formed.
 
-    matrix_h : n x K, matrix_q : K x K; scipy CSR, anything csr_matrix() accepts, or a PinnedOperand.
+    matrix_h : n x K, matrix_q : K x K; scipy CSR, anything csr_matrix() accepts, or a PinnedOperand.  matrix_q may be a
+               KroneckerOperand(D, E) (square factors, p * r == K): Q = D (x) E is applied through its factors, never formed.
     matrix_r : n x n in the same forms, a 1-D array of the n diagonal entries, or None for S alone.  S + R is expected
                to be symmetric positive definite.
     d        : n x k or n, numpy or a float64 CUDA tensor as in triple_product_apply.  Every column is its own CG from
@@ -1183,7 +1296,11 @@ def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
     of a block of columns are sized by Context.tune_spmm's apply budget.
     """
     matrix_h = _as_csr(matrix_h)
-    matrix_q = _as_csr(matrix_q)
+    kron = isinstance(matrix_q, KroneckerOperand)
+    if kron:
+        matrix_q._square("innovation_solve")
+    else:
+        matrix_q = _as_csr(matrix_q)
     if matrix_q.shape[0] != matrix_q.shape[1]:
         raise ValueError(f"innovation_solve: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
     if matrix_h.shape[1] != matrix_q.shape[0]:
@@ -1233,10 +1350,15 @@ def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
         return z, info
     ctx = default_context()
 
-    def body(lh, lq, *lr):
-        h, q, r = lh.handle, lq.handle, (lr[0].handle if lr else None)
+    nq = 2 if kron else 1
+
+    def body(lh, *rest):
+        h, q, lr = lh.handle, [lease.handle for lease in rest[:nq]], rest[nq:]
+        r = lr[0].handle if lr else None
         if not on_device:
-            return ctx.innovation_solve_host(h, q, r, d, tol, maxiter, exact=_exact)
+            if kron:
+                return ctx.innovation_solve_kron_host(h, q[0], q[1], r, d, tol, maxiter, exact=_exact)
+            return ctx.innovation_solve_host(h, q[0], r, d, tol, maxiter, exact=_exact)
         import torch
         dev = torch.device("cuda", ctx.device)
         if not is_torch:
@@ -1246,7 +1368,12 @@ def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
         else:
             b = d
         z = torch.empty(tuple(b.shape), dtype=torch.float64, device=dev)
-        info = ctx.innovation_solve_into(h, q, r, b, 1 if b.dim() == 1 else b.stride(0), k, z, k, tol, maxiter, exact=_exact)
+        ldb = 1 if b.dim() == 1 else b.stride(0)
+        if kron:
+            info = ctx.innovation_solve_kron_into(h, q[0], q[1], r, b, ldb, k, z, k, tol, maxiter, exact=_exact)
+        else:
+            info = ctx.innovation_solve_into(h, q[0], r, b, ldb, k, z, k, tol, maxiter, exact=_exact)
         return z, info
 
-    return _with_leases(ctx, (matrix_h, matrix_q) + ((matrix_r,) if matrix_r is not None else ()), body)
+    mats = (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)) + ((matrix_r,) if matrix_r is not None else ())
+    return _with_leases(ctx, mats, body)
