@@ -516,6 +516,43 @@ int  smm_innovation_solve_kron_host(smm_ctx *ctx, smm_csr *h, smm_csr *d, smm_cs
                                     int64_t ldb, double *x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
                                     double *residual_sq, double *rhs_sq);
 
+/* ------------------------------------------------------------------ log det(H Q H^T + R): probes and recorded CG coefficients
+ * Stochastic Lanczos quadrature reads ln det Psi, Psi = H Q H^T + R, off the batched CG above: probes z_c with entries +-1,
+ * CG on Psi x = z_c, the CG coefficients turned into the Lanczos tridiagonal T_c (m x m for a column with m iterations),
+ *     T[j, j] = 1 / alpha_j + beta_{j-1} / alpha_{j-1}  (second term absent for j = 0),   T[j, j+1] = T[j+1, j] = sqrt(beta_j) / alpha_j,
+ * and z_c^T ln(Psi) z_c ~ n e_1^T ln(T_c) e_1; the mean over the probes estimates tr ln Psi = ln det Psi.  The device part is
+ * the two calls below; the eigen-decomposition of the small tridiagonals is the caller's (the Python package uses LAPACK).
+ *
+ * smm_probe_fill: X[i, c] = +1.0 or -1.0 for i < n, c < k, into a row-major float64 block with leading dimension ldx >= k;
+ *   padding is not written.  The sign is part of the contract.  With 64-bit wrap-around arithmetic,
+ *       z = seed + c * 0xD1B54A32D192ED03 + (i + 1) * 0x9E3779B97F4A7C15
+ *       z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9
+ *       z ^= z >> 27;  z *= 0x94D049BB133111EB
+ *       z ^= z >> 31
+ *   and the entry is -1.0 iff bit 63 of z is set.  The value depends on (seed, i, c) only -- not on k, ldx or the launch
+ *   geometry: column c of any call with the same seed is the same probe.  k = 0 or n = 0: no launch.  A NULL buffer with data
+ *   to write, ldx < k and negative sizes are SMM_ERR_INVALID.  The call returns with the fill queued on the context's stream.
+ *
+ * smm_innovation_solve_coef / smm_innovation_solve_coef_kron: smm_innovation_solve / smm_innovation_solve_kron on device B and
+ *   X -- the same arguments, recipe, outputs and bits -- with the coefficients of every column kept.  alpha and beta are
+ *   host arrays of maxiter x k doubles, row it - 1, column j:
+ *       alpha[it - 1, j]  the alpha of iteration it of column j, written where the column does not break down in it
+ *       beta[it - 1, j]   the beta of iteration it, written where the column does not converge in it
+ *   and every other entry is +0.0 (a frozen column is never written again).  So a column with iterations = m has m alphas;
+ *   m - 1 betas when its status is 0, m betas when it is 1 or 2.  On the device the histories are two pool temporaries of
+ *   maxiter x kb per column block, zeroed per block and downloaded after the block's loop into the caller's columns: nothing
+ *   new synchronises inside the iteration, and column blocking puts every column's coefficients in its own place.  Under
+ *   SMM_EXACT alpha and beta are bit-identical to the recipe above carried out in IEEE double, for any blocking; in default
+ *   mode two runs agree bit for bit.  maxiter sizes the histories: 1 <= maxiter <= 65536, else SMM_ERR_INVALID, as are NULL
+ *   alpha or beta (k > 0) and a NULL d_x. */
+int  smm_probe_fill(smm_ctx *ctx, int64_t n, int64_t k, uint64_t seed, double *d_x, int64_t ldx);
+int  smm_innovation_solve_coef(smm_ctx *ctx, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, const double *d_b,
+                               int64_t ldb, double *d_x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
+                               double *residual_sq, double *rhs_sq, double *alpha, double *beta);
+int  smm_innovation_solve_coef_kron(smm_ctx *ctx, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k,
+                                    const double *d_b, int64_t ldb, double *d_x, int64_t ldx, double tol, int64_t maxiter,
+                                    int *iterations, int *status, double *residual_sq, double *rhs_sq, double *alpha, double *beta);
+
 /* ------------------------------------------------------------------ device memory helpers
  * (so that hosts without torch can still hold results in HBM) */
 int  smm_device_malloc(smm_ctx *ctx, int64_t bytes, void **d_ptr);

@@ -127,6 +127,11 @@ V2_PROTOTYPES = {
                                                  _c_i64, _vp, _vp, _vp, _vp]),
     "smm_innovation_solve_kron_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64,
                                                       ctypes.c_double, _c_i64, _vp, _vp, _vp, _vp]),
+    "smm_probe_fill": (ctypes.c_int, [_vp, _c_i64, _c_i64, ctypes.c_uint64, _vp, _c_i64]),
+    "smm_innovation_solve_coef": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_double,
+                                                 _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smm_innovation_solve_coef_kron": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64,
+                                                      ctypes.c_double, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "smm_device_malloc": (ctypes.c_int, [_vp, _c_i64, _pp]),
     "smm_device_free": (ctypes.c_int, [_vp, _vp]),
     "smm_memcpy_d2h": (ctypes.c_int, [_vp, _vp, _vp, _c_i64]),

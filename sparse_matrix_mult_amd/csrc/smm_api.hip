@@ -10,6 +10,7 @@
 #include "smm_spmm.hpp"
 #include "smm_kron.hpp"
 #include "smm_cg.hpp"
+#include "smm_slq.hpp"
 #include "smm_sddmm.hpp"
 #include "smm_taper.hpp"
 #include "../../include/smm_hip.h"
@@ -3945,10 +3946,13 @@ static int cg_host_words(smm_ctx *c)
 // One column block of the solve (smm_cg.hpp; the contract is in include/smm_hip.h).  b / x point at the block's first column.
 // The host enqueues iteration it, then waits for the live count that iteration it - 1 left: the device always has one
 // iteration queued, and at most one runs after the last column froze -- on frozen columns, which no kernel writes.
+// hist (smm_innovation_solve_coef) or NULL: the block's two device histories (maxiter x k each) and the caller's host arrays,
+// pointing at the block's first column, with their leading dimension.
+struct CgHist { double *d_alpha, *d_beta, *alpha, *beta; int64_t ld; };
 static int cg_block(smm_ctx *c, const smm_csr *ht, const QOp &q, const smm_csr *h, const smm_csr *r, bool exact, int64_t k,
                     const double *b, int64_t ldb, double *x, int64_t ldx, double tol, int64_t maxiter, double *rv, double *pv, double *wv,
                     double *rpv, double *z1, double *z2, double *zu, double *part, double *sc, int *iterations, int *status,
-                    double *residual_sq, double *rhs_sq)
+                    double *residual_sq, double *rhs_sq, const CgHist *hist)
 {
     const int64_t n = h->rows;
     ClassLists bht(c), bq(c), bh(c), br(c);
@@ -3975,13 +3979,20 @@ static int cg_block(smm_ctx *c, const smm_csr *ht, const QOp &q, const smm_csr *
     } while (0)
 #define CG_COMMA ,
     HIPCHK(hipMemsetAsync(st + 3 * k, 0, sizeof(int), c->stream));
+    if (hist) {                                                   // +0.0 wherever no coefficient is written
+        HIPCHK(hipMemsetAsync(hist->d_alpha, 0, (size_t)(maxiter * k) * sizeof(double), c->stream));
+        HIPCHK(hipMemsetAsync(hist->d_beta, 0, (size_t)(maxiter * k) * sizeof(double), c->stream));
+    }
+    double *const none = nullptr;
     CG_LAUNCH("smm_cg_init", smm_cg_init);
-    LAUNCH(c, "smm_cg_finish", smm_cg_finish<0>, k, CG_FIN, 0, part, k, sc, st, tol2, 0);
+    LAUNCH(c, "smm_cg_finish", smm_cg_finish<0>, k, CG_FIN, 0, part, k, sc, st, tol2, 0, none);
     LAUNCH_CHECK();
     HIPCHK(hipMemcpyAsync(c->cg_live, st + 3 * k, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     bool live = c->cg_live[0] > 0;
+    int64_t ran = 0;                                              // iterations enqueued
     for (int64_t it = 1; live && it <= maxiter; ++it) {
+        ran = it;
         CHK(spmm_launch(c, ht, bht, exact, k, pv, k, z1, k));         // Z1 = H^T P
         if (q.pair()) CHK(kron_apply_launch(c, q.d, q.e, exact, k, z1, k, zu, z2, k));
         else          CHK(spmm_launch(c, q.q, bq, exact, k, z1, k, z2, k));           // Z2 = Q Z1
@@ -3992,9 +4003,11 @@ static int cg_block(smm_ctx *c, const smm_csr *ht, const QOp &q, const smm_csr *
         } else {
             CG_LAUNCH("smm_cg_pw", smm_cg_pw, CG_COMMA false);
         }
-        LAUNCH(c, "smm_cg_finish", smm_cg_finish<1>, k, CG_FIN, 0, part, k, sc, st, tol2, (int)it);
+        if (hist) LAUNCH(c, "smm_cg_finish", (smm_cg_finish<1, true>), k, CG_FIN, 0, part, k, sc, st, tol2, (int)it, hist->d_alpha);
+        else      LAUNCH(c, "smm_cg_finish", smm_cg_finish<1>, k, CG_FIN, 0, part, k, sc, st, tol2, (int)it, none);
         CG_LAUNCH("smm_cg_update", smm_cg_update);
-        LAUNCH(c, "smm_cg_finish", smm_cg_finish<2>, k, CG_FIN, 0, part, k, sc, st, tol2, (int)it);
+        if (hist) LAUNCH(c, "smm_cg_finish", (smm_cg_finish<2, true>), k, CG_FIN, 0, part, k, sc, st, tol2, (int)it, hist->d_beta);
+        else      LAUNCH(c, "smm_cg_finish", smm_cg_finish<2>, k, CG_FIN, 0, part, k, sc, st, tol2, (int)it, none);
         CG_LAUNCH("smm_cg_direction", smm_cg_direction);
         LAUNCH_CHECK();
         const int slot = (int)(it & 1);
@@ -4007,6 +4020,18 @@ static int cg_block(smm_ctx *c, const smm_csr *ht, const QOp &q, const smm_csr *
     }
 #undef CG_COMMA
 #undef CG_LAUNCH
+    // the histories' rows that an iteration could have written (the rest are the caller's zeros), queued in front of the
+    // scalars' download: its synchronisation serves all three copies
+    if (hist && ran > 0) {
+        const size_t row = (size_t)k * sizeof(double), pitch = (size_t)hist->ld * sizeof(double);
+        if (hist->ld == k) {                                      // one block: the rows are contiguous on both sides
+            HIPCHK(hipMemcpyAsync(hist->alpha, hist->d_alpha, row * (size_t)ran, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(hist->beta, hist->d_beta, row * (size_t)ran, hipMemcpyDeviceToHost, c->stream));
+        } else {
+            HIPCHK(hipMemcpy2DAsync(hist->alpha, pitch, hist->d_alpha, row, row, (size_t)ran, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpy2DAsync(hist->beta, pitch, hist->d_beta, row, row, (size_t)ran, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
     // the block's scalars, as the device left them
     std::vector<double> hs((size_t)(CG_NSC * k + (3 * k + 2) / 2 + 1));
     CHK(download(c, hs.data(), sc, ((size_t)CG_NSC * k) * sizeof(double) + ((size_t)3 * k + 1) * sizeof(int)));
@@ -4021,9 +4046,14 @@ static int cg_block(smm_ctx *c, const smm_csr *ht, const QOp &q, const smm_csr *
 // Vectors of one column block: r, p, w, R p (n x kb), the two intermediates (K x kb; three for a pair of factors), the dot
 // partials and the scalars.
 static int innovation_impl(smm_ctx *c, smm_csr *h, const QOp &q, smm_csr *r, bool exact, int64_t k, const double *b, int64_t ldb, double *x,
-                           int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status, double *residual_sq, double *rhs_sq)
+                           int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status, double *residual_sq, double *rhs_sq,
+                           double *alpha = nullptr, double *beta = nullptr)
 {
     const int64_t n = h->rows, K = h->cols;
+    if (alpha) {                                                  // maxiter x k each: +0.0 wherever no coefficient lands
+        memset(alpha, 0, (size_t)(maxiter * k) * sizeof(double));
+        memset(beta, 0, (size_t)(maxiter * k) * sizeof(double));
+    }
     if (n == 0 || k == 0) return SMM_OK;
     const smm_csr *ht = nullptr;
     CHK(spmm_op(c, h, true, &ht));
@@ -4032,7 +4062,7 @@ static int innovation_impl(smm_ctx *c, smm_csr *h, const QOp &q, smm_csr *r, boo
     int64_t kb = std::max<int64_t>(1, std::min<int64_t>(k, c->apply_budget / std::max<int64_t>(per_col, 1)));
     const int64_t nblocks = (k + kb - 1) / kb, even = (k + nblocks - 1) / nblocks;      // blocks of one size (64 = 32 + 32, not 44 + 20),
     kb = (even % 2 && even < kb) ? even + 1 : even;                                      // of an even width where the budget allows
-    PoolBuf<double> rv(c), pv(c), wv(c), rpv(c), z1(c), z2(c), zu(c), part(c), sc(c);
+    PoolBuf<double> rv(c), pv(c), wv(c), rpv(c), z1(c), z2(c), zu(c), part(c), sc(c), ha(c), hb(c);
     CHK(rv.alloc((size_t)(n * kb)));
     CHK(pv.alloc((size_t)(n * kb)));
     CHK(wv.alloc((size_t)(n * kb)));
@@ -4042,10 +4072,15 @@ static int innovation_impl(smm_ctx *c, smm_csr *h, const QOp &q, smm_csr *r, boo
     if (q.pair()) CHK(zu.alloc((size_t)std::max<int64_t>(K * kb, 1)));
     CHK(part.alloc((size_t)CG_T * kb));
     CHK(sc.alloc((size_t)(CG_NSC * kb + (3 * kb + 2) / 2 + 1)));
+    if (alpha) {
+        CHK(ha.alloc((size_t)(maxiter * kb)));
+        CHK(hb.alloc((size_t)(maxiter * kb)));
+    }
     for (int64_t j0 = 0; j0 < k; j0 += kb) {
         const int64_t w = std::min(kb, k - j0);
+        const CgHist hist{ha, hb, alpha ? alpha + j0 : nullptr, beta ? beta + j0 : nullptr, k};
         CHK(cg_block(c, ht, q, h, r, exact, w, b + j0, ldb, x + j0, ldx, tol, maxiter, rv, pv, wv, rpv, z1, z2, zu, part, sc, iterations + j0,
-                     status + j0, residual_sq + j0, rhs_sq + j0));
+                     status + j0, residual_sq + j0, rhs_sq + j0, alpha ? &hist : nullptr));
     }
     return SMM_OK;
 }
@@ -4162,6 +4197,69 @@ extern "C" int smm_innovation_solve_kron_host(smm_ctx *c, smm_csr *h, smm_csr *d
                         rhs_sq));
     CHK(take_plan_error(c, "smm_innovation_solve_kron_host"));
     return download_rows(c, x, dx, n, k, ldx);
+}
+
+// ------------------------------------------------------------------------------ probes and recorded CG coefficients (SLQ)
+extern "C" int smm_probe_fill(smm_ctx *c, int64_t n, int64_t k, uint64_t seed, double *d_x, int64_t ldx)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    if (n < 0 || k < 0 || ldx < k) return fail(SMM_ERR_INVALID, "smm_probe_fill: need n >= 0 and 0 <= k <= ldx (n %lld, k %lld, ldx %lld)",
+                                               (long long)n, (long long)k, (long long)ldx);
+    if (n == 0 || k == 0) return SMM_OK;
+    if (!d_x) return fail(SMM_ERR_INVALID, "smm_probe_fill: X is NULL");
+    if (n > INT64_MAX / ldx) return fail(SMM_ERR_INVALID, "smm_probe_fill: n * ldx does not fit 64 bits");
+    HIPCHK(hipSetDevice(c->device));
+    // 16-byte stores where every thread's pair of columns is aligned (the rule of cg_block)
+    const int vec = (k % 2 == 0 && ldx % 2 == 0 && (uintptr_t)d_x % 16 == 0) ? 2 : 1;
+    const int64_t total = n * (k / vec);
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, (int64_t)c->n_cu * 32));
+    if (vec == 2) LAUNCH(c, "smm_probe_fill", smm_probe_fill_k<2>, grid, 256, 0, n, k, (unsigned long long)seed, d_x, ldx);
+    else          LAUNCH(c, "smm_probe_fill", smm_probe_fill_k<1>, grid, 256, 0, n, k, (unsigned long long)seed, d_x, ldx);
+    LAUNCH_CHECK();
+    return SMM_OK;
+}
+
+// What the recording entries ask beyond their plain counterparts: the histories are sized by maxiter.
+static int coef_args(int64_t k, int64_t maxiter, const double *alpha, const double *beta, const char *where)
+{
+    if (maxiter < 1 || maxiter > 65536) return fail(SMM_ERR_INVALID, "%s: need 1 <= maxiter <= 65536 (the histories are maxiter x k), got %lld",
+                                                    where, (long long)maxiter);
+    if (k > 0 && (!alpha || !beta)) return fail(SMM_ERR_INVALID, "%s: alpha or beta is NULL", where);
+    return SMM_OK;
+}
+
+extern "C" int smm_innovation_solve_coef(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, const double *d_b, int64_t ldb,
+                                         double *d_x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
+                                         double *residual_sq, double *rhs_sq, double *alpha, double *beta)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(innovation_args(c, h, q, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq, "smm_innovation_solve_coef"));
+    CHK(coef_args(k, maxiter, alpha, beta, "smm_innovation_solve_coef"));
+    const int64_t n = h->rows, bb = span_bytes(n, k, ldb), xb = span_bytes(n, k, ldx);
+    if ((bb > 0 && !d_b) || !d_x) return fail(SMM_ERR_INVALID, "smm_innovation_solve_coef: B or X is NULL");
+    if (ranges_overlap(d_b, bb, d_x, xb)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_coef: the device ranges of B and X overlap");
+    CHK(innovation_impl(c, h, QOp{q}, r, (flags & SMM_EXACT) != 0, k, d_b, ldb, d_x, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq,
+                        k > 0 ? alpha : nullptr, k > 0 ? beta : nullptr));
+    return take_plan_error(c, "smm_innovation_solve_coef");
+}
+
+extern "C" int smm_innovation_solve_coef_kron(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k,
+                                              const double *d_b, int64_t ldb, double *d_x, int64_t ldx, double tol, int64_t maxiter,
+                                              int *iterations, int *status, double *residual_sq, double *rhs_sq, double *alpha, double *beta)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(innovation_kron_args(c, h, d, e, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq,
+                             "smm_innovation_solve_coef_kron"));
+    CHK(coef_args(k, maxiter, alpha, beta, "smm_innovation_solve_coef_kron"));
+    const int64_t n = h->rows, bb = span_bytes(n, k, ldb), xb = span_bytes(n, k, ldx);
+    if ((bb > 0 && !d_b) || !d_x) return fail(SMM_ERR_INVALID, "smm_innovation_solve_coef_kron: B or X is NULL");
+    if (ranges_overlap(d_b, bb, d_x, xb)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_coef_kron: the device ranges of B and X overlap");
+    CHK(innovation_impl(c, h, QOp{nullptr, d, e}, r, (flags & SMM_EXACT) != 0, k, d_b, ldb, d_x, ldx, tol, maxiter, iterations, status,
+                        residual_sq, rhs_sq, k > 0 ? alpha : nullptr, k > 0 ? beta : nullptr));
+    return take_plan_error(c, "smm_innovation_solve_coef_kron");
 }
 
 // ------------------------------------------------------------------------------ memory helpers

@@ -176,9 +176,12 @@ __global__ __launch_bounds__(256) void smm_cg_direction(const CgArgs A)
 //   STEP 0 (after smm_cg_init)    rho = rhs_sq = res_sq = s, thr = tol2 * s; frozen at once when rho <= thr
 //   STEP 1 (after smm_cg_pw)      pw = s; not (pw > 0): breakdown, else alpha = rho / pw
 //   STEP 2 (after smm_cg_update)  rho_new = s; rho_new <= thr: converged, else beta = rho_new / rho, rho = rho_new
-template <int STEP>
+// REC (smm_innovation_solve_coef): hist is the block's maxiter x k history of alpha (STEP 1) or beta (STEP 2), zeroed by the
+// host; row it - 1 gets the coefficient where the column computes one.  Without REC hist is never read (NULL) and the
+// kernels are the code they were before the history existed.
+template <int STEP, bool REC = false>
 __global__ __launch_bounds__(CG_FIN) void smm_cg_finish(const double *__restrict__ part, int64_t k, double *__restrict__ sc, int *__restrict__ st,
-                                                        double tol2, int it)
+                                                        double tol2, int it, double *__restrict__ hist)
 {
     __shared__ double s[CG_FIN];
     const int64_t j = blockIdx.x;
@@ -203,12 +206,20 @@ __global__ __launch_bounds__(CG_FIN) void smm_cg_finish(const double *__restrict
         if (frozen[j]) return;
         if constexpr (STEP == 1) {
             if (!(sum > 0.0)) { status[j] = CG_BREAKDOWN; frozen[j] = 1; iters[j] = it - 1; atomicSub(live, 1); }
-            else sc[CG_ALPHA * k + j] = sc[CG_RHO * k + j] / sum;
+            else {
+                const double alpha = sc[CG_RHO * k + j] / sum;
+                sc[CG_ALPHA * k + j] = alpha;
+                if constexpr (REC) hist[(int64_t)(it - 1) * k + j] = alpha;
+            }
         } else {
             sc[CG_RES * k + j] = sum;
             iters[j] = it;
             if (sum <= sc[CG_THR * k + j]) { status[j] = CG_CONVERGED; frozen[j] = 1; atomicSub(live, 1); }
-            else { sc[CG_BETA * k + j] = sum / sc[CG_RHO * k + j]; sc[CG_RHO * k + j] = sum; }
+            else {
+                const double beta = sum / sc[CG_RHO * k + j];
+                sc[CG_BETA * k + j] = beta; sc[CG_RHO * k + j] = sum;
+                if constexpr (REC) hist[(int64_t)(it - 1) * k + j] = beta;
+            }
         }
     }
 }

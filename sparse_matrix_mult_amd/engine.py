@@ -642,17 +642,55 @@ class Context:
         self.synchronize()
         return info
 
+    # ------------------------------------------------------------------ log det(H Q H^T + R): probes, recorded coefficients
+    def probe_fill_into(self, d_x, ldx, n, k, seed=0):
+        """X[i, c] = +-1.0 by the hash of include/smm_hip.h (seed taken modulo 2^64) into the n x k block at d_x, leading
+        dimension ldx (smm_probe_fill); padding is not written.  An int (device address) or a torch tensor; stream rules
+        as spmm_into."""
+        if hasattr(d_x, "data_ptr"):
+            self._sync_torch(d_x)
+        check(self.lib, self.lib.smm_probe_fill(self.handle, int(n), int(k), int(seed) % (1 << 64), ctypes.c_void_p(_dptr(d_x)), int(ldx)))
+        self.synchronize()
+
+    def _solve_coef(self, entry, ops, r, k, d_b, ldb, d_x, ldx, tol, maxiter, exact):
+        for t in (d_b, d_x):
+            if hasattr(t, "data_ptr"):
+                self._sync_torch(t)
+        maxiter = int(maxiter)
+        # (a maxiter the library refuses gets no history to size: it is refused there, before anything is written)
+        info = SolveInfo(k, maxiter if 1 <= maxiter <= 65536 else 0)
+        check(self.lib, entry(self.handle, *[o.handle for o in ops], r.handle if r is not None else None, _flags(exact=exact), int(k),
+                              ctypes.c_void_p(_dptr(d_b)), int(ldb), ctypes.c_void_p(_dptr(d_x)), int(ldx), float(tol), maxiter,
+                              _ptr(info.iterations), _ptr(info.status), _ptr(info.residual_sq), _ptr(info.rhs_sq), _ptr(info.alpha),
+                              _ptr(info.beta)))
+        self.synchronize()
+        return info
+
+    def innovation_solve_coef_into(self, h, q, r, d_b, ldb, k, d_x, ldx, tol=1e-8, maxiter=1000, exact=False):
+        """innovation_solve_into that keeps every column's CG coefficients (smm_innovation_solve_coef): info.alpha and
+        info.beta are maxiter x k, row it - 1 holding iteration it, +0.0 where a column computed none.  maxiter must be
+        given as 1 .. 65536: it sizes the histories."""
+        return self._solve_coef(self.lib.smm_innovation_solve_coef, (h, q), r, k, d_b, ldb, d_x, ldx, tol, maxiter, exact)
+
+    def innovation_solve_coef_kron_into(self, h, d, e, r, d_b, ldb, k, d_x, ldx, tol=1e-8, maxiter=1000, exact=False):
+        """The same with Q = D (x) E applied through its factors (smm_innovation_solve_coef_kron)."""
+        return self._solve_coef(self.lib.smm_innovation_solve_coef_kron, (h, d, e), r, k, d_b, ldb, d_x, ldx, tol, maxiter, exact)
+
 
 class SolveInfo:
     """Per-column outcome of innovation_solve: iterations (int32), status (int32: 0 converged, 1 iteration limit,
-    2 breakdown), residual_sq (the recurrence's dot(r, r) at the end) and rhs_sq (dot(d, d)), numpy arrays of k entries."""
+    2 breakdown), residual_sq (the recurrence's dot(r, r) at the end) and rhs_sq (dot(d, d)), numpy arrays of k entries.
+    alpha and beta: None, or -- from the calls that record them -- the maxiter x k CG coefficients (row it - 1, column j)."""
     CONVERGED, ITERATION_LIMIT, BREAKDOWN = 0, 1, 2
 
-    def __init__(self, k):
+    def __init__(self, k, history=None):
         self.iterations = np.zeros(k, dtype=np.int32)
         self.status = np.zeros(k, dtype=np.int32)
         self.residual_sq = np.zeros(k, dtype=np.float64)
         self.rhs_sq = np.zeros(k, dtype=np.float64)
+        self.alpha = self.beta = None
+        if history is not None:
+            self.alpha, self.beta = np.zeros((history, k), dtype=np.float64), np.zeros((history, k), dtype=np.float64)
 
     @property
     def converged(self):

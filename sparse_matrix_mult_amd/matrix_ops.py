@@ -1242,11 +1242,12 @@ def _cg_dot(u, v):
     return s[0]
 
 
-def _cg_on_host(apply, d, tol, maxiter):
+def _cg_on_host(apply, d, tol, maxiter, record=False):
     """The iteration of smm_innovation_solve in numpy, for the systems that never reach the device (S = 0): apply(P)
-    is (S + R) P.  Returns (Z, info)."""
+    is (S + R) P.  Returns (Z, info); with record, info.alpha and info.beta are the maxiter x k histories by the contract
+    of smm_innovation_solve_coef."""
     n, k = d.shape
-    info = SolveInfo(k)
+    info = SolveInfo(k, maxiter if record else None)
     x, r, p = np.zeros((n, k)), d.copy(), d.copy()
     with np.errstate(all="ignore"):
         rho = _cg_dot(r, r)
@@ -1265,6 +1266,8 @@ def _cg_on_host(apply, d, tol, maxiter):
             live = live & ~broke
             j = np.flatnonzero(live)
             alpha = rho[j] / pw[j]
+            if record:
+                info.alpha[it - 1, j] = alpha
             x[:, j] = x[:, j] + alpha * p[:, j]
             r[:, j] = r[:, j] - alpha * w[:, j]
             rho_new = _cg_dot(r[:, j], r[:, j])
@@ -1273,9 +1276,59 @@ def _cg_on_host(apply, d, tol, maxiter):
             info.status[j[done]] = SolveInfo.CONVERGED
             live[j[done]] = False
             j, rho_new = j[~done], rho_new[~done]
-            p[:, j] = r[:, j] + (rho_new / rho[j]) * p[:, j]
+            beta = rho_new / rho[j]
+            if record:
+                info.beta[it - 1, j] = beta
+            p[:, j] = r[:, j] + beta * p[:, j]
             rho[j] = rho_new
     return x, info
+
+
+def _innovation_operands(matrix_h, matrix_q, matrix_r, what):
+    """(H, Q, R, kron, n) of a call on H Q H^T + R: H and Q as CSR or PinnedOperand (Q a KroneckerOperand when kron), R the
+    same, built from its diagonal when a vector, or None.  ValueError for shapes that do not fit."""
+    matrix_h = _as_csr(matrix_h)
+    kron = isinstance(matrix_q, KroneckerOperand)
+    if kron:
+        matrix_q._square(what)
+    else:
+        matrix_q = _as_csr(matrix_q)
+    if matrix_q.shape[0] != matrix_q.shape[1]:
+        raise ValueError(f"{what}: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
+    if matrix_h.shape[1] != matrix_q.shape[0]:
+        raise ValueError("Matrix dimensions are incompatible for multiplication.")
+    n = matrix_h.shape[0]
+    if matrix_r is not None:
+        if not (isspmatrix_csr(matrix_r) or isinstance(matrix_r, PinnedOperand) or hasattr(matrix_r, "tocsr")):
+            dense_r = np.asarray(matrix_r, dtype=np.float64)
+            if dense_r.ndim == 1:                        # the diagonal; zeros stay stored
+                if dense_r.shape[0] != n:
+                    raise ValueError(f"{what}: the diagonal of R has {dense_r.shape[0]} entries, expected {n}")
+                matrix_r = csr_matrix((dense_r, np.arange(n, dtype=np.int32), np.arange(n + 1, dtype=np.int32)), shape=(n, n))
+        matrix_r = _as_csr(matrix_r)
+        if tuple(matrix_r.shape) != (n, n):
+            raise ValueError(f"{what}: R must be {n} x {n}, got {matrix_r.shape[0]} x {matrix_r.shape[1]}")
+    return matrix_h, matrix_q, matrix_r, kron, n
+
+
+def _innovation_tol(tol, what):
+    try:
+        tol = float(tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: tol must be a finite positive number") from None
+    if not (tol > 0.0 and np.isfinite(tol)):
+        raise ValueError(f"{what}: tol must be a finite positive number, got {tol}")
+    return tol
+
+
+def _host_r_apply(matrix_r):
+    """P -> R P on the host, for the systems whose S has no entries (R: CSR, PinnedOperand or None)."""
+    if matrix_r is None:
+        return np.zeros_like
+    if isinstance(matrix_r, PinnedOperand):
+        ctx = default_context()
+        return lambda p: 0.0 + _with_leases(ctx, (matrix_r,), lambda lr: ctx.spmm_host(lr.handle, p, exact=True))
+    return lambda p: 0.0 + np.asarray(matrix_r @ p)
 
 
 def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
@@ -1295,34 +1348,9 @@ def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
     that recipe in IEEE double, otherwise fused multiply-adds are used and two runs still agree bit for bit.  The vectors
     of a block of columns are sized by Context.tune_spmm's apply budget.
     """
-    matrix_h = _as_csr(matrix_h)
-    kron = isinstance(matrix_q, KroneckerOperand)
-    if kron:
-        matrix_q._square("innovation_solve")
-    else:
-        matrix_q = _as_csr(matrix_q)
-    if matrix_q.shape[0] != matrix_q.shape[1]:
-        raise ValueError(f"innovation_solve: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
-    if matrix_h.shape[1] != matrix_q.shape[0]:
-        raise ValueError("Matrix dimensions are incompatible for multiplication.")
-    n = matrix_h.shape[0]
-    if matrix_r is not None:
-        if not (isspmatrix_csr(matrix_r) or isinstance(matrix_r, PinnedOperand) or hasattr(matrix_r, "tocsr")):
-            dense_r = np.asarray(matrix_r, dtype=np.float64)
-            if dense_r.ndim == 1:                        # the diagonal; zeros stay stored
-                if dense_r.shape[0] != n:
-                    raise ValueError(f"innovation_solve: the diagonal of R has {dense_r.shape[0]} entries, expected {n}")
-                matrix_r = csr_matrix((dense_r, np.arange(n, dtype=np.int32), np.arange(n + 1, dtype=np.int32)), shape=(n, n))
-        matrix_r = _as_csr(matrix_r)
-        if tuple(matrix_r.shape) != (n, n):
-            raise ValueError(f"innovation_solve: R must be {n} x {n}, got {matrix_r.shape[0]} x {matrix_r.shape[1]}")
+    matrix_h, matrix_q, matrix_r, kron, n = _innovation_operands(matrix_h, matrix_q, matrix_r, "innovation_solve")
     d, k, is_torch = _dense_operand(d, n, "innovation_solve", "D")
-    try:
-        tol = float(tol)
-    except (TypeError, ValueError):
-        raise ValueError("innovation_solve: tol must be a finite positive number") from None
-    if not (tol > 0.0 and np.isfinite(tol)):
-        raise ValueError(f"innovation_solve: tol must be a finite positive number, got {tol}")
+    tol = _innovation_tol(tol, "innovation_solve")
     if maxiter is None:
         maxiter = n
     if int(maxiter) != maxiter or maxiter < 0:
@@ -1335,14 +1363,7 @@ def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
         return _dense_zeros(tuple(d.shape), on_device), SolveInfo(k)
     if matrix_h.nnz == 0 or matrix_q.nnz == 0:           # S = 0: R Z = D, iterated on the host
         dh = (d.cpu().numpy() if is_torch else d).reshape(n, k)
-        if matrix_r is None:
-            apply = np.zeros_like
-        elif isinstance(matrix_r, PinnedOperand):
-            ctx = default_context()
-            apply = lambda p: 0.0 + _with_leases(ctx, (matrix_r,), lambda lr: ctx.spmm_host(lr.handle, p, exact=True))  # noqa: E731
-        else:
-            apply = lambda p: 0.0 + np.asarray(matrix_r @ p)  # noqa: E731
-        z, info = _cg_on_host(apply, dh, tol, maxiter)
+        z, info = _cg_on_host(_host_r_apply(matrix_r), dh, tol, maxiter)
         z = z.reshape(tuple(d.shape))
         if on_device:
             import torch
@@ -1377,3 +1398,216 @@ def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
 
     mats = (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)) + ((matrix_r,) if matrix_r is not None else ())
     return _with_leases(ctx, mats, body)
+
+
+# ------------------------------------------------------------------ log det(H Q H^T + R) by stochastic Lanczos quadrature
+def _probe_signs(n, k, seed):
+    """The probes of smm_probe_fill in numpy uint64 (include/smm_hip.h): n x k float64 of +-1.0."""
+    u = np.uint64
+    i = np.arange(1, n + 1, dtype=u)[:, None]
+    c = np.arange(k, dtype=u)[None, :]
+    z = np.array([int(seed) % (1 << 64)], dtype=u) + c * u(0xD1B54A32D192ED03) + i * u(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+    z = z ^ (z >> u(31))
+    return np.where((z >> u(63)).astype(bool), -1.0, 1.0)
+
+
+def _slq_column(alpha, beta, m, n):
+    """(sample, theta): n * sum_i V[0, i]^2 ln(theta_i) of the m x m Lanczos tridiagonal that m CG iterations give
+    (T[j, j] = 1/alpha_j + beta_{j-1}/alpha_{j-1}, T[j, j+1] = sqrt(beta_j)/alpha_j), and its eigenvalues (Ritz values).
+    A Ritz value <= 0 makes the sample NaN; m = 0 gives (NaN, empty)."""
+    if m == 0:
+        return np.nan, np.empty(0)
+    a, b = np.asarray(alpha[:m], np.float64), np.asarray(beta[:m], np.float64)
+    with np.errstate(all="ignore"):
+        diag = 1.0 / a
+        diag[1:] = diag[1:] + b[:m - 1] / a[:m - 1]
+        off = np.sqrt(b[:m - 1]) / a[:m - 1]
+        T = np.diag(diag) + np.diag(off, 1) + np.diag(off, -1)
+        if not np.all(np.isfinite(T)):
+            return np.nan, np.empty(0)
+        theta, V = np.linalg.eigh(T)
+        return float(n * np.sum(V[0] ** 2 * np.log(theta))), theta
+
+
+def _info_columns(info, cols):
+    """The SolveInfo of a slice of columns (histories included)."""
+    out = SolveInfo(0)
+    for f in ("iterations", "status", "residual_sq", "rhs_sq"):
+        setattr(out, f, np.ascontiguousarray(getattr(info, f)[cols]))
+    if info.alpha is not None:
+        out.alpha, out.beta = np.ascontiguousarray(info.alpha[:, cols]), np.ascontiguousarray(info.beta[:, cols])
+    return out
+
+
+class LogdetResult:
+    """What innovation_logdet returns: logdet, stderr, samples, lambda_min, lambda_max, info, positive_definite, and --
+    None unless asked for -- Z, info_d (with d) and solutions (with return_solutions)."""
+
+    def __init__(self):
+        self.logdet = self.stderr = self.lambda_min = self.lambda_max = np.nan
+        self.samples = np.empty(0)
+        self.info = self.Z = self.info_d = self.solutions = None
+        self.positive_definite = True
+
+    def __repr__(self):
+        return (f"LogdetResult(logdet={self.logdet!r}, stderr={self.stderr!r}, probes={len(self.samples)}, "
+                f"lambda_min={self.lambda_min!r}, lambda_max={self.lambda_max!r}, positive_definite={self.positive_definite})")
+
+
+def _slq_result(res, info, n):
+    """Fill res from the probe columns' SolveInfo: the tridiagonal quadrature of every probe, on the host."""
+    k = len(info.iterations)
+    res.info = info
+    res.samples = np.full(k, np.nan)
+    lo, hi = np.inf, -np.inf
+    for c in range(k):
+        if info.status[c] == SolveInfo.BREAKDOWN:
+            res.positive_definite = False
+            continue
+        res.samples[c], theta = _slq_column(info.alpha[:, c], info.beta[:, c], int(info.iterations[c]), n)
+        if theta.size:
+            lo, hi = min(lo, float(theta[0])), max(hi, float(theta[-1]))
+    res.lambda_min, res.lambda_max = (lo, hi) if lo <= hi else (np.nan, np.nan)
+    res.logdet = float(np.mean(res.samples)) if res.positive_definite else np.nan
+    res.stderr = float(np.std(res.samples, ddof=1) / np.sqrt(k)) if k > 1 else np.nan
+    return res
+
+
+def innovation_logdet(matrix_h, matrix_q, matrix_r, probes=32, seed=0, tol=1e-8, maxiter=None, d=None, return_solutions=False):
+    """ln det(H Q H^T + R) by stochastic Lanczos quadrature read off the batched CG of innovation_solve; Psi = H Q H^T + R
+    is never formed.  Returns a LogdetResult.
+
+    matrix_h, matrix_q, matrix_r : as in innovation_solve (scipy CSR, PinnedOperand, a KroneckerOperand for Q, a vector for
+               R's diagonal, R = None for S alone).  Psi is expected to be symmetric positive definite.
+    probes   : the number of probes z_c with entries +-1, filled on the device by the hash of include/smm_hip.h from
+               (seed, row, c): the same seed gives the same probes, and column c does not depend on `probes`.
+    tol, maxiter : of the CG on Psi x = z_c; maxiter None means min(n, 1000), at most 65536 (it sizes the recorded histories).
+    d        : optional right-hand sides, n or n x m, numpy or a float64 CUDA tensor.  Their columns go in front of the probes
+               in the same batch, so Z = Psi^-1 d -- the quadratic form of a likelihood -- costs no extra products.  Columns
+               never mix: under set_exact(True) Z and info_d are the bits of innovation_solve(H, Q, R, d).
+    Result fields:
+      logdet    the mean of samples;  stderr  their sample standard deviation / sqrt(probes) (NaN for a single probe)
+      samples   per probe, n * sum_i V[0, i]^2 ln(theta_i): theta and V from numpy.linalg.eigh of the probe's m x m
+                Lanczos tridiagonal (m its CG iterations), T[j, j] = 1/alpha_j + beta_{j-1}/alpha_{j-1},
+                T[j, j+1] = T[j+1, j] = sqrt(beta_j)/alpha_j
+      lambda_min, lambda_max  the extreme Ritz values over all probes (lambda_max converges to Psi's from below within a
+                few iterations; lambda_min stays somewhat above Psi's)
+      info      the SolveInfo of the probe columns, with the recorded alpha and beta (maxiter x probes)
+      Z, info_d with d: of d's kind and shape, as innovation_solve returns them
+      solutions with return_solutions: Psi^-1 times the probes, n x probes -- the input of the trace terms
+                tr(Psi^-1 dPsi/dtheta); a torch tensor under set_result_device(True), numpy otherwise
+      positive_definite  False when a probe broke down (status 2): logdet is then NaN -- the matrix is not positive
+                definite; this is reported, not raised.  A probe that hit the iteration limit (status 1) contributes its
+                m-point quadrature and info.converged is False.
+    alpha and beta come from the device and follow the bit-for-bit contract of innovation_solve (fixed summation order; under
+    set_exact(True) the numpy recipe's bits; otherwise two runs agree bit for bit).  The tridiagonal eigen-decompositions run
+    on the host on purpose -- at most probes * maxiter^2 flops on matrices of a few hundred rows -- and are LAPACK's
+    (numpy.linalg.eigh): samples, logdet and the Ritz values are deterministic on one machine but not part of that contract.
+    n = 0 gives logdet 0.0.  H or Q without entries leaves Psi = R, iterated on the host without a device; R = None is then
+    a ValueError (the matrix is singular).
+    """
+    what = "innovation_logdet"
+    matrix_h, matrix_q, matrix_r, kron, n = _innovation_operands(matrix_h, matrix_q, matrix_r, what)
+    try:
+        ok = int(probes) == probes and probes >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: probes must be a positive integer, got {probes!r}")
+    probes = int(probes)
+    try:
+        seed = int(seed) % (1 << 64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: seed must be an integer, got {seed!r}") from None
+    tol = _innovation_tol(tol, what)
+    if maxiter is None:
+        maxiter = max(1, min(n, 1000))
+    try:
+        ok = int(maxiter) == maxiter and 1 <= maxiter <= 65536
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: maxiter must be an integer in 1 .. 65536, got {maxiter!r}")
+    maxiter = int(maxiter)
+    m, is_torch = 0, False
+    if d is not None:
+        d, m, is_torch = _dense_operand(d, n, what, "D")
+    on_device = is_torch or _result_device
+    if matrix_r is not None and matrix_r.nnz == 0:
+        matrix_r = None
+    res = LogdetResult()
+
+    def finish(z, info):
+        """Split the batch (numpy, or a tensor on the device path) into d's columns and the probes'."""
+        if d is not None:
+            zd = z[:, :m].reshape(tuple(d.shape))
+            res.Z = zd.contiguous() if hasattr(zd, "contiguous") else np.ascontiguousarray(zd)
+            res.info_d = _info_columns(info, slice(0, m))
+        if return_solutions:
+            zs = z[:, m:]
+            res.solutions = zs.contiguous() if hasattr(zs, "contiguous") else np.ascontiguousarray(zs)
+        return _slq_result(res, _info_columns(info, slice(m, m + probes)), n)
+
+    def to_kind(z, want_device):
+        if want_device == hasattr(z, "is_cuda"):
+            return z
+        if want_device:
+            import torch
+            return torch.from_numpy(np.ascontiguousarray(z)).to(torch.device("cuda", default_context().device))
+        return z.cpu().numpy()
+
+    if n == 0:
+        res.info = SolveInfo(probes, maxiter)
+        res.samples = np.zeros(probes)
+        res.logdet, res.stderr = 0.0, (0.0 if probes > 1 else np.nan)
+        if d is not None:
+            res.Z, res.info_d = _dense_zeros(tuple(d.shape), on_device), SolveInfo(m)
+        if return_solutions:
+            res.solutions = _dense_zeros((0, probes), _result_device)
+        return res
+    if matrix_h.nnz == 0 or matrix_q.nnz == 0:           # Psi = R: iterated on the host, as innovation_solve does
+        if matrix_r is None:
+            raise ValueError(f"{what}: H Q H^T has no entries and R is None: the matrix is singular")
+        batch = _probe_signs(n, probes, seed)
+        if d is not None:
+            dh = (d.cpu().numpy() if is_torch else d).reshape(n, m)
+            batch = np.concatenate([dh, batch], axis=1)
+        z, info = _cg_on_host(_host_r_apply(matrix_r), np.ascontiguousarray(batch), tol, maxiter, record=True)
+        finish(z, info)
+        if res.Z is not None:
+            res.Z = to_kind(res.Z, on_device)
+        if res.solutions is not None:
+            res.solutions = to_kind(res.solutions, _result_device)
+        return res
+    ctx = default_context()
+    nq = 2 if kron else 1
+
+    def body(lh, *rest):
+        import torch
+        h, q, lr = lh.handle, [lease.handle for lease in rest[:nq]], rest[nq:]
+        r = lr[0].handle if lr else None
+        dev = torch.device("cuda", ctx.device)
+        if is_torch and d.device != dev:
+            raise ValueError(f"D is on {d.device}, the library works on {dev}")
+        k = m + probes
+        b = torch.empty((n, k), dtype=torch.float64, device=dev)
+        if m:
+            b[:, :m] = (d if is_torch else torch.from_numpy(d).to(dev)).reshape(n, m)
+        ctx.probe_fill_into(b.data_ptr() + 8 * m, k, n, probes, seed)
+        z = torch.empty((n, k), dtype=torch.float64, device=dev)
+        if kron:
+            info = ctx.innovation_solve_coef_kron_into(h, q[0], q[1], r, b, k, k, z, k, tol, maxiter, exact=_exact)
+        else:
+            info = ctx.innovation_solve_coef_into(h, q[0], r, b, k, k, z, k, tol, maxiter, exact=_exact)
+        return z, info
+
+    mats = (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)) + ((matrix_r,) if matrix_r is not None else ())
+    z, info = _with_leases(ctx, mats, body)
+    finish(z, info)
+    if res.Z is not None:
+        res.Z = to_kind(res.Z, on_device)
+    if res.solutions is not None:
+        res.solutions = to_kind(res.solutions, _result_device)
+    return res
