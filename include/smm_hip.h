@@ -142,6 +142,11 @@ int  smm_ctx_tune_stage2(smm_ctx *ctx, int ring);
 /* B's packed payload for the CSR product's piece walk: 1 = 1.5-byte columns ("pack12") where that is smaller (default),
    0 = 16-bit columns always, 2 = pack12 wherever the four-entries-per-lane walk applies.  Results never depend on it. */
 int  smm_ctx_tune_pack(smm_ctx *ctx, int mode);
+/* Where pack12 is chosen: its pieces at a fixed stride (the longest piece's size, a multiple of 128 bytes), addressed by
+   (tile, row) with a 2-byte length table instead of the 8-byte descriptors.  1 = where the strided payload is at most 1.5
+   times the compact one (default), 0 = never, 2 = wherever pack12 is chosen and the payload stays below 2^31 units.
+   Results never depend on it.  Also: env SMM_PACK_STRIDE when the context is created. */
+int  smm_ctx_tune_pack_stride(smm_ctx *ctx, int mode);
 /* Run-time guard of SMM_EXACT.  The exact walk adds the products of one wave-instruction that fall on the same
  * accumulator in ascending lane order (the reference's order, src/sparsework.cpp:59-76) -- a property of
  * gfx950's ds_add_f64 that was measured, not one the ISA promises.  This runs a sub-millisecond kernel that

@@ -55,6 +55,7 @@ V2_PROTOTYPES = {
     "smm_ctx_tune_dense_runs": (ctypes.c_int, [_vp, ctypes.c_int]),
     "smm_ctx_tune_stage2": (ctypes.c_int, [_vp, ctypes.c_int]),
     "smm_ctx_tune_pack": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "smm_ctx_tune_pack_stride": (ctypes.c_int, [_vp, ctypes.c_int]),
     "smm_ctx_set_check": (ctypes.c_int, [_vp, ctypes.c_int]),
     "smm_ctx_release_pool": (ctypes.c_int, [_vp]),
     "smm_ctx_pool_bytes": (_c_i64, [_vp]),

@@ -80,6 +80,8 @@ struct smm_ctx {
     int piece_walk = 1;      // default mode: one piece of B per wave iteration where every piece has <= 256 entries (env SMM_PIECE_WALK=0: chunk walk)
     int pack12 = 1;          // pack12 payload of B (1.5-byte columns, smm_pack12_*) for the CSR product's four-entries-per-lane piece walk: 1 = where it is
                              // smaller than the 16-bit payload, 0 never, 2 wherever that walk applies (env SMM_PACK12, smm_ctx_tune_pack)
+    int pack_stride = 1;     // pack12 pieces at a fixed stride, addressed by row (no descriptor gather in the walk): 1 = where the stride costs at most
+                             // half the compact payload again, 0 never, 2 wherever pack12 is chosen (env SMM_PACK_STRIDE, smm_ctx_tune_pack_stride)
     int sym_max_ws = 0;      // widest column slab of that walk (0 = CCS_MAX_WS); B with more columns is walked slab by slab
                              // (smm_ctx_tune_symbolic; tests set it small to reach the slab path with small matrices)
     int sym_dense = 1;       // symbolic walk over operands with dense runs of columns: 0 never, 1 chosen from B (>= 80 % of the neighbouring
@@ -284,6 +286,7 @@ extern "C" int smm_ctx_create(int device, void *hip_stream, smm_ctx **out)
     if (const char *e = getenv("SMM_SYM_CCS")) c->sym_ccs = atoi(e) != 0;
     if (const char *e = getenv("SMM_PIECE_WALK")) c->piece_walk = atoi(e);
     if (const char *e = getenv("SMM_PACK12")) c->pack12 = std::max(0, std::min(2, atoi(e)));
+    if (const char *e = getenv("SMM_PACK_STRIDE")) c->pack_stride = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("SMM_SYM_MAX_WS")) c->sym_max_ws = std::max(0, std::min(atoi(e), (int)CCS_MAX_WS));
     if (const char *e = getenv("SMM_CHECK")) c->check = atoi(e) != 0;
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -353,9 +356,10 @@ static int take_plan_error(smm_ctx *c, const char *where)
     HIPCHK(hipMemcpyAsync(c->d_err, clean, sizeof(clean), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     static const char *names[] = {"sub-run bounds", "tail descriptor", "slab sub-run table", "start slots", "hash look-up",
-                                  "list capacity", "row counts", "list entries", "ring schedule / progress words of triple-product stage 2"};
+                                  "list capacity", "row counts", "list entries", "ring schedule / progress words of triple-product stage 2",
+                                  "piece lengths of the strided payload"};
     std::string what;
-    for (int b = 0; b < 9; ++b)
+    for (int b = 0; b < 10; ++b)
         if (h[0] & (1u << b)) { if (!what.empty()) what += ", "; what += names[b]; }
     return fail(SMM_ERR_INTERNAL, "%s: inconsistent plan metadata (%s; first at row %u of A) -- the result of this product is not valid; "
                                   "please report this with the operands (SMM_CHECK=1 verifies every plan)", where, what.c_str(), h[1]);
@@ -531,6 +535,14 @@ extern "C" int smm_ctx_tune_pack(smm_ctx *c, int mode)
     CTX_LOCK(c);
     if (mode < 0 || mode > 2) return fail(SMM_ERR_INVALID, "mode must be 0 (never), 1 (where smaller) or 2 (wherever the walk applies)");
     c->pack12 = mode;
+    return SMM_OK;
+}
+extern "C" int smm_ctx_tune_pack_stride(smm_ctx *c, int mode)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    if (mode < 0 || mode > 2) return fail(SMM_ERR_INVALID, "mode must be 0 (never), 1 (where the stride fits the capacity rule) or 2 (wherever pack12 is chosen)");
+    c->pack_stride = mode;
     return SMM_OK;
 }
 extern "C" int smm_ctx_tune_shared(smm_ctx *c, int lds_cols, int waves)
@@ -807,11 +819,18 @@ struct smm_csr {
     };
     // packed tile-major payload (smm_pack_*), one entry per (tile geometry, format); maxlen: longest piece (fmt 0: entries;
     // PACK_FMT_12: slots n).  A pack12 entry always holds the counts it was judged by (units16 / units12: the operand as
-    // either format, in 8-byte units) and its arrays only once a product chose it.
-    struct PackView { int wc, nct; int2 *desc; double *pay; int maxlen; int fmt; };
+    // either format, in 8-byte units) and its arrays only once a product chose it.  It can hold its pieces twice: back to
+    // back behind descriptors (desc / pay) and at a fixed stride behind a length table (len16 / spay, stride in units;
+    // see smm_pack12_len16) -- each built when a product first chooses it, so both only after SMM_PACK_STRIDE changed.
+    struct PackView { int wc, nct; int2 *desc; double *pay; int maxlen; int fmt; unsigned short *len16 = nullptr; int stride = 0; };
     struct PackCache {
         int wc, nct; const int *seg; DevBuf<int2> desc; DevBuf<double> pay; int maxlen; int fmt; int64_t units16, units12;
-        PackView view() const { return {wc, nct, desc, pay, maxlen, fmt}; }
+        DevBuf<unsigned short> len16; DevBuf<double> spay; int stride = 0;
+        PackView view(bool strided = false) const
+        {
+            if (strided) return {wc, nct, nullptr, spay, maxlen, fmt, len16, stride};
+            return {wc, nct, desc, pay, maxlen, fmt, nullptr, 0};
+        }
     };
     // chunk-padded 16-bit column stream per column slab (smm_ccs_*): the symbolic phase's gather stream
     // (same_word: share of neighbouring entries in one bitmap word)
@@ -958,7 +977,7 @@ extern "C" int64_t smm_csr_device_bytes(const smm_csr *m)
     for (auto &e : m->segs) total += e.seg.bytes;
     for (auto &e : m->locs) total += e.loc.bytes;
     for (auto &e : m->slabs) total += e.soff.bytes + e.scol.bytes + e.sval.bytes;
-    for (auto &e : m->packs) total += e.desc.bytes + e.pay.bytes;
+    for (auto &e : m->packs) total += e.desc.bytes + e.pay.bytes + e.len16.bytes + e.spay.bytes;
     for (auto &e : m->ccs) total += e.cptr.bytes + e.stream.bytes;
     total += m->ell.off.bytes + m->ell.col.bytes + m->ell.val.bytes;
     total += m->ring.off.bytes + m->ring.col.bytes + m->ring.val.bytes + m->ring.hdr.bytes;
@@ -1363,13 +1382,19 @@ static int scan_launch(smm_ctx *c, int64_t n, const T *in, int64_t *out)
 // Packed tile-major payload of B for the shared-tile walk (smm_pack_* / smm_pack12_* in smm_kernels.hpp), cached per
 // (geometry, format).
 // pack_fill: the payload of e from b's current values (pack12: +0.0 into the mid-piece pads as well); queued, not checked.
-static void pack_fill(smm_ctx *c, const smm_csr *b, const smm_csr::PackCache &e)
+// which: an entry that holds its pieces both back to back and strided re-fills both on a value update, a build fills its own.
+enum { FILL_COMPACT = 1, FILL_STRIDED = 2, FILL_ALL = 3 };
+static void pack_fill(smm_ctx *c, const smm_csr *b, const smm_csr::PackCache &e, int which = FILL_ALL)
 {
     const int64_t cells = (int64_t)e.nct * b->rows;
-    if (cells <= 0 || !e.pay) return;
+    if (cells <= 0) return;
+    if (e.fmt == PACK_FMT_12 && e.spay && (which & FILL_STRIDED))
+        LAUNCH(c, "smm_pack12_fill", smm_pack12_fill, std::min<int64_t>((cells + 3) / 4, 65536), 256, 0, (int)b->rows, e.nct, e.wc, b->idx, b->val, e.seg,
+               (const int2 *)nullptr, e.spay.p, e.stride, (const unsigned short *)e.len16);
+    if (!e.pay || !(which & FILL_COMPACT)) return;
     if (e.fmt == PACK_FMT_12)
         LAUNCH(c, "smm_pack12_fill", smm_pack12_fill, std::min<int64_t>((cells + 3) / 4, 65536), 256, 0, (int)b->rows, e.nct, e.wc, b->idx, b->val, e.seg,
-               (const int2 *)e.desc, e.pay.p);
+               (const int2 *)e.desc, e.pay.p, 0, (const unsigned short *)nullptr);
     else
         LAUNCH(c, "smm_pack_fill", smm_pack_fill, std::min<int64_t>((b->rows + 3) / 4, 65536), 256, 0, (int)b->rows, e.nct, e.wc, b->ptr,
                b->idx, b->val, e.seg, (const int2 *)e.desc, e.pay.p);
@@ -1381,7 +1406,18 @@ static bool pack12_chosen(const smm_ctx *c, const smm_csr::PackCache &e)
     if (c->pack12 == 0 || !c->piece_walk || e.maxlen <= 128 || e.maxlen > 256) return false;
     return c->pack12 == 2 || e.units12 < e.units16;
 }
-// Count b's pieces as pack12 into e (a new entry, or one that holds no arrays yet) and build its arrays where the rule chooses it.
+// The stride rule: pack12 is chosen, the strided payload (the longest piece's units for every piece) stays below 2^31
+// units and, unless forced (mode 2), it is at most 1.5 times the compact one -- a condition on capacity, not a tuned
+// number: one very long row must not multiply the operand's footprint.
+static int64_t stride_units(const smm_csr::PackCache &e, int64_t rows) { return (int64_t)pack12_units(e.maxlen) * rows * e.nct; }
+static bool stride_chosen(const smm_ctx *c, const smm_csr::PackCache &e, int64_t rows)
+{
+    if (c->pack_stride == 0 || !pack12_chosen(c, e)) return false;
+    const int64_t total = stride_units(e, rows);
+    if (total + PACK12_STRIDE_SLACK >= INT32_MAX) return false;
+    return c->pack_stride == 2 || 2 * total <= 3 * e.units12;
+}
+// Count b's pieces as pack12 into e (a new entry, or one that lacks the arrays the rules choose now) and build them.
 static int pack12_prepare(smm_ctx *c, smm_csr *b, smm_csr::PackCache &e)
 {
     const int64_t cells = (int64_t)e.nct * b->rows;
@@ -1401,14 +1437,25 @@ static int pack12_prepare(smm_ctx *c, smm_csr *b, smm_csr::PackCache &e)
     HIPCHK(hipMemcpyAsync(stat, d_stat, sizeof(stat), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     e.maxlen = (int)stat[0]; e.units16 = (int64_t)stat[1]; e.units12 = (int64_t)stat[2];
-    if (pack12_chosen(c, e)) {
+    if (stride_chosen(c, e, b->rows)) {
+        if (!e.spay) {
+            e.stride = pack12_units(e.maxlen);
+            if (e.len16.alloc(c, (size_t)std::max<int64_t>(cells, 1)) != hipSuccess || e.spay.alloc(c, (size_t)(stride_units(e, b->rows) + PACK12_STRIDE_SLACK)) != hipSuccess) {
+                e.len16.reset(); e.spay.reset();
+                return fail(SMM_ERR_ALLOC, "hipMalloc of the packed payload failed");
+            }
+            LAUNCH(c, "smm_pack12_len16", smm_pack12_len16, (cells + 255) / 256, 256, 0, cells, (const int *)n12, e.len16.p);
+            pack_fill(c, b, e, FILL_STRIDED);
+            LAUNCH_CHECK();
+        }
+    } else if (pack12_chosen(c, e) && !e.pay) {
         if (e.units12 >= INT32_MAX) return fail(SMM_ERR_INVALID, "operand too large for the packed payload");
         CHK(scan_launch<int>(c, cells, units, off64));
         // (+ 4 units of slack, as for the 16-bit payload)
         if (e.desc.alloc(c, (size_t)std::max<int64_t>(cells, 1)) != hipSuccess || e.pay.alloc(c, (size_t)(std::max<int64_t>(e.units12, 1) + 4)) != hipSuccess)
             return fail(SMM_ERR_ALLOC, "hipMalloc of the packed payload failed");
         LAUNCH(c, "smm_pack12_desc", smm_pack12_desc, (cells + 255) / 256, 256, 0, cells, (const int64_t *)off64, (const int *)n12, e.desc.p);
-        pack_fill(c, b, e);
+        pack_fill(c, b, e, FILL_COMPACT);
         LAUNCH_CHECK();
     }
     HIPCHK(hipStreamSynchronize(c->stream));            // units / n12 / off64 go back to the pool
@@ -1430,10 +1477,13 @@ static int ensure_pack(smm_ctx *c, smm_csr *b, const Geom &g, int fmt, smm_csr::
             CHK(ensure_seg(c, b, tiles_geom(g.nct, g.wc), &e.seg));
             CHK(pack12_prepare(c, b, e));
             b->packs.push_back(std::move(e));
-        } else if (!b->packs[at].pay && pack12_chosen(c, b->packs[at])) {
-            CHK(pack12_prepare(c, b, b->packs[at]));       // (judged under another SMM_PACK12 mode before)
+        } else if (pack12_chosen(c, b->packs[at]) && (stride_chosen(c, b->packs[at], b->rows) ? !b->packs[at].spay : !b->packs[at].pay)) {
+            CHK(pack12_prepare(c, b, b->packs[at]));       // (judged under another SMM_PACK12 / SMM_PACK_STRIDE mode before)
         }
-        if (b->packs[at].pay && pack12_chosen(c, b->packs[at])) { *out = b->packs[at].view(); return SMM_OK; }
+        if (pack12_chosen(c, b->packs[at])) {
+            const bool strided = stride_chosen(c, b->packs[at], b->rows);
+            if (strided ? (bool)b->packs[at].spay : (bool)b->packs[at].pay) { *out = b->packs[at].view(strided); return SMM_OK; }
+        }
     }
     for (auto &e : b->packs)
         if (e.wc == g.wc && e.nct == g.nct && e.fmt == PACK_FMT_16) { *out = e.view(); return SMM_OK; }
@@ -1759,6 +1809,13 @@ static int plan_check(smm_ctx *c, smm_plan *p)
             LAUNCH(c, "smm_plan_check", smm_plan_check_runs<int>, rgrid, 256, 0, nd, p->g.nct, p->g.wc, rows, a->ptr,
                    (const int64_t *)p->d_ub_off, (const int *)p->d_rowcnt, (const unsigned *)p->d_P, (const int *)p->d_tmp,
                    (const unsigned *)p->d_runs, (const int2 *)p->d_tail, c->d_err);
+        LAUNCH_CHECK();
+    }
+    if (p->pack.stride > 0 && p->pack.len16 && p->b) {
+        const int64_t cells = (int64_t)p->pack.nct * p->b->rows;
+        if (cells > 0)
+            LAUNCH(c, "smm_plan_check", smm_plan_check_len16, (int)std::min<int64_t>((cells + 255) / 256, 16384), 256, 0, cells, p->pack.maxlen,
+                   (const unsigned short *)p->pack.len16, c->d_err);
         LAUNCH_CHECK();
     }
     return take_plan_error(c, "smm_plan_check");
@@ -2223,6 +2280,7 @@ extern "C" int smm_spgemm_numeric(smm_ctx *c, smm_plan *p, int64_t *d_c_indptr, 
         A.tdesc = p->pack.desc; A.tpay = p->pack.pay;
         A.piece_epl = !c->piece_walk || !p->pack.pay ? 0 : (p->pack.maxlen <= 128 ? 2 : (p->pack.maxlen <= 256 ? 4 : 0));
         A.piece_fmt = p->pack.fmt;
+        A.tstride = p->pack.stride; A.tlen16 = p->pack.len16;
         if (A.piece_fmt == PACK_FMT_12 && A.piece_epl != 4) return fail(SMM_ERR_INTERNAL, "pack12 payload without the four-entries-per-lane walk");
         A.rowsB = (int)p->b->rows;
         A.c_ptr = p->d_cptr; A.c_idx = d_c_indices; A.c_val = d_c_data;

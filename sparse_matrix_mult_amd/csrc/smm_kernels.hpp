@@ -51,6 +51,7 @@ enum {
     PLAN_ERR_CAP = 32,      // negative / overlapping list capacity, or a list longer than its capacity
     PLAN_ERR_COUNT = 64,    // row counts do not add up to the row pointer
     PLAN_ERR_LIST = 128,    // a list entry is not a column of the (slab of the) result, or not in its sub-run's tile
+    PLAN_ERR_PIECE = 512,   // strided pack12 payload: a piece's length is above what its stride holds (256 is PLAN_ERR_RING, smm_ring.hpp)
 };
 #ifndef SMM_CLAMPS
 #define SMM_CLAMPS 1       // 0: a diagnostic build without the always-on clamps (A/B of their cost; never shipped)
@@ -420,7 +421,7 @@ __device__ __forceinline__ int pack12_walk(const int *__restrict__ idx, const in
     }
     return slot;
 }
-__device__ __forceinline__ int pack12_units(const int n) {
+__host__ __device__ __forceinline__ int pack12_units(const int n) {
     const int g = (n + 3) >> 2;
     return (n + ((6 * g + 7) >> 3) + (SMM_PACK_ALIGN - 1)) & ~(SMM_PACK_ALIGN - 1);
 }
@@ -457,6 +458,21 @@ __global__ __launch_bounds__(256) void smm_pack12_desc(int64_t cells, const int6
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid < cells) desc[gid] = make_int2((int)off[gid], n12[gid]);
 }
+// "Strided pack12": the same pieces, byte for byte, at a fixed stride instead of back to back.  stride = the longest
+// piece's pack12_units (a multiple of SMM_PACK_ALIGN units = 128 bytes; pack12_units grows with n, so the longest n
+// decides), piece (tile t, row k) starts at unit (t * rows + k) * stride, and the only table is len16[t * rows + k] = n
+// (n <= 256).  The walk's piece address is then arithmetic: the 8-byte descriptor gather (one scattered line per lane,
+// rows x 8 B per tile) becomes a 2-byte one into a table a quarter the size.  The lines between a piece's end and the
+// next piece's start are never written and never read: the stride costs capacity, not traffic.  Chosen per operand on
+// the host (ensure_pack); restated in plain Python in tests/piece_stride_restatement.py.
+// Units behind the last piece's start that the walk can touch with n clamped to 256: 64 x 32 B of values, then plane D
+// (256 B) and plane H (128 B) behind 256 value slots = 2432 B.
+constexpr int PACK12_STRIDE_SLACK = 304;
+__global__ __launch_bounds__(256) void smm_pack12_len16(int64_t cells, const int *__restrict__ n12, unsigned short *__restrict__ len16)
+{
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid < cells) len16[gid] = (unsigned short)n12[gid];
+}
 // One wave per piece, 64 entries at a time; writes every value slot (mid-piece pads: +0.0) and every field of both
 // planes (trailing pads included): nothing relies on what the buffer held.  A window starts at a group's slot 0, so its
 // slots depend on nothing before it; lane l takes entry l, slot = first slot + l, and every entry that comes more than
@@ -464,8 +480,10 @@ __global__ __launch_bounds__(256) void smm_pack12_desc(int64_t cells, const int6
 // wave-uniform loop over those entries: there are next to none).  The lane that holds a group's slot 0 builds the
 // group's two words from the three lanes after it, so only groups whose slot 0 sits in lanes 0..60 are written in this
 // window and the next one starts at the first group that was not.
+// stride > 0: the strided payload -- the piece starts at unit cell * stride and its n comes from len16 (desc unused).
 __global__ __launch_bounds__(256) void smm_pack12_fill(int rows, int nct, int wc, const int *__restrict__ idx, const double *__restrict__ val,
-                                                       const int *__restrict__ seg, const int2 *__restrict__ desc, double *__restrict__ pay)
+                                                       const int *__restrict__ seg, const int2 *__restrict__ desc, double *__restrict__ pay,
+                                                       int stride, const unsigned short *__restrict__ len16)
 {
     const int lane = lane_id();
     const int wpb = blockDim.x / WAVE;
@@ -474,7 +492,9 @@ __global__ __launch_bounds__(256) void smm_pack12_fill(int rows, int nct, int wc
         const int t = (int)(cell / rows), j = (int)(cell % rows);
         const int *sp = seg + (size_t)j * (nct + 1) + t;
         const int k0 = sp[0], k1 = sp[1], lo_c = t * wc;
-        const int2 d = desc[cell];
+        int2 d;
+        if (stride > 0) d = make_int2((int)(cell * stride), (int)len16[cell]);      // (cells * stride < 2^31: ensure_pack)
+        else d = desc[cell];
         const int n = d.y, ng = (d.y + 3) >> 2;
         if (n <= 0 || k1 <= k0) continue;
         double *__restrict__ v = pay + d.x;
@@ -1584,6 +1604,8 @@ struct NumericArgs {
     const int2 *tdesc; const double *tpay; int rowsB;   // packed tile-major payload (smm_pack_*): the shared-tile walk
     int piece_epl;                  // 2 / 4: every piece of the payload has <= 128 / 256 entries -> smm_accumulate_pieces; 0: chunk walk
     int piece_fmt;                  // 0: 16-bit tile-local columns; 1: pack12 planes (piece_epl == 4, CSR output only)
+    int tstride;                    // pack12 only: > 0 = strided payload, piece (t, k) at unit (t * rowsB + k) * tstride, tdesc unused
+    const unsigned short *tlen16;   //   ... [nct][rowsB] n of every piece
     const int *seg;                 // [rowsB][n_ft+1]
     int kmax;                       // last valid position of b_loc / b_val (exact walk: lanes past a stream's end read it)
     const int *dummy_idx;           // one int  = -1   (read by inactive lanes; its low half is the int16 -1)
@@ -1860,12 +1882,15 @@ __device__ __forceinline__ void wait_vm_n(int n) {
 }
 // FMT 1 (EPL 4 only): the piece's columns are pack12 planes (see smm_pack12_fill) -- four loads per piece, the columns
 // decoded per lane: one mask, three field extracts, three adds, three pad selects.
-template <bool SYM, int NW, int EPL, int U, int FMT = 0>
+// STRIDED (FMT 1 only): the piece's first unit is (tc * rowsB + r) * tstride and only its n is looked up (tlen16): no
+// descriptor gather in front of the piece loads.  Everything behind s_l / n_l is the same code.
+template <bool SYM, int NW, int EPL, int U, int FMT = 0, bool STRIDED = false>
 __device__ __forceinline__ void smm_accumulate_pieces(const NumericArgs &A, double *__restrict__ acc, const int thresh,
                                                       const int a0, const int a1, const int tc, const int wave)
 {
     static_assert(EPL == 2 || EPL == 4, "entries per lane");
     static_assert(FMT == 0 || EPL == 4, "pack12 pieces are walked four entries per lane");
+    static_assert(!STRIDED || FMT == 1, "only the pack12 payload has a strided layout");
     constexpr int LPP = FMT ? 4 : (EPL == 4 ? 3 : 2);       // loads per piece
     const int lane = lane_id();
     const int2 *__restrict__ desc = A.tdesc + (size_t)tc * A.rowsB;
@@ -1880,8 +1905,19 @@ __device__ __forceinline__ void smm_accumulate_pieces(const NumericArgs &A, doub
         const int ec = ev ? e : a1 - 1;
         const int r = A.a_idx[ec];
         const double av = A.a_val[ec];
-        const int2 d = desc[r];                             // {first 8-byte unit of the piece, entries}
-        const int s_l = d.x, n_l = ev ? d.y : 0;
+        int s_l, n_l;
+        if constexpr (STRIDED) {
+            const int cell = tc * A.rowsB + r;              // (cells and cells * tstride < 2^31: ensure_pack)
+            int n = (int)A.tlen16[cell];
+            // Whatever the table holds, the loads stay inside the payload and its slack (PACK12_STRIDE_SLACK).  A length above
+            // the stride's capacity is PLAN_ERR_PIECE in the plan checker; reporting it from here (an atomic behind a test
+            // of n against the capacity, or a flag carried to the end of the walk) costs six VGPRs and an occupancy step.
+            n = n > WAVE * EPL ? WAVE * EPL : n;
+            s_l = cell * A.tstride; n_l = ev ? n : 0;
+        } else {
+            const int2 d = desc[r];                         // {first 8-byte unit of the piece, entries}
+            s_l = d.x; n_l = ev ? d.y : 0;
+        }
         int cnt = (a1 - rb - wave + NW - 1) / NW;           // this wave's entries of the round (wave-uniform)
         cnt = cnt < 0 ? 0 : (cnt > WAVE ? WAVE : cnt);
         for (int i0 = 0; i0 < cnt; i0 += U) {
@@ -2087,6 +2123,7 @@ __device__ __forceinline__ void smm_numeric_unit(const NumericArgs &A, double *_
                 smm_accumulate<SYM>(A, acc, scr + wave, (double *)(scr + NW), thresh, a0, a1, tc * NW + wave);
                 wait_lgkm0();                   // its hand-issued ds_add's (the compiler does not count them)
             }
+            else if (OUT == OUT_SPARSE && A.piece_epl == 4 && A.piece_fmt == 1 && A.tstride > 0) smm_accumulate_pieces<SYM, NW, 4, SMM_PIECE_U_SPARSE, 1, true>(A, acc, thresh, a0, a1, tc, wave);
             else if (OUT == OUT_SPARSE && A.piece_epl == 4 && A.piece_fmt == 1) smm_accumulate_pieces<SYM, NW, 4, SMM_PIECE_U_SPARSE, 1>(A, acc, thresh, a0, a1, tc, wave);
             else if (A.piece_epl == 4) smm_accumulate_pieces<SYM, NW, 4, (OUT == OUT_DENSE ? SMM_PIECE_U_DENSE : SMM_PIECE_U_SPARSE)>(A, acc, thresh, a0, a1, tc, wave);
             else if (A.piece_epl == 2) smm_accumulate_pieces<SYM, NW, 2, (OUT == OUT_DENSE ? SMM_PIECE_U_DENSE : SMM_PIECE_U_SPARSE)>(A, acc, thresh, a0, a1, tc, wave);
@@ -3539,6 +3576,12 @@ __global__ __launch_bounds__(256) void smm_plan_check_runs2(int nrows, int m, in
         if (covered != rowlen) bad |= PLAN_ERR_RUNS2;
         if (bad) plan_err(err, bad, row);
     }
+}
+// the strided pack12 payload's length table: no piece longer than its stride holds
+__global__ __launch_bounds__(256) void smm_plan_check_len16(int64_t cells, int nmax, const unsigned short *__restrict__ len16, unsigned *__restrict__ err)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cells; i += (int64_t)gridDim.x * blockDim.x)
+        if ((int)len16[i] > nmax) plan_err(err, PLAN_ERR_PIECE, 0);
 }
 
 // Test hook (smm_plan_inject_fault): damage ONE piece of a plan's metadata the way a defect in the kernel that

@@ -111,6 +111,11 @@ class Context:
         0 = 16-bit columns always, 2 = pack12 wherever the four-entries-per-lane walk applies."""
         check(self.lib, self.lib.smm_ctx_tune_pack(self.handle, int(mode)))
 
+    def tune_pack_stride(self, mode=1):
+        """pack12 pieces at a fixed stride, addressed by row behind a 2-byte length table: 1 = where the strided payload is at
+        most 1.5 times the compact one (default), 0 = never, 2 = wherever pack12 is chosen."""
+        check(self.lib, self.lib.smm_ctx_tune_pack_stride(self.handle, int(mode)))
+
     def exact_selftest(self, inject_fault=False):
         """Run the SMM_EXACT guard now (every context runs it by itself before its first exact product):
         raises SmmError (code SMM_ERR_UNSUPPORTED) where the device does not add same-address lanes of one
