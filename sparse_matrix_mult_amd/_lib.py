@@ -33,6 +33,9 @@ SMM_ERR_INTERNAL = -7
 _c_i64 = ctypes.c_int64
 _vp = ctypes.c_void_p
 _pp = ctypes.POINTER(ctypes.c_void_p)
+# the argument tails of the entries that take one row-major block in and give one out, behind the context and the operands
+_BLOCKS = [ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]                  # flags, k, in, ld_in, out, ld_out
+_SOLVE = _BLOCKS + [ctypes.c_double, _c_i64, _vp, _vp, _vp, _vp]            # tol, maxiter, the four per-column outputs
 
 # name -> (restype, argtypes); every v2 symbol declared in include/smm_hip.h
 V2_PROTOTYPES = {
@@ -104,35 +107,29 @@ V2_PROTOTYPES = {
     "smm_spgemm_masked": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "smm_spgemm_masked_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "smm_ctx_tune_masked": (ctypes.c_int, [_vp, ctypes.c_int]),
-    "smm_spmm": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
-    "smm_spmm_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
-    "smm_triple_apply": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
-    "smm_triple_apply_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
+    "smm_spmm": (ctypes.c_int, [_vp] * 2 + _BLOCKS),
+    "smm_spmm_host": (ctypes.c_int, [_vp] * 2 + _BLOCKS),
+    "smm_triple_apply": (ctypes.c_int, [_vp] * 3 + _BLOCKS),
+    "smm_triple_apply_host": (ctypes.c_int, [_vp] * 3 + _BLOCKS),
     "smm_ctx_tune_spmm": (ctypes.c_int, [_vp, ctypes.c_int, _c_i64]),
-    "smm_sddmm": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp]),
-    "smm_sddmm_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "smm_sddmm": (ctypes.c_int, [_vp] * 2 + _BLOCKS + [_vp]),
+    "smm_sddmm_host": (ctypes.c_int, [_vp] * 2 + _BLOCKS + [_vp]),
     "smm_ctx_tune_sddmm": (ctypes.c_int, [_vp, ctypes.c_int]),
     "smm_taper_build": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64, _pp]),
     "smm_taper_build_host": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64,
                                             _pp]),
-    "smm_innovation_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_double,
-                                            _c_i64, _vp, _vp, _vp, _vp]),
-    "smm_innovation_solve_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_double,
-                                                 _c_i64, _vp, _vp, _vp, _vp]),
+    "smm_innovation_solve": (ctypes.c_int, [_vp] * 4 + _SOLVE),
+    "smm_innovation_solve_host": (ctypes.c_int, [_vp] * 4 + _SOLVE),
     "smm_kron_build": (ctypes.c_int, [_vp, _vp, _vp, _pp]),
-    "smm_kron_apply": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
-    "smm_kron_apply_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
-    "smm_triple_apply_kron": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
-    "smm_triple_apply_kron_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]),
-    "smm_innovation_solve_kron": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_double,
-                                                 _c_i64, _vp, _vp, _vp, _vp]),
-    "smm_innovation_solve_kron_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64,
-                                                      ctypes.c_double, _c_i64, _vp, _vp, _vp, _vp]),
+    "smm_kron_apply": (ctypes.c_int, [_vp] * 3 + _BLOCKS),
+    "smm_kron_apply_host": (ctypes.c_int, [_vp] * 3 + _BLOCKS),
+    "smm_triple_apply_kron": (ctypes.c_int, [_vp] * 4 + _BLOCKS),
+    "smm_triple_apply_kron_host": (ctypes.c_int, [_vp] * 4 + _BLOCKS),
+    "smm_innovation_solve_kron": (ctypes.c_int, [_vp] * 5 + _SOLVE),
+    "smm_innovation_solve_kron_host": (ctypes.c_int, [_vp] * 5 + _SOLVE),
     "smm_probe_fill": (ctypes.c_int, [_vp, _c_i64, _c_i64, ctypes.c_uint64, _vp, _c_i64]),
-    "smm_innovation_solve_coef": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_double,
-                                                 _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "smm_innovation_solve_coef_kron": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64,
-                                                      ctypes.c_double, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smm_innovation_solve_coef": (ctypes.c_int, [_vp] * 4 + _SOLVE + [_vp, _vp]),
+    "smm_innovation_solve_coef_kron": (ctypes.c_int, [_vp] * 5 + _SOLVE + [_vp, _vp]),
     "smm_device_malloc": (ctypes.c_int, [_vp, _c_i64, _pp]),
     "smm_device_free": (ctypes.c_int, [_vp, _vp]),
     "smm_memcpy_d2h": (ctypes.c_int, [_vp, _vp, _vp, _c_i64]),

@@ -3530,40 +3530,28 @@ static bool ranges_overlap(const void *p, int64_t pb, const void *q, int64_t qb)
     return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
 }
 
-// Arguments common to smm_spmm[_host]: flags, operand, sizes.
-static int spmm_args(smm_ctx *c, smm_csr *a, int flags, int64_t k, int64_t ldx, int64_t ldy, const char *where)
+// The one size check of a pair of row-major blocks: 0 <= k <= both leading dimensions, under the names the header gives them.
+static int dense_dims(const char *where, int64_t k, int64_t ld_a, int64_t ld_b, const char *name_a = "ldx", const char *name_b = "ldy")
 {
-    if (flags & ~(SMM_EXACT | SMM_TRANSPOSE)) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT and SMM_TRANSPOSE are flags of this call", where);
-    if (!a) return fail(SMM_ERR_INVALID, "%s: NULL operand", where);
-    if (a->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
-    if (k < 0 || ldx < k || ldy < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldx, ldy (k %lld, ldx %lld, ldy %lld)", where,
-                                                 (long long)k, (long long)ldx, (long long)ldy);
-    HIPCHK(hipSetDevice(c->device));
-    CHK(validate(c, a));
-    return SMM_OK;
-}
-// Device buffers of Y = op X: present where they hold anything, and apart.
-static int spmm_buffers(int64_t m, int64_t kx, int64_t k, const double *x, int64_t ldx, const double *y, int64_t ldy, const char *where)
-{
-    const int64_t xb = span_bytes(kx, k, ldx), yb = span_bytes(m, k, ldy);
-    if ((xb > 0 && !x) || (yb > 0 && !y)) return fail(SMM_ERR_INVALID, "%s: X or Y is NULL", where);
-    if (ranges_overlap(x, xb, y, yb)) return fail(SMM_ERR_INVALID, "%s: the device ranges of X and Y overlap", where);
+    if (k < 0 || ld_a < k || ld_b < k)
+        return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= %s, %s (k %lld, %s %lld, %s %lld)", where, name_a, name_b, (long long)k, name_a,
+                    (long long)ld_a, name_b, (long long)ld_b);
     return SMM_OK;
 }
 
-extern "C" int smm_spmm(smm_ctx *c, smm_csr *a, int flags, int64_t k, const double *d_x, int64_t ldx, double *d_y, int64_t ldy)
+constexpr bool ON_DEVICE = false, ON_HOST = true;               // where an entry's two blocks live: the `host` of what follows
+// The two blocks of an entry, in (in_rows x k) and out (out_rows x k): present where they hold anything and, on the device,
+// apart.  Host blocks of one height n (the triple apply, the solve) hold data both or neither, so for them this is
+// span_bytes(n, k, max(ld_in, ld_out)) > 0 && (!in || !out).  out_always: a NULL out is refused even where it would hold
+// nothing -- the rule of the _coef entries alone (include/smm_hip.h); the plain solves take one with k == 0.
+static int blocks_check(const char *where, bool host, const double *in, int64_t in_rows, int64_t ld_in, const double *out, int64_t out_rows,
+                        int64_t ld_out, int64_t k, const char *name_in, const char *name_out, bool out_always = false)
 {
-    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
-    CTX_LOCK(c);
-    CHK(spmm_args(c, a, flags, k, ldx, ldy, "smm_spmm"));
-    const bool tr = (flags & SMM_TRANSPOSE) != 0;
-    const int64_t m = tr ? a->cols : a->rows, kx = tr ? a->rows : a->cols;
-    CHK(spmm_buffers(m, kx, k, d_x, ldx, d_y, ldy, "smm_spmm"));
-    if (m == 0 || k == 0) return SMM_OK;
-    const smm_csr *op = nullptr;
-    CHK(spmm_op(c, a, tr, &op));
-    CHK(spmm_impl(c, op, (flags & SMM_EXACT) != 0, k, d_x, ldx, d_y, ldy));
-    return take_plan_error(c, "smm_spmm");
+    const int64_t ib = span_bytes(in_rows, k, ld_in), ob = span_bytes(out_rows, k, ld_out);
+    if ((ib > 0 && !in) || ((ob > 0 || out_always) && !out)) return fail(SMM_ERR_INVALID, "%s: %s or %s is NULL", where, name_in, name_out);
+    if (!host && ranges_overlap(in, ib, out, ob))
+        return fail(SMM_ERR_INVALID, "%s: the device ranges of %s and %s overlap", where, name_in, name_out);
+    return SMM_OK;
 }
 
 // Host rows x k (leading dimension ld) <-> packed device rows x k.
@@ -3586,24 +3574,60 @@ static int download_rows(smm_ctx *c, double *h, const double *d, int64_t rows, i
     return SMM_OK;
 }
 
+// body(d_in, ld_in, d_out, ld_out) on an entry's checked blocks, then the error word of its kernels.  Device blocks go to body as
+// they are.  Host blocks are staged through packed pool copies: an empty problem returns before anything is allocated; the
+// input's copy is allocated first, then the output's, then whatever body takes.
+template <typename Body>
+static int blocks_run(smm_ctx *c, const char *where, bool host, const double *in, int64_t in_rows, int64_t ld_in, double *out, int64_t out_rows,
+                      int64_t ld_out, int64_t k, Body body)
+{
+    if (!host) {
+        CHK(body(in, ld_in, out, ld_out));
+        return take_plan_error(c, where);
+    }
+    if (out_rows == 0 || k == 0) return SMM_OK;
+    PoolBuf<double> d_in(c), d_out(c);
+    CHK(d_in.alloc((size_t)std::max<int64_t>(in_rows * k, 1)));   // (op(A) without columns: in_rows 0; else in_rows * k as it is)
+    CHK(d_out.alloc((size_t)(out_rows * k)));
+    CHK(upload_rows(c, d_in, in, in_rows, k, ld_in));
+    CHK(body(d_in, k, d_out, k));
+    CHK(take_plan_error(c, where));
+    return download_rows(c, out, d_out, out_rows, k, ld_out);
+}
+
+// smm_spmm[_host]: flags, operand and sizes, then Y = op(A) X on the device's or the host's blocks.
+static int spmm_entry(smm_ctx *c, smm_csr *a, int flags, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy, bool host,
+                      const char *where)
+{
+    if (flags & ~(SMM_EXACT | SMM_TRANSPOSE)) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT and SMM_TRANSPOSE are flags of this call", where);
+    if (!a) return fail(SMM_ERR_INVALID, "%s: NULL operand", where);
+    if (a->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
+    CHK(dense_dims(where, k, ldx, ldy));
+    HIPCHK(hipSetDevice(c->device));
+    CHK(validate(c, a));
+    const bool tr = (flags & SMM_TRANSPOSE) != 0, exact = (flags & SMM_EXACT) != 0;
+    const int64_t m = tr ? a->cols : a->rows, kx = tr ? a->rows : a->cols;
+    CHK(blocks_check(where, host, x, kx, ldx, y, m, ldy, k, "X", "Y"));
+    if (m == 0 || k == 0) return SMM_OK;                          // (ahead of op(A): an empty product builds no transpose)
+    const smm_csr *op = nullptr;
+    CHK(spmm_op(c, a, tr, &op));
+    return blocks_run(c, where, host, x, kx, ldx, y, m, ldy, k, [&](const double *dx, int64_t lx, double *dy, int64_t ly) {
+        return spmm_impl(c, op, exact, k, dx, lx, dy, ly);
+    });
+}
+
+extern "C" int smm_spmm(smm_ctx *c, smm_csr *a, int flags, int64_t k, const double *d_x, int64_t ldx, double *d_y, int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    return spmm_entry(c, a, flags, k, d_x, ldx, d_y, ldy, ON_DEVICE, "smm_spmm");
+}
+
 extern "C" int smm_spmm_host(smm_ctx *c, smm_csr *a, int flags, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy)
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(spmm_args(c, a, flags, k, ldx, ldy, "smm_spmm_host"));
-    const bool tr = (flags & SMM_TRANSPOSE) != 0;
-    const int64_t m = tr ? a->cols : a->rows, kx = tr ? a->rows : a->cols;
-    if ((span_bytes(kx, k, ldx) > 0 && !x) || (span_bytes(m, k, ldy) > 0 && !y)) return fail(SMM_ERR_INVALID, "smm_spmm_host: X or Y is NULL");
-    if (m == 0 || k == 0) return SMM_OK;
-    const smm_csr *op = nullptr;
-    CHK(spmm_op(c, a, tr, &op));
-    PoolBuf<double> dx(c), dy(c);
-    CHK(dx.alloc((size_t)std::max<int64_t>(kx * k, 1)));
-    CHK(dy.alloc((size_t)(m * k)));
-    CHK(upload_rows(c, dx, x, kx, k, ldx));
-    CHK(spmm_impl(c, op, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
-    CHK(take_plan_error(c, "smm_spmm_host"));
-    return download_rows(c, y, dy, m, k, ldy);
+    return spmm_entry(c, a, flags, k, x, ldx, y, ldy, ON_HOST, "smm_spmm_host");
 }
 
 // ------------------------------------------------------------------------------ Kronecker operand Q = D (x) E
@@ -3719,17 +3743,22 @@ static int kron_apply_impl(smm_ctx *c, const smm_csr *d, const smm_csr *e, bool 
     return SMM_OK;
 }
 
-static int kron_apply_args(smm_ctx *c, smm_csr *d, smm_csr *e, int flags, int64_t k, int64_t ldx, int64_t ldy, const char *where)
+// smm_kron_apply[_host]: flags, factors and sizes, then Y = (D (x) E) X on the device's or the host's blocks.
+static int kron_apply_entry(smm_ctx *c, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy,
+                            bool host, const char *where)
 {
     if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call ((D (x) E)^T is D^T (x) E^T: pass "
                                                          "transposed factors)", where);
     CHK(kron_factors(c, d, e, where));
-    if (k < 0 || ldx < k || ldy < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldx, ldy (k %lld, ldx %lld, ldy %lld)", where,
-                                                 (long long)k, (long long)ldx, (long long)ldy);
+    CHK(dense_dims(where, k, ldx, ldy));
     HIPCHK(hipSetDevice(c->device));
     CHK(validate(c, d));
     CHK(validate(c, e));
-    return SMM_OK;
+    const int64_t m = d->rows * e->rows, kx = d->cols * e->cols;
+    CHK(blocks_check(where, host, x, kx, ldx, y, m, ldy, k, "X", "Y"));
+    return blocks_run(c, where, host, x, kx, ldx, y, m, ldy, k, [&](const double *dx, int64_t lx, double *dy, int64_t ly) {
+        return kron_apply_impl(c, d, e, (flags & SMM_EXACT) != 0, k, dx, lx, dy, ly);
+    });
 }
 
 extern "C" int smm_kron_apply(smm_ctx *c, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *d_x, int64_t ldx, double *d_y,
@@ -3737,10 +3766,7 @@ extern "C" int smm_kron_apply(smm_ctx *c, smm_csr *d, smm_csr *e, int flags, int
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(kron_apply_args(c, d, e, flags, k, ldx, ldy, "smm_kron_apply"));
-    CHK(spmm_buffers(d->rows * e->rows, d->cols * e->cols, k, d_x, ldx, d_y, ldy, "smm_kron_apply"));
-    CHK(kron_apply_impl(c, d, e, (flags & SMM_EXACT) != 0, k, d_x, ldx, d_y, ldy));
-    return take_plan_error(c, "smm_kron_apply");
+    return kron_apply_entry(c, d, e, flags, k, d_x, ldx, d_y, ldy, ON_DEVICE, "smm_kron_apply");
 }
 
 extern "C" int smm_kron_apply_host(smm_ctx *c, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *x, int64_t ldx, double *y,
@@ -3748,93 +3774,27 @@ extern "C" int smm_kron_apply_host(smm_ctx *c, smm_csr *d, smm_csr *e, int flags
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(kron_apply_args(c, d, e, flags, k, ldx, ldy, "smm_kron_apply_host"));
-    const int64_t m = d->rows * e->rows, kx = d->cols * e->cols;
-    if ((span_bytes(kx, k, ldx) > 0 && !x) || (span_bytes(m, k, ldy) > 0 && !y)) return fail(SMM_ERR_INVALID, "smm_kron_apply_host: X or Y is NULL");
-    if (m == 0 || k == 0) return SMM_OK;
-    PoolBuf<double> dx(c), dy(c);
-    CHK(dx.alloc((size_t)std::max<int64_t>(kx * k, 1)));
-    CHK(dy.alloc((size_t)(m * k)));
-    CHK(upload_rows(c, dx, x, kx, k, ldx));
-    CHK(kron_apply_impl(c, d, e, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
-    CHK(take_plan_error(c, "smm_kron_apply_host"));
-    return download_rows(c, y, dy, m, k, ldy);
+    return kron_apply_entry(c, d, e, flags, k, x, ldx, y, ldy, ON_HOST, "smm_kron_apply_host");
 }
 
 // The K x K operator in the middle of H Q H^T as the host code sees it: one CSR, or a pair of factors D (x) E (square, with
-// p * r == K) that is applied without being formed.
+// p * r == K) that is applied without being formed.  Which of the two is said, not read off the pointers: a call may pass NULL.
 struct QOp {
-    const smm_csr *q = nullptr, *d = nullptr, *e = nullptr;
-    bool pair() const { return d != nullptr; }
+    smm_csr *q = nullptr, *d = nullptr, *e = nullptr;
+    bool factors = false;
 };
+static QOp q_factors(smm_csr *d, smm_csr *e) { return QOp{nullptr, d, e, true}; }
 
-// Y = H (Q (H^T X)): H^T X through H's cached transpose, two pool intermediates of K x kb (three when Q is a pair of factors:
-// the U of its E-step), X taken in column blocks of kb columns so that they fit the context's apply budget (columns are
-// independent: blocking changes no bit).
-static int triple_apply_impl(smm_ctx *c, smm_csr *h, const QOp &q, bool exact, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy)
+// H and Q of a call: present, of this context, validated, Q square with as many rows as H has columns.
+static int hq_args(smm_ctx *c, smm_csr *h, const QOp &q, const char *where)
 {
-    const int64_t n = h->rows, K = h->cols;
-    if (n == 0 || k == 0) return SMM_OK;
-    const smm_csr *ht = nullptr;
-    CHK(spmm_op(c, h, true, &ht));
-    const int64_t nz = q.pair() ? 3 : 2;
-    const int64_t kb = std::max<int64_t>(1, std::min<int64_t>(k, c->apply_budget / std::max<int64_t>(nz * K * (int64_t)sizeof(double), 1)));
-    PoolBuf<double> z1(c), z2(c), u(c);
-    CHK(z1.alloc((size_t)std::max<int64_t>(K * kb, 1)));
-    CHK(z2.alloc((size_t)std::max<int64_t>(K * kb, 1)));
-    if (q.pair()) CHK(u.alloc((size_t)std::max<int64_t>(K * kb, 1)));
-    for (int64_t j0 = 0; j0 < k; j0 += kb) {
-        const int64_t b = std::min(kb, k - j0);
-        CHK(spmm_impl(c, ht, exact, b, x + j0, ldx, z1, b));      // Z1 = H^T X[:, j0 .. j0 + b)
-        if (q.pair()) CHK(kron_apply_launch(c, q.d, q.e, exact, b, z1, b, u, z2, b));
-        else          CHK(spmm_impl(c, q.q, exact, b, z1, b, z2, b));             // Z2 = Q Z1
-        CHK(spmm_impl(c, h, exact, b, z2, b, y + j0, ldy));       // Y[:, j0 .. j0 + b) = H Z2
+    if (!q.factors) {
+        CHK(check_pair(c, h, q.q));
+        if (q.q->rows != q.q->cols)
+            return fail(SMM_ERR_INVALID, "%s: Q must be square, got %lld x %lld", where, (long long)q.q->rows, (long long)q.q->cols);
+        return SMM_OK;
     }
-    return SMM_OK;
-}
-
-static int triple_apply_args(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t k, int64_t ldx, int64_t ldy, const char *where)
-{
-    if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call", where);
-    CHK(check_pair(c, h, q));
-    if (q->rows != q->cols) return fail(SMM_ERR_INVALID, "%s: Q must be square, got %lld x %lld", where, (long long)q->rows, (long long)q->cols);
-    if (k < 0 || ldx < k || ldy < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldx, ldy (k %lld, ldx %lld, ldy %lld)", where,
-                                                 (long long)k, (long long)ldx, (long long)ldy);
-    return SMM_OK;
-}
-
-extern "C" int smm_triple_apply(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t k, const double *d_x, int64_t ldx, double *d_y,
-                                int64_t ldy)
-{
-    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
-    CTX_LOCK(c);
-    CHK(triple_apply_args(c, h, q, flags, k, ldx, ldy, "smm_triple_apply"));
-    CHK(spmm_buffers(h->rows, h->rows, k, d_x, ldx, d_y, ldy, "smm_triple_apply"));
-    CHK(triple_apply_impl(c, h, QOp{q}, (flags & SMM_EXACT) != 0, k, d_x, ldx, d_y, ldy));
-    return take_plan_error(c, "smm_triple_apply");
-}
-
-extern "C" int smm_triple_apply_host(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t k, const double *x, int64_t ldx, double *y,
-                                     int64_t ldy)
-{
-    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
-    CTX_LOCK(c);
-    CHK(triple_apply_args(c, h, q, flags, k, ldx, ldy, "smm_triple_apply_host"));
-    const int64_t n = h->rows;
-    if (span_bytes(n, k, std::max(ldx, ldy)) > 0 && (!x || !y)) return fail(SMM_ERR_INVALID, "smm_triple_apply_host: X or Y is NULL");
-    if (n == 0 || k == 0) return SMM_OK;
-    PoolBuf<double> dx(c), dy(c);
-    CHK(dx.alloc((size_t)(n * k)));
-    CHK(dy.alloc((size_t)(n * k)));
-    CHK(upload_rows(c, dx, x, n, k, ldx));
-    CHK(triple_apply_impl(c, h, QOp{q}, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
-    CHK(take_plan_error(c, "smm_triple_apply_host"));
-    return download_rows(c, y, dy, n, k, ldy);
-}
-
-// H and the factors of Q = D (x) E: D and E square with p * r == H.cols.
-static int kron_q_args(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, const char *where)
-{
+    smm_csr *d = q.d, *e = q.e;
     if (!c || !h) return fail(SMM_ERR_INVALID, "%s: NULL argument", where);
     if (h->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
     CHK(kron_factors(c, d, e, where));
@@ -3851,13 +3811,59 @@ static int kron_q_args(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, const cha
     return SMM_OK;
 }
 
-static int triple_apply_kron_args(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, int flags, int64_t k, int64_t ldx, int64_t ldy, const char *where)
+// Y = H (Q (H^T X)): H^T X through H's cached transpose, two pool intermediates of K x kb (three when Q is a pair of factors:
+// the U of its E-step), X taken in column blocks of kb columns so that they fit the context's apply budget (columns are
+// independent: blocking changes no bit).
+static int triple_apply_impl(smm_ctx *c, smm_csr *h, const QOp &q, bool exact, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy)
+{
+    const int64_t n = h->rows, K = h->cols;
+    if (n == 0 || k == 0) return SMM_OK;
+    const smm_csr *ht = nullptr;
+    CHK(spmm_op(c, h, true, &ht));
+    const int64_t nz = q.factors ? 3 : 2;
+    const int64_t kb = std::max<int64_t>(1, std::min<int64_t>(k, c->apply_budget / std::max<int64_t>(nz * K * (int64_t)sizeof(double), 1)));
+    PoolBuf<double> z1(c), z2(c), u(c);
+    CHK(z1.alloc((size_t)std::max<int64_t>(K * kb, 1)));
+    CHK(z2.alloc((size_t)std::max<int64_t>(K * kb, 1)));
+    if (q.factors) CHK(u.alloc((size_t)std::max<int64_t>(K * kb, 1)));
+    for (int64_t j0 = 0; j0 < k; j0 += kb) {
+        const int64_t b = std::min(kb, k - j0);
+        CHK(spmm_impl(c, ht, exact, b, x + j0, ldx, z1, b));      // Z1 = H^T X[:, j0 .. j0 + b)
+        if (q.factors) CHK(kron_apply_launch(c, q.d, q.e, exact, b, z1, b, u, z2, b));
+        else          CHK(spmm_impl(c, q.q, exact, b, z1, b, z2, b));             // Z2 = Q Z1
+        CHK(spmm_impl(c, h, exact, b, z2, b, y + j0, ldy));       // Y[:, j0 .. j0 + b) = H Z2
+    }
+    return SMM_OK;
+}
+
+// smm_triple_apply[_kron][_host]: flags, operands and sizes, then Y = H Q H^T X on the device's or the host's blocks.
+static int triple_apply_entry(smm_ctx *c, smm_csr *h, const QOp &q, int flags, int64_t k, const double *x, int64_t ldx, double *y, int64_t ldy,
+                              bool host, const char *where)
 {
     if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call", where);
-    CHK(kron_q_args(c, h, d, e, where));
-    if (k < 0 || ldx < k || ldy < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldx, ldy (k %lld, ldx %lld, ldy %lld)", where,
-                                                 (long long)k, (long long)ldx, (long long)ldy);
-    return SMM_OK;
+    CHK(hq_args(c, h, q, where));
+    CHK(dense_dims(where, k, ldx, ldy));
+    const int64_t n = h->rows;
+    CHK(blocks_check(where, host, x, n, ldx, y, n, ldy, k, "X", "Y"));
+    return blocks_run(c, where, host, x, n, ldx, y, n, ldy, k, [&](const double *dx, int64_t lx, double *dy, int64_t ly) {
+        return triple_apply_impl(c, h, q, (flags & SMM_EXACT) != 0, k, dx, lx, dy, ly);
+    });
+}
+
+extern "C" int smm_triple_apply(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t k, const double *d_x, int64_t ldx, double *d_y,
+                                int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    return triple_apply_entry(c, h, QOp{q}, flags, k, d_x, ldx, d_y, ldy, ON_DEVICE, "smm_triple_apply");
+}
+
+extern "C" int smm_triple_apply_host(smm_ctx *c, smm_csr *h, smm_csr *q, int flags, int64_t k, const double *x, int64_t ldx, double *y,
+                                     int64_t ldy)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    return triple_apply_entry(c, h, QOp{q}, flags, k, x, ldx, y, ldy, ON_HOST, "smm_triple_apply_host");
 }
 
 extern "C" int smm_triple_apply_kron(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *d_x, int64_t ldx,
@@ -3865,10 +3871,7 @@ extern "C" int smm_triple_apply_kron(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(triple_apply_kron_args(c, h, d, e, flags, k, ldx, ldy, "smm_triple_apply_kron"));
-    CHK(spmm_buffers(h->rows, h->rows, k, d_x, ldx, d_y, ldy, "smm_triple_apply_kron"));
-    CHK(triple_apply_impl(c, h, QOp{nullptr, d, e}, (flags & SMM_EXACT) != 0, k, d_x, ldx, d_y, ldy));
-    return take_plan_error(c, "smm_triple_apply_kron");
+    return triple_apply_entry(c, h, q_factors(d, e), flags, k, d_x, ldx, d_y, ldy, ON_DEVICE, "smm_triple_apply_kron");
 }
 
 extern "C" int smm_triple_apply_kron_host(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, int flags, int64_t k, const double *x, int64_t ldx,
@@ -3876,17 +3879,7 @@ extern "C" int smm_triple_apply_kron_host(smm_ctx *c, smm_csr *h, smm_csr *d, sm
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(triple_apply_kron_args(c, h, d, e, flags, k, ldx, ldy, "smm_triple_apply_kron_host"));
-    const int64_t n = h->rows;
-    if (span_bytes(n, k, std::max(ldx, ldy)) > 0 && (!x || !y)) return fail(SMM_ERR_INVALID, "smm_triple_apply_kron_host: X or Y is NULL");
-    if (n == 0 || k == 0) return SMM_OK;
-    PoolBuf<double> dx(c), dy(c);
-    CHK(dx.alloc((size_t)(n * k)));
-    CHK(dy.alloc((size_t)(n * k)));
-    CHK(upload_rows(c, dx, x, n, k, ldx));
-    CHK(triple_apply_impl(c, h, QOp{nullptr, d, e}, (flags & SMM_EXACT) != 0, k, dx, k, dy, k));
-    CHK(take_plan_error(c, "smm_triple_apply_kron_host"));
-    return download_rows(c, y, dy, n, k, ldy);
+    return triple_apply_entry(c, h, q_factors(d, e), flags, k, x, ldx, y, ldy, ON_HOST, "smm_triple_apply_kron_host");
 }
 
 // ------------------------------------------------------------------------------ sampled dense product (X Y^T on a pattern)
@@ -3904,8 +3897,7 @@ static int sddmm_args(smm_ctx *c, smm_csr *mask, int flags, int64_t k, int64_t l
     if (flags & ~(SMM_EXACT | SMM_SCALE_BY_MASK)) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT and SMM_SCALE_BY_MASK are flags of this call", where);
     if (!mask) return fail(SMM_ERR_INVALID, "%s: mask is NULL", where);
     if (mask->ctx != c) return fail(SMM_ERR_INVALID, "%s: mask belongs to another context", where);
-    if (k < 0 || ldx < k || ldy < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldx, ldy (k %lld, ldx %lld, ldy %lld)", where,
-                                                 (long long)k, (long long)ldx, (long long)ldy);
+    CHK(dense_dims(where, k, ldx, ldy));
     HIPCHK(hipSetDevice(c->device));
     CHK(validate(c, mask));
     if ((flags & SMM_SCALE_BY_MASK) && mask->nnz > 0 && !mask->val) return fail(SMM_ERR_INVALID, "%s: SMM_SCALE_BY_MASK needs the mask's values", where);
@@ -4015,7 +4007,7 @@ static int cg_block(smm_ctx *c, const smm_csr *ht, const QOp &q, const smm_csr *
     const int64_t n = h->rows;
     ClassLists bht(c), bq(c), bh(c), br(c);
     CHK(spmm_bin(c, ht, k, bht));
-    if (!q.pair()) CHK(spmm_bin(c, q.q, k, bq));                  // (the kernels of a pair of factors bin nothing)
+    if (!q.factors) CHK(spmm_bin(c, q.q, k, bq));                  // (the kernels of a pair of factors bin nothing)
     CHK(spmm_bin(c, h, k, bh));
     if (r) CHK(spmm_bin(c, r, k, br));
     int *st = reinterpret_cast<int *>(sc + CG_NSC * k);
@@ -4052,7 +4044,7 @@ static int cg_block(smm_ctx *c, const smm_csr *ht, const QOp &q, const smm_csr *
     for (int64_t it = 1; live && it <= maxiter; ++it) {
         ran = it;
         CHK(spmm_launch(c, ht, bht, exact, k, pv, k, z1, k));         // Z1 = H^T P
-        if (q.pair()) CHK(kron_apply_launch(c, q.d, q.e, exact, k, z1, k, zu, z2, k));
+        if (q.factors) CHK(kron_apply_launch(c, q.d, q.e, exact, k, z1, k, zu, z2, k));
         else          CHK(spmm_launch(c, q.q, bq, exact, k, z1, k, z2, k));           // Z2 = Q Z1
         CHK(spmm_launch(c, h, bh, exact, k, z2, k, wv, k));           // W = H Z2
         if (r) {
@@ -4116,7 +4108,7 @@ static int innovation_impl(smm_ctx *c, smm_csr *h, const QOp &q, smm_csr *r, boo
     const smm_csr *ht = nullptr;
     CHK(spmm_op(c, h, true, &ht));
     CHK(cg_host_words(c));
-    const int64_t per_col = (5 * n + (q.pair() ? 3 : 2) * K) * (int64_t)sizeof(double);
+    const int64_t per_col = (5 * n + (q.factors ? 3 : 2) * K) * (int64_t)sizeof(double);
     int64_t kb = std::max<int64_t>(1, std::min<int64_t>(k, c->apply_budget / std::max<int64_t>(per_col, 1)));
     const int64_t nblocks = (k + kb - 1) / kb, even = (k + nblocks - 1) / nblocks;      // blocks of one size (64 = 32 + 32, not 44 + 20),
     kb = (even % 2 && even < kb) ? even + 1 : even;                                      // of an even width where the budget allows
@@ -4127,7 +4119,7 @@ static int innovation_impl(smm_ctx *c, smm_csr *h, const QOp &q, smm_csr *r, boo
     if (r) CHK(rpv.alloc((size_t)(n * kb)));
     CHK(z1.alloc((size_t)std::max<int64_t>(K * kb, 1)));
     CHK(z2.alloc((size_t)std::max<int64_t>(K * kb, 1)));
-    if (q.pair()) CHK(zu.alloc((size_t)std::max<int64_t>(K * kb, 1)));
+    if (q.factors) CHK(zu.alloc((size_t)std::max<int64_t>(K * kb, 1)));
     CHK(part.alloc((size_t)CG_T * kb));
     CHK(sc.alloc((size_t)(CG_NSC * kb + (3 * kb + 2) / 2 + 1)));
     if (alpha) {
@@ -4143,13 +4135,13 @@ static int innovation_impl(smm_ctx *c, smm_csr *h, const QOp &q, smm_csr *r, boo
     return SMM_OK;
 }
 
-static int innovation_args(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, int64_t ldb, int64_t ldx, double tol,
+// What every solve asks of its arguments; Q as one CSR or as its factors (applied through smm_kron.hpp, never formed).
+static int innovation_args(smm_ctx *c, smm_csr *h, const QOp &q, smm_csr *r, int flags, int64_t k, int64_t ldb, int64_t ldx, double tol,
                            int64_t maxiter, const int *iterations, const int *status, const double *residual_sq, const double *rhs_sq,
                            const char *where)
 {
     if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call", where);
-    CHK(check_pair(c, h, q));
-    if (q->rows != q->cols) return fail(SMM_ERR_INVALID, "%s: Q must be square, got %lld x %lld", where, (long long)q->rows, (long long)q->cols);
+    CHK(hq_args(c, h, q, where));
     if (r) {
         if (r->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
         if (r->rows != h->rows || r->cols != h->rows)
@@ -4157,12 +4149,39 @@ static int innovation_args(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, int f
                         (long long)r->rows, (long long)r->cols);
         CHK(validate(c, r));
     }
-    if (k < 0 || ldb < k || ldx < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldb, ldx (k %lld, ldb %lld, ldx %lld)", where,
-                                                 (long long)k, (long long)ldb, (long long)ldx);
+    CHK(dense_dims(where, k, ldb, ldx, "ldb", "ldx"));
     if (!(tol > 0.0) || !std::isfinite(tol)) return fail(SMM_ERR_INVALID, "%s: tol must be a finite positive number", where);
     if (maxiter < 0 || maxiter > INT32_MAX) return fail(SMM_ERR_INVALID, "%s: need 0 <= maxiter < 2^31", where);
     if (k > 0 && (!iterations || !status || !residual_sq || !rhs_sq)) return fail(SMM_ERR_INVALID, "%s: a per-column output is NULL", where);
     return SMM_OK;
+}
+
+// What the recording entries ask beyond their plain counterparts: the histories are sized by maxiter.
+static int coef_args(int64_t k, int64_t maxiter, const double *alpha, const double *beta, const char *where)
+{
+    if (maxiter < 1 || maxiter > 65536) return fail(SMM_ERR_INVALID, "%s: need 1 <= maxiter <= 65536 (the histories are maxiter x k), got %lld",
+                                                    where, (long long)maxiter);
+    if (k > 0 && (!alpha || !beta)) return fail(SMM_ERR_INVALID, "%s: alpha or beta is NULL", where);
+    return SMM_OK;
+}
+
+// The per-column outputs of a solve, and the two histories of a recording one.
+struct SolveOut { int *iterations, *status; double *residual_sq, *rhs_sq, *alpha = nullptr, *beta = nullptr; };
+
+// smm_innovation_solve[_kron][_host] and, with coef (device blocks only), smm_innovation_solve_coef[_kron]: arguments, then the
+// solve on the device's or the host's blocks.  Everything is checked, and every operand validated, ahead of the first
+// allocation, whatever k is; innovation_impl zeroes the histories ahead of its own return for an empty problem.
+static int innovation_entry(smm_ctx *c, smm_csr *h, const QOp &q, smm_csr *r, int flags, int64_t k, const double *b, int64_t ldb, double *x,
+                            int64_t ldx, double tol, int64_t maxiter, const SolveOut &o, bool host, const char *where, bool coef = false)
+{
+    CHK(innovation_args(c, h, q, r, flags, k, ldb, ldx, tol, maxiter, o.iterations, o.status, o.residual_sq, o.rhs_sq, where));
+    if (coef) CHK(coef_args(k, maxiter, o.alpha, o.beta, where));
+    const int64_t n = h->rows;
+    CHK(blocks_check(where, host, b, n, ldb, x, n, ldx, k, "B", "X", /*out_always=*/coef));
+    return blocks_run(c, where, host, b, n, ldb, x, n, ldx, k, [&](const double *db, int64_t lb, double *dx, int64_t lx) {
+        return innovation_impl(c, h, q, r, (flags & SMM_EXACT) != 0, k, db, lb, dx, lx, tol, maxiter, o.iterations, o.status, o.residual_sq,
+                               o.rhs_sq, k > 0 ? o.alpha : nullptr, k > 0 ? o.beta : nullptr);
+    });
 }
 
 extern "C" int smm_innovation_solve(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, const double *d_b, int64_t ldb,
@@ -4171,12 +4190,8 @@ extern "C" int smm_innovation_solve(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr 
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(innovation_args(c, h, q, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq, "smm_innovation_solve"));
-    const int64_t n = h->rows, bb = span_bytes(n, k, ldb), xb = span_bytes(n, k, ldx);
-    if ((bb > 0 && !d_b) || (xb > 0 && !d_x)) return fail(SMM_ERR_INVALID, "smm_innovation_solve: B or X is NULL");
-    if (ranges_overlap(d_b, bb, d_x, xb)) return fail(SMM_ERR_INVALID, "smm_innovation_solve: the device ranges of B and X overlap");
-    CHK(innovation_impl(c, h, QOp{q}, r, (flags & SMM_EXACT) != 0, k, d_b, ldb, d_x, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq));
-    return take_plan_error(c, "smm_innovation_solve");
+    return innovation_entry(c, h, QOp{q}, r, flags, k, d_b, ldb, d_x, ldx, tol, maxiter, {iterations, status, residual_sq, rhs_sq}, ON_DEVICE,
+                            "smm_innovation_solve");
 }
 
 extern "C" int smm_innovation_solve_host(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, const double *b, int64_t ldb,
@@ -4185,39 +4200,8 @@ extern "C" int smm_innovation_solve_host(smm_ctx *c, smm_csr *h, smm_csr *q, smm
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(innovation_args(c, h, q, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq, "smm_innovation_solve_host"));
-    const int64_t n = h->rows;
-    if (span_bytes(n, k, std::max(ldb, ldx)) > 0 && (!b || !x)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_host: B or X is NULL");
-    if (n == 0 || k == 0) return SMM_OK;
-    PoolBuf<double> db(c), dx(c);
-    CHK(db.alloc((size_t)(n * k)));
-    CHK(dx.alloc((size_t)(n * k)));
-    CHK(upload_rows(c, db, b, n, k, ldb));
-    CHK(innovation_impl(c, h, QOp{q}, r, (flags & SMM_EXACT) != 0, k, db, k, dx, k, tol, maxiter, iterations, status, residual_sq, rhs_sq));
-    CHK(take_plan_error(c, "smm_innovation_solve_host"));
-    return download_rows(c, x, dx, n, k, ldx);
-}
-
-// The same solve with Q = D (x) E applied through its factors (smm_kron.hpp), never formed.
-static int innovation_kron_args(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k, int64_t ldb, int64_t ldx,
-                                double tol, int64_t maxiter, const int *iterations, const int *status, const double *residual_sq,
-                                const double *rhs_sq, const char *where)
-{
-    if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call", where);
-    CHK(kron_q_args(c, h, d, e, where));
-    if (r) {
-        if (r->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
-        if (r->rows != h->rows || r->cols != h->rows)
-            return fail(SMM_ERR_INVALID, "%s: R must be %lld x %lld, got %lld x %lld", where, (long long)h->rows, (long long)h->rows,
-                        (long long)r->rows, (long long)r->cols);
-        CHK(validate(c, r));
-    }
-    if (k < 0 || ldb < k || ldx < k) return fail(SMM_ERR_INVALID, "%s: need 0 <= k <= ldb, ldx (k %lld, ldb %lld, ldx %lld)", where,
-                                                 (long long)k, (long long)ldb, (long long)ldx);
-    if (!(tol > 0.0) || !std::isfinite(tol)) return fail(SMM_ERR_INVALID, "%s: tol must be a finite positive number", where);
-    if (maxiter < 0 || maxiter > INT32_MAX) return fail(SMM_ERR_INVALID, "%s: need 0 <= maxiter < 2^31", where);
-    if (k > 0 && (!iterations || !status || !residual_sq || !rhs_sq)) return fail(SMM_ERR_INVALID, "%s: a per-column output is NULL", where);
-    return SMM_OK;
+    return innovation_entry(c, h, QOp{q}, r, flags, k, b, ldb, x, ldx, tol, maxiter, {iterations, status, residual_sq, rhs_sq}, ON_HOST,
+                            "smm_innovation_solve_host");
 }
 
 extern "C" int smm_innovation_solve_kron(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k, const double *d_b,
@@ -4226,14 +4210,8 @@ extern "C" int smm_innovation_solve_kron(smm_ctx *c, smm_csr *h, smm_csr *d, smm
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(innovation_kron_args(c, h, d, e, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq,
-                             "smm_innovation_solve_kron"));
-    const int64_t n = h->rows, bb = span_bytes(n, k, ldb), xb = span_bytes(n, k, ldx);
-    if ((bb > 0 && !d_b) || (xb > 0 && !d_x)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_kron: B or X is NULL");
-    if (ranges_overlap(d_b, bb, d_x, xb)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_kron: the device ranges of B and X overlap");
-    CHK(innovation_impl(c, h, QOp{nullptr, d, e}, r, (flags & SMM_EXACT) != 0, k, d_b, ldb, d_x, ldx, tol, maxiter, iterations, status,
-                        residual_sq, rhs_sq));
-    return take_plan_error(c, "smm_innovation_solve_kron");
+    return innovation_entry(c, h, q_factors(d, e), r, flags, k, d_b, ldb, d_x, ldx, tol, maxiter, {iterations, status, residual_sq, rhs_sq},
+                            ON_DEVICE, "smm_innovation_solve_kron");
 }
 
 extern "C" int smm_innovation_solve_kron_host(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k, const double *b,
@@ -4242,19 +4220,8 @@ extern "C" int smm_innovation_solve_kron_host(smm_ctx *c, smm_csr *h, smm_csr *d
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(innovation_kron_args(c, h, d, e, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq,
-                             "smm_innovation_solve_kron_host"));
-    const int64_t n = h->rows;
-    if (span_bytes(n, k, std::max(ldb, ldx)) > 0 && (!b || !x)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_kron_host: B or X is NULL");
-    if (n == 0 || k == 0) return SMM_OK;
-    PoolBuf<double> db(c), dx(c);
-    CHK(db.alloc((size_t)(n * k)));
-    CHK(dx.alloc((size_t)(n * k)));
-    CHK(upload_rows(c, db, b, n, k, ldb));
-    CHK(innovation_impl(c, h, QOp{nullptr, d, e}, r, (flags & SMM_EXACT) != 0, k, db, k, dx, k, tol, maxiter, iterations, status, residual_sq,
-                        rhs_sq));
-    CHK(take_plan_error(c, "smm_innovation_solve_kron_host"));
-    return download_rows(c, x, dx, n, k, ldx);
+    return innovation_entry(c, h, q_factors(d, e), r, flags, k, b, ldb, x, ldx, tol, maxiter, {iterations, status, residual_sq, rhs_sq}, ON_HOST,
+                            "smm_innovation_solve_kron_host");
 }
 
 // ------------------------------------------------------------------------------ probes and recorded CG coefficients (SLQ)
@@ -4278,29 +4245,14 @@ extern "C" int smm_probe_fill(smm_ctx *c, int64_t n, int64_t k, uint64_t seed, d
     return SMM_OK;
 }
 
-// What the recording entries ask beyond their plain counterparts: the histories are sized by maxiter.
-static int coef_args(int64_t k, int64_t maxiter, const double *alpha, const double *beta, const char *where)
-{
-    if (maxiter < 1 || maxiter > 65536) return fail(SMM_ERR_INVALID, "%s: need 1 <= maxiter <= 65536 (the histories are maxiter x k), got %lld",
-                                                    where, (long long)maxiter);
-    if (k > 0 && (!alpha || !beta)) return fail(SMM_ERR_INVALID, "%s: alpha or beta is NULL", where);
-    return SMM_OK;
-}
-
 extern "C" int smm_innovation_solve_coef(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *r, int flags, int64_t k, const double *d_b, int64_t ldb,
                                          double *d_x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
                                          double *residual_sq, double *rhs_sq, double *alpha, double *beta)
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(innovation_args(c, h, q, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq, "smm_innovation_solve_coef"));
-    CHK(coef_args(k, maxiter, alpha, beta, "smm_innovation_solve_coef"));
-    const int64_t n = h->rows, bb = span_bytes(n, k, ldb), xb = span_bytes(n, k, ldx);
-    if ((bb > 0 && !d_b) || !d_x) return fail(SMM_ERR_INVALID, "smm_innovation_solve_coef: B or X is NULL");
-    if (ranges_overlap(d_b, bb, d_x, xb)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_coef: the device ranges of B and X overlap");
-    CHK(innovation_impl(c, h, QOp{q}, r, (flags & SMM_EXACT) != 0, k, d_b, ldb, d_x, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq,
-                        k > 0 ? alpha : nullptr, k > 0 ? beta : nullptr));
-    return take_plan_error(c, "smm_innovation_solve_coef");
+    return innovation_entry(c, h, QOp{q}, r, flags, k, d_b, ldb, d_x, ldx, tol, maxiter, {iterations, status, residual_sq, rhs_sq, alpha, beta},
+                            ON_DEVICE, "smm_innovation_solve_coef", /*coef=*/true);
 }
 
 extern "C" int smm_innovation_solve_coef_kron(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *r, int flags, int64_t k,
@@ -4309,15 +4261,8 @@ extern "C" int smm_innovation_solve_coef_kron(smm_ctx *c, smm_csr *h, smm_csr *d
 {
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
-    CHK(innovation_kron_args(c, h, d, e, r, flags, k, ldb, ldx, tol, maxiter, iterations, status, residual_sq, rhs_sq,
-                             "smm_innovation_solve_coef_kron"));
-    CHK(coef_args(k, maxiter, alpha, beta, "smm_innovation_solve_coef_kron"));
-    const int64_t n = h->rows, bb = span_bytes(n, k, ldb), xb = span_bytes(n, k, ldx);
-    if ((bb > 0 && !d_b) || !d_x) return fail(SMM_ERR_INVALID, "smm_innovation_solve_coef_kron: B or X is NULL");
-    if (ranges_overlap(d_b, bb, d_x, xb)) return fail(SMM_ERR_INVALID, "smm_innovation_solve_coef_kron: the device ranges of B and X overlap");
-    CHK(innovation_impl(c, h, QOp{nullptr, d, e}, r, (flags & SMM_EXACT) != 0, k, d_b, ldb, d_x, ldx, tol, maxiter, iterations, status,
-                        residual_sq, rhs_sq, k > 0 ? alpha : nullptr, k > 0 ? beta : nullptr));
-    return take_plan_error(c, "smm_innovation_solve_coef_kron");
+    return innovation_entry(c, h, q_factors(d, e), r, flags, k, d_b, ldb, d_x, ldx, tol, maxiter,
+                            {iterations, status, residual_sq, rhs_sq, alpha, beta}, ON_DEVICE, "smm_innovation_solve_coef_kron", /*coef=*/true);
 }
 
 // ------------------------------------------------------------------------------ memory helpers

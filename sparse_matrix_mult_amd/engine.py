@@ -398,12 +398,15 @@ class Context:
         long class) and the bytes of triple_apply's two intermediates per column block (0 = default, 1 GiB)."""
         check(self.lib, self.lib.smm_ctx_tune_spmm(self.handle, int(mode), int(apply_budget_bytes)))
 
-    def _sync_torch(self, t):
-        """Torch's current stream finished with t before the library reads it (csr_from_torch's rule)."""
-        import torch
-        cur = torch.cuda.current_stream(t.device)
-        if self.stream is None or int(cur.cuda_stream) != self.stream:
-            cur.synchronize()
+    def _sync_all(self, *tensors):
+        """Torch's current stream finished with every torch tensor among these before the library reads it (csr_from_torch's
+        rule); an int is a device address, whose ordering is the caller's."""
+        for t in tensors:
+            if hasattr(t, "data_ptr"):
+                import torch
+                cur = torch.cuda.current_stream(t.device)
+                if self.stream is None or int(cur.cuda_stream) != self.stream:
+                    cur.synchronize()
 
     @staticmethod
     def _host_x(x):
@@ -413,51 +416,46 @@ class Context:
         x = np.ascontiguousarray(x)
         return x, (1 if x.ndim == 1 else x.shape[1])
 
+    def _host_blocks(self, entry, ops, x, in_rows, out_rows, flags, name, expect, tail=(), fill=np.empty):
+        """Host block in, host block of the same kind out, through a _host entry of the library: x (1-D or 2-D, cast to
+        C-contiguous float64) must have in_rows rows; a numpy array of out_rows rows and x's number of dimensions."""
+        x, k = self._host_x(x)
+        if x.shape[0] != in_rows:
+            raise ValueError(f"{name} has {x.shape[0]} rows, {expect}")
+        y = fill((out_rows,) + x.shape[1:], dtype=np.float64)
+        check(self.lib, entry(self.handle, *_handles(ops), flags, k, _ptr(x), k, _ptr(y), k, *tail))
+        return y
+
+    def _device_blocks(self, entry, ops, flags, k, d_in, ld_in, d_out, ld_out, tail=()):
+        """Device block in, device block out, through an entry of the library.  Ints (device addresses) or torch tensors:
+        torch's current stream is synchronised before the library reads, and the context before this returns."""
+        self._sync_all(d_in, d_out)
+        check(self.lib, entry(self.handle, *_handles(ops), flags, int(k), ctypes.c_void_p(_dptr(d_in)), int(ld_in),
+                              ctypes.c_void_p(_dptr(d_out)), int(ld_out), *tail))
+        self.synchronize()
+
     def spmm_host(self, a, x, transpose=False, exact=False):
         """Y = op(A) X with X a numpy array (1-D or 2-D, cast to C-contiguous float64): a numpy array of the same number
         of dimensions (smm_spmm_host).  op(A) = A^T when transpose."""
-        x, k = self._host_x(x)
         m, kx = (a.cols, a.rows) if transpose else (a.rows, a.cols)
-        if x.shape[0] != kx:
-            raise ValueError(f"X has {x.shape[0]} rows, op(A) has {kx} columns")
-        y = np.empty((m,) if x.ndim == 1 else (m, k), dtype=np.float64)
         flags = _flags(exact=exact) | (SMM_TRANSPOSE if transpose else 0)
-        check(self.lib, self.lib.smm_spmm_host(self.handle, a.handle, flags, k, _ptr(x), k, _ptr(y), k))
-        return y
+        return self._host_blocks(self.lib.smm_spmm_host, (a,), x, kx, m, flags, "X", f"op(A) has {kx} columns")
 
     def spmm_into(self, a, d_x, ldx, k, d_y, ldy, transpose=False, exact=False):
         """Y = op(A) X on device buffers: X (op(A).cols x k, leading dimension ldx) at d_x, Y (op(A).rows x k, leading
         dimension ldy) at d_y (smm_spmm).  Ints (device addresses) or torch tensors: torch's current stream is
         synchronised before the library reads, and the context before this returns."""
-        if hasattr(d_x, "data_ptr"):
-            self._sync_torch(d_x)
-        if hasattr(d_y, "data_ptr"):
-            self._sync_torch(d_y)
         flags = _flags(exact=exact) | (SMM_TRANSPOSE if transpose else 0)
-        check(self.lib, self.lib.smm_spmm(self.handle, a.handle, flags, int(k), ctypes.c_void_p(_dptr(d_x)), int(ldx),
-                                          ctypes.c_void_p(_dptr(d_y)), int(ldy)))
-        self.synchronize()
+        self._device_blocks(self.lib.smm_spmm, (a,), flags, k, d_x, ldx, d_y, ldy)
 
     def triple_apply_host(self, h, q, x, exact=False):
         """Y = H (Q (H^T X)) with numpy X (n x k or n): the same shape back (smm_triple_apply_host)."""
-        x, k = self._host_x(x)
-        if x.shape[0] != h.rows:
-            raise ValueError(f"X has {x.shape[0]} rows, H has {h.rows}")
-        y = np.empty(x.shape, dtype=np.float64)
-        check(self.lib, self.lib.smm_triple_apply_host(self.handle, h.handle, q.handle, _flags(exact=exact), k, _ptr(x), k,
-                                                       _ptr(y), k))
-        return y
+        return self._host_blocks(self.lib.smm_triple_apply_host, (h, q), x, h.rows, h.rows, _flags(exact=exact), "X", f"H has {h.rows}")
 
     def triple_apply_into(self, h, q, d_x, ldx, k, d_y, ldy, exact=False):
         """Y = H (Q (H^T X)) on device buffers (n x k, leading dimensions ldx / ldy; smm_triple_apply); stream rules as
         spmm_into."""
-        if hasattr(d_x, "data_ptr"):
-            self._sync_torch(d_x)
-        if hasattr(d_y, "data_ptr"):
-            self._sync_torch(d_y)
-        check(self.lib, self.lib.smm_triple_apply(self.handle, h.handle, q.handle, _flags(exact=exact), int(k),
-                                                  ctypes.c_void_p(_dptr(d_x)), int(ldx), ctypes.c_void_p(_dptr(d_y)), int(ldy)))
-        self.synchronize()
+        self._device_blocks(self.lib.smm_triple_apply, (h, q), _flags(exact=exact), k, d_x, ldx, d_y, ldy)
 
     # ------------------------------------------------------------------ (X Y^T) on a pattern
     def tune_sddmm(self, mode=0):
@@ -492,9 +490,7 @@ class Context:
         """sddmm_host on device buffers: X (mask.rows x k, leading dimension ldx) at d_x, Y (mask.cols x k, leading
         dimension ldy) at d_y, nnz(mask) float64 written at d_c (smm_sddmm).  Ints (device addresses) or torch tensors;
         stream rules as spmm_into."""
-        for t in (d_x, d_y, d_c):
-            if hasattr(t, "data_ptr"):
-                self._sync_torch(t)
+        self._sync_all(d_x, d_y, d_c)
         flags = _flags(exact=exact) | (SMM_SCALE_BY_MASK if scale else 0)
         check(self.lib, self.lib.smm_sddmm(self.handle, mask.handle, flags, int(k), ctypes.c_void_p(_dptr(d_x)), int(ldx),
                                            ctypes.c_void_p(_dptr(d_y)), int(ldy), ctypes.c_void_p(_dptr(d_c))))
@@ -533,9 +529,7 @@ class Context:
         d_b -- the same buffer for the square case (smm_taper_build).  Ints (device addresses) or torch tensors; stream
         rules as spmm_into.  Returns the DeviceCSR, which the library owns: nothing of the caller's is kept."""
         kind = _taper_kind(kind)
-        for t in (d_a, d_b):
-            if hasattr(t, "data_ptr"):
-                self._sync_torch(t)
+        self._sync_all(d_a, d_b)
         h = ctypes.c_void_p()
         check(self.lib, self.lib.smm_taper_build(self.handle, int(dim), kind, float(cutoff), int(na), ctypes.c_void_p(_dptr(d_a)), int(lda),
                                                  int(nb), ctypes.c_void_p(_dptr(d_b)), int(ldb), ctypes.byref(h)))
@@ -552,134 +546,80 @@ class Context:
     def kron_apply_host(self, d, e, x, exact=False):
         """Y = (D (x) E) X without forming it, X a numpy array (1-D or 2-D, cast to C-contiguous float64): a numpy array of
         the same number of dimensions (smm_kron_apply_host)."""
-        x, k = self._host_x(x)
         m, kx = d.rows * e.rows, d.cols * e.cols
-        if x.shape[0] != kx:
-            raise ValueError(f"X has {x.shape[0]} rows, D (x) E has {kx} columns")
-        y = np.empty((m,) if x.ndim == 1 else (m, k), dtype=np.float64)
-        check(self.lib, self.lib.smm_kron_apply_host(self.handle, d.handle, e.handle, _flags(exact=exact), k, _ptr(x), k, _ptr(y), k))
-        return y
+        return self._host_blocks(self.lib.smm_kron_apply_host, (d, e), x, kx, m, _flags(exact=exact), "X", f"D (x) E has {kx} columns")
 
     def kron_apply_into(self, d, e, d_x, ldx, k, d_y, ldy, exact=False):
         """Y = (D (x) E) X on device buffers (smm_kron_apply): X ((d.cols * e.cols) x k, leading dimension ldx) at d_x, Y
         ((d.rows * e.rows) x k, leading dimension ldy) at d_y; stream rules as spmm_into."""
-        for t in (d_x, d_y):
-            if hasattr(t, "data_ptr"):
-                self._sync_torch(t)
-        check(self.lib, self.lib.smm_kron_apply(self.handle, d.handle, e.handle, _flags(exact=exact), int(k), ctypes.c_void_p(_dptr(d_x)),
-                                                int(ldx), ctypes.c_void_p(_dptr(d_y)), int(ldy)))
-        self.synchronize()
+        self._device_blocks(self.lib.smm_kron_apply, (d, e), _flags(exact=exact), k, d_x, ldx, d_y, ldy)
 
     def triple_apply_kron_host(self, h, d, e, x, exact=False):
         """Y = H ((D (x) E) (H^T X)) with numpy X (n x k or n): the same shape back (smm_triple_apply_kron_host)."""
-        x, k = self._host_x(x)
-        if x.shape[0] != h.rows:
-            raise ValueError(f"X has {x.shape[0]} rows, H has {h.rows}")
-        y = np.empty(x.shape, dtype=np.float64)
-        check(self.lib, self.lib.smm_triple_apply_kron_host(self.handle, h.handle, d.handle, e.handle, _flags(exact=exact), k, _ptr(x), k,
-                                                            _ptr(y), k))
-        return y
+        return self._host_blocks(self.lib.smm_triple_apply_kron_host, (h, d, e), x, h.rows, h.rows, _flags(exact=exact), "X",
+                                 f"H has {h.rows}")
 
     def triple_apply_kron_into(self, h, d, e, d_x, ldx, k, d_y, ldy, exact=False):
         """triple_apply_kron_host on device buffers (smm_triple_apply_kron); stream rules as spmm_into."""
-        for t in (d_x, d_y):
-            if hasattr(t, "data_ptr"):
-                self._sync_torch(t)
-        check(self.lib, self.lib.smm_triple_apply_kron(self.handle, h.handle, d.handle, e.handle, _flags(exact=exact), int(k),
-                                                       ctypes.c_void_p(_dptr(d_x)), int(ldx), ctypes.c_void_p(_dptr(d_y)), int(ldy)))
-        self.synchronize()
-
-    def _solve_kron(self, entry, h, d, e, r, k, b, ldb, x, ldx, tol, maxiter, exact):
-        info = SolveInfo(k)
-        check(self.lib, entry(self.handle, h.handle, d.handle, e.handle, r.handle if r is not None else None, _flags(exact=exact), int(k),
-                              b, int(ldb), x, int(ldx), float(tol), int(maxiter), _ptr(info.iterations), _ptr(info.status),
-                              _ptr(info.residual_sq), _ptr(info.rhs_sq)))
-        return info
-
-    def innovation_solve_kron_host(self, h, d, e, r, rhs, tol=1e-8, maxiter=None, exact=False):
-        """innovation_solve_host with Q = D (x) E applied through its factors (smm_innovation_solve_kron_host): (Z, info)."""
-        rhs, k = self._host_x(rhs)
-        if rhs.shape[0] != h.rows:
-            raise ValueError(f"D has {rhs.shape[0]} rows, H has {h.rows}")
-        z = np.zeros(rhs.shape, dtype=np.float64)
-        info = self._solve_kron(self.lib.smm_innovation_solve_kron_host, h, d, e, r, k, _ptr(rhs), k, _ptr(z), k, tol,
-                                h.rows if maxiter is None else maxiter, exact)
-        return z, info
-
-    def innovation_solve_kron_into(self, h, d, e, r, d_b, ldb, k, d_x, ldx, tol=1e-8, maxiter=None, exact=False):
-        """The same on device buffers (smm_innovation_solve_kron); stream rules as spmm_into.  Returns info."""
-        for t in (d_b, d_x):
-            if hasattr(t, "data_ptr"):
-                self._sync_torch(t)
-        info = self._solve_kron(self.lib.smm_innovation_solve_kron, h, d, e, r, k, ctypes.c_void_p(_dptr(d_b)), ldb,
-                                ctypes.c_void_p(_dptr(d_x)), ldx, tol, h.rows if maxiter is None else maxiter, exact)
-        self.synchronize()
-        return info
+        self._device_blocks(self.lib.smm_triple_apply_kron, (h, d, e), _flags(exact=exact), k, d_x, ldx, d_y, ldy)
 
     # ------------------------------------------------------------------ CG on (H Q H^T + R) Z = D
-    def _solve(self, entry, h, q, r, k, b, ldb, x, ldx, tol, maxiter, exact):
-        info = SolveInfo(k)
-        check(self.lib, entry(self.handle, h.handle, q.handle, r.handle if r is not None else None, _flags(exact=exact), int(k),
-                              b, int(ldb), x, int(ldx), float(tol), int(maxiter), _ptr(info.iterations), _ptr(info.status),
-                              _ptr(info.residual_sq), _ptr(info.rhs_sq)))
+    def _solve_host(self, entry, ops, r, d, tol, maxiter, exact):
+        """A solve entry on the numpy right-hand sides d (n x k or n), ops = (H, Q) or (H, D, E): (Z, info)."""
+        n = ops[0].rows
+        info = SolveInfo(self._host_x(d)[1])
+        z = self._host_blocks(entry, (*ops, r), d, n, n, _flags(exact=exact), "D", f"H has {n}",
+                              info.tail(tol, n if maxiter is None else maxiter), np.zeros)
+        return z, info
+
+    def _solve(self, entry, ops, r, d_b, ldb, k, d_x, ldx, tol, maxiter, exact, history=None):
+        """A solve entry on device buffers, ops = (H, Q) or (H, D, E); stream rules as spmm_into.  Returns info, with the
+        coefficient histories (history rows each) where the entry records them."""
+        info = SolveInfo(k, history)
+        self._device_blocks(entry, (*ops, r), _flags(exact=exact), k, d_b, ldb, d_x, ldx, info.tail(tol, maxiter))
         return info
 
     def innovation_solve_host(self, h, q, r, d, tol=1e-8, maxiter=None, exact=False):
         """(Z, info) with (H Q H^T + R) Z = D by conjugate gradients, one CG per column of the numpy D (n x k or n), Z of
         the same shape (smm_innovation_solve_host).  r: a DeviceCSR (n x n) or None; maxiter None means n."""
-        d, k = self._host_x(d)
-        if d.shape[0] != h.rows:
-            raise ValueError(f"D has {d.shape[0]} rows, H has {h.rows}")
-        z = np.zeros(d.shape, dtype=np.float64)
-        info = self._solve(self.lib.smm_innovation_solve_host, h, q, r, k, _ptr(d), k, _ptr(z), k, tol,
-                           h.rows if maxiter is None else maxiter, exact)
-        return z, info
+        return self._solve_host(self.lib.smm_innovation_solve_host, (h, q), r, d, tol, maxiter, exact)
 
     def innovation_solve_into(self, h, q, r, d_b, ldb, k, d_x, ldx, tol=1e-8, maxiter=None, exact=False):
         """The same on device buffers: D (n x k, leading dimension ldb) at d_b, Z (leading dimension ldx) at d_x
         (smm_innovation_solve); stream rules as spmm_into.  Returns info."""
-        if hasattr(d_b, "data_ptr"):
-            self._sync_torch(d_b)
-        if hasattr(d_x, "data_ptr"):
-            self._sync_torch(d_x)
-        info = self._solve(self.lib.smm_innovation_solve, h, q, r, k, ctypes.c_void_p(_dptr(d_b)), ldb, ctypes.c_void_p(_dptr(d_x)),
-                           ldx, tol, h.rows if maxiter is None else maxiter, exact)
-        self.synchronize()
-        return info
+        return self._solve(self.lib.smm_innovation_solve, (h, q), r, d_b, ldb, k, d_x, ldx, tol, h.rows if maxiter is None else maxiter, exact)
+
+    def innovation_solve_kron_host(self, h, d, e, r, rhs, tol=1e-8, maxiter=None, exact=False):
+        """innovation_solve_host with Q = D (x) E applied through its factors (smm_innovation_solve_kron_host): (Z, info)."""
+        return self._solve_host(self.lib.smm_innovation_solve_kron_host, (h, d, e), r, rhs, tol, maxiter, exact)
+
+    def innovation_solve_kron_into(self, h, d, e, r, d_b, ldb, k, d_x, ldx, tol=1e-8, maxiter=None, exact=False):
+        """The same on device buffers (smm_innovation_solve_kron); stream rules as spmm_into.  Returns info."""
+        return self._solve(self.lib.smm_innovation_solve_kron, (h, d, e), r, d_b, ldb, k, d_x, ldx, tol,
+                           h.rows if maxiter is None else maxiter, exact)
 
     # ------------------------------------------------------------------ log det(H Q H^T + R): probes, recorded coefficients
     def probe_fill_into(self, d_x, ldx, n, k, seed=0):
         """X[i, c] = +-1.0 by the hash of include/smm_hip.h (seed taken modulo 2^64) into the n x k block at d_x, leading
         dimension ldx (smm_probe_fill); padding is not written.  An int (device address) or a torch tensor; stream rules
         as spmm_into."""
-        if hasattr(d_x, "data_ptr"):
-            self._sync_torch(d_x)
+        self._sync_all(d_x)
         check(self.lib, self.lib.smm_probe_fill(self.handle, int(n), int(k), int(seed) % (1 << 64), ctypes.c_void_p(_dptr(d_x)), int(ldx)))
         self.synchronize()
 
-    def _solve_coef(self, entry, ops, r, k, d_b, ldb, d_x, ldx, tol, maxiter, exact):
-        for t in (d_b, d_x):
-            if hasattr(t, "data_ptr"):
-                self._sync_torch(t)
-        maxiter = int(maxiter)
+    def _solve_coef(self, entry, ops, r, d_b, ldb, k, d_x, ldx, tol, maxiter, exact):
         # (a maxiter the library refuses gets no history to size: it is refused there, before anything is written)
-        info = SolveInfo(k, maxiter if 1 <= maxiter <= 65536 else 0)
-        check(self.lib, entry(self.handle, *[o.handle for o in ops], r.handle if r is not None else None, _flags(exact=exact), int(k),
-                              ctypes.c_void_p(_dptr(d_b)), int(ldb), ctypes.c_void_p(_dptr(d_x)), int(ldx), float(tol), maxiter,
-                              _ptr(info.iterations), _ptr(info.status), _ptr(info.residual_sq), _ptr(info.rhs_sq), _ptr(info.alpha),
-                              _ptr(info.beta)))
-        self.synchronize()
-        return info
+        return self._solve(entry, ops, r, d_b, ldb, k, d_x, ldx, tol, maxiter, exact, history=int(maxiter) if 1 <= int(maxiter) <= 65536 else 0)
 
     def innovation_solve_coef_into(self, h, q, r, d_b, ldb, k, d_x, ldx, tol=1e-8, maxiter=1000, exact=False):
         """innovation_solve_into that keeps every column's CG coefficients (smm_innovation_solve_coef): info.alpha and
         info.beta are maxiter x k, row it - 1 holding iteration it, +0.0 where a column computed none.  maxiter must be
         given as 1 .. 65536: it sizes the histories."""
-        return self._solve_coef(self.lib.smm_innovation_solve_coef, (h, q), r, k, d_b, ldb, d_x, ldx, tol, maxiter, exact)
+        return self._solve_coef(self.lib.smm_innovation_solve_coef, (h, q), r, d_b, ldb, k, d_x, ldx, tol, maxiter, exact)
 
     def innovation_solve_coef_kron_into(self, h, d, e, r, d_b, ldb, k, d_x, ldx, tol=1e-8, maxiter=1000, exact=False):
         """The same with Q = D (x) E applied through its factors (smm_innovation_solve_coef_kron)."""
-        return self._solve_coef(self.lib.smm_innovation_solve_coef_kron, (h, d, e), r, k, d_b, ldb, d_x, ldx, tol, maxiter, exact)
+        return self._solve_coef(self.lib.smm_innovation_solve_coef_kron, (h, d, e), r, d_b, ldb, k, d_x, ldx, tol, maxiter, exact)
 
 
 class SolveInfo:
@@ -697,6 +637,11 @@ class SolveInfo:
         if history is not None:
             self.alpha, self.beta = np.zeros((history, k), dtype=np.float64), np.zeros((history, k), dtype=np.float64)
 
+    def tail(self, tol, maxiter):
+        """What a solve entry takes behind its blocks: tol, maxiter, the per-column outputs and, where kept, the histories."""
+        out = (self.iterations, self.status, self.residual_sq, self.rhs_sq) + (() if self.alpha is None else (self.alpha, self.beta))
+        return [float(tol), int(maxiter)] + [_ptr(a) for a in out]
+
     @property
     def converged(self):
         return bool(np.all(self.status == 0))
@@ -704,6 +649,11 @@ class SolveInfo:
     def __repr__(self):
         return (f"SolveInfo(iterations={self.iterations.tolist()}, status={self.status.tolist()}, "
                 f"residual_sq={self.residual_sq.tolist()}, rhs_sq={self.rhs_sq.tolist()})")
+
+
+def _handles(ops):
+    """The library's handles of these operands (None: an operand the call leaves out)."""
+    return [o.handle if o is not None else None for o in ops]
 
 
 def _dptr(p):
