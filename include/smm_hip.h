@@ -430,6 +430,48 @@ int  smm_taper_build(smm_ctx *ctx, int dim, int kind, double cutoff, int64_t na,
 int  smm_taper_build_host(smm_ctx *ctx, int dim, int kind, double cutoff, int64_t na, const double *a, int64_t lda,
                           int64_t nb, const double *b, int64_t ldb, smm_csr **out);
 
+/* ------------------------------------------------------------------ observation operator from point coordinates
+ * H (n x K): the matrix that interpolates a field on a rectilinear grid to n points, as a new operand owned by the caller
+ * (smm_csr_destroy), as smm_taper_build returns one -- the H of smm_triple_apply, smm_innovation_solve and their _kron forms,
+ * built where it is used instead of on the host.
+ *   Grid        dim is 1 to 4.  Axis t has m_t >= 2 nodes x_t[0] < x_t[1] < ... (finite, strictly ascending, float64; the
+ *               spacing may vary).  K = prod m_t < 2^31 - 1.  Node (j_0, ..., j_{dim-1}) is column (j_0 m_1 + j_1) m_2 + ...:
+ *               row-major, axis 0 slowest, stride_t = prod of m_u over u > t.  With time as axis 0 the columns are those of
+ *               the Kronecker operand below (t r + j).
+ *   Cell        for point i and axis t with coordinate x: c = (number of nodes <= x) - 1, clamped to [0, m_t - 2] (only
+ *               comparisons: any search gives the same c), and f = (x - x_t[c]) / (x_t[c+1] - x_t[c]), one IEEE
+ *               subtraction each and one IEEE division.  For x inside [x_t[0], x_t[m_t-1]] this gives 0 <= f <= 1, and
+ *               f = 1.0 exactly on the last node.
+ *   SMM_INTERP_LINEAR   row i holds 2^dim entries; entry e (bit b_t of e, axis 0 the most significant bit) is at column
+ *               sum (c_t + b_t) stride_t with value ((w_0 * w_1) * w_2) * w_3, taken left to right, every product rounded,
+ *               w_t = f_t if b_t is set and 1.0 - f_t otherwise.  Columns ascend strictly with e (stride_t >= 2 stride_{t+1}),
+ *               so smm_csr_is_canonical holds; explicit zeros stay entries, as in smm_kron_build.  The row pointer is the
+ *               closed form ptr[i] = i 2^dim: no count pass, no scan.
+ *   SMM_INTERP_NEAREST  one entry per row, at node c_t + (f_t > 0.5 ? 1 : 0) in every axis (a tie goes to the lower node),
+ *               with value 1.0; ptr[i] = i.
+ *   Outside     a point is outside if x < x_t[0] or x > x_t[m_t-1] in any axis.
+ *               SMM_INTERP_REJECT: the call returns SMM_ERR_INVALID with the number of outside points in the message; no
+ *               operand is returned and no pool block stays handed out (an integer count, taken before the operand is
+ *               allocated).  SMM_INTERP_CLAMP: f_t is replaced by 0.0 below the first node and 1.0 above the last --
+ *               constant extrapolation.  SMM_INTERP_ZERO: the columns of CLAMP, and every value of the row is +0.0: the
+ *               observation sees nothing and the closed-form row pointer survives.
+ *               A coordinate that is NaN or +-inf is SMM_ERR_INVALID under every policy, with the count in the message.
+ *   One mode: there is no SMM_EXACT flag and no other order.  Pattern and values are bit-identical to that recipe carried
+ *   out in IEEE double.  No float atomics: two calls give the same bits.
+ * axis_len (dim entries) and axes (the nodes of axis 0, 1, ... one after the other: sum m_t doubles) are HOST arrays in both
+ * forms and go up through a pool temporary.  The points are n x dim row-major float64 with leading dimension ldp >= dim,
+ * 64-bit offsets, used where they are.
+ * SMM_ERR_INVALID before any launch: dim outside 1..4, unknown method or policy, an axis shorter than 2, not strictly
+ * ascending or not finite, K >= 2^31 - 1, n < 0 or n >= 2^31 - 1, ldp < dim, a NULL buffer with n > 0.  More than 2^31 - 2
+ * entries (n 2^dim, or n): SMM_ERR_OVERFLOW.  n == 0: an operand without entries, no launch. */
+enum smm_interp_method { SMM_INTERP_LINEAR = 0, SMM_INTERP_NEAREST = 1 };
+enum smm_interp_outside { SMM_INTERP_REJECT = 0, SMM_INTERP_CLAMP = 1, SMM_INTERP_ZERO = 2 };
+int  smm_interp_build(smm_ctx *ctx, int dim, const int64_t *axis_len, const double *axes, int method, int outside,
+                      int64_t n, const double *d_pts, int64_t ldp, smm_csr **out);
+/* Same with the points in host memory (uploaded through a pool temporary). */
+int  smm_interp_build_host(smm_ctx *ctx, int dim, const int64_t *axis_len, const double *axes, int method, int outside,
+                           int64_t n, const double *pts, int64_t ldp, smm_csr **out);
+
 /* ------------------------------------------------------------------ conjugate gradients on (H Q H^T + R) Z = D
  * S = H Q H^T is never formed (H: n x K, Q: K x K, R: n x n sparse or NULL for S alone; the system is expected to be
  * symmetric positive definite).  B (the right-hand sides D) and X (the solution Z) are n x k row-major float64 with

@@ -24,6 +24,11 @@ SMM_TRANSPOSE = 16
 SMM_SCALE_BY_MASK = 32
 SMM_TAPER_BOXCAR = 0
 SMM_TAPER_GASPARI_COHN = 1
+SMM_INTERP_LINEAR = 0
+SMM_INTERP_NEAREST = 1
+SMM_INTERP_REJECT = 0
+SMM_INTERP_CLAMP = 1
+SMM_INTERP_ZERO = 2
 SMM_ERR_INVALID = -2
 SMM_ERR_ALLOC = -3
 SMM_ERR_OVERFLOW = -5
@@ -118,6 +123,8 @@ V2_PROTOTYPES = {
     "smm_taper_build": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64, _pp]),
     "smm_taper_build_host": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64,
                                             _pp]),
+    "smm_interp_build": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, _c_i64, _vp, _c_i64, _pp]),
+    "smm_interp_build_host": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, _c_i64, _vp, _c_i64, _pp]),
     "smm_innovation_solve": (ctypes.c_int, [_vp] * 4 + _SOLVE),
     "smm_innovation_solve_host": (ctypes.c_int, [_vp] * 4 + _SOLVE),
     "smm_kron_build": (ctypes.c_int, [_vp, _vp, _vp, _pp]),

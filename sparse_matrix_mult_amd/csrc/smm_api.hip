@@ -13,6 +13,7 @@
 #include "smm_slq.hpp"
 #include "smm_sddmm.hpp"
 #include "smm_taper.hpp"
+#include "smm_interp.hpp"
 #include "../../include/smm_hip.h"
 
 #include <sys/mman.h>
@@ -109,6 +110,7 @@ struct smm_ctx {
     int spmm_mode = 0;                     // sparse x dense: 0 rows binned by length, 1 / 2 / 3 every row in the tiny / group / long class
     int64_t apply_budget = (int64_t)1 << 30;   // smm_triple_apply: bytes of the two intermediates of one column block
     int sddmm_mode = 0;                    // sampled dense product: 0 chosen from nnz(mask), 1 interleaved entries, 2 runs of entries
+    int interp_stage = 1;                  // smm_interp_fill: 1 = axes of at most IP_STAGE_NODES nodes are searched in LDS, 0 = always through L2 (env SMM_INTERP_STAGE)
     int n_cu = 256;
     std::vector<PoolBlock> pool;          // free blocks
     std::map<void *, size_t> live;        // blocks handed out
@@ -289,6 +291,7 @@ extern "C" int smm_ctx_create(int device, void *hip_stream, smm_ctx **out)
     if (const char *e = getenv("SMM_PACK_STRIDE")) c->pack_stride = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("SMM_SYM_MAX_WS")) c->sym_max_ws = std::max(0, std::min(atoi(e), (int)CCS_MAX_WS));
     if (const char *e = getenv("SMM_CHECK")) c->check = atoi(e) != 0;
+    if (const char *e = getenv("SMM_INTERP_STAGE")) c->interp_stage = atoi(e) != 0;
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (hip_stream == SMM_STREAM_DEFAULT) { c->stream = nullptr; c->own_stream = false; }   // the device's null stream
     else if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->own_stream = false; }
@@ -2990,6 +2993,133 @@ extern "C" int smm_taper_build_host(smm_ctx *c, int dim, int kind, double cutoff
     CHK(upload_rows(c, da, a, na, dim, lda));
     if (!same) CHK(upload_rows(c, db, b, nb, dim, ldb));
     return taper_dispatch(c, dim, kind, cutoff, na, da, dim, nb, same ? (const double *)da : (const double *)db, dim, out);
+}
+
+// ------------------------------------------------------------------------------ observation operator from coordinates
+// (kernels: smm_interp.hpp; contract: include/smm_hip.h)
+
+// Everything smm_interp_build[_host] refuse before any launch; on success A holds the grid (not yet the device arrays).
+static int interp_args(smm_ctx *c, int dim, const int64_t *axis_len, const double *axes, int method, int outside, int64_t n,
+                       const double *pts, int64_t ldp, smm_csr **out, const char *where, InterpArgs *A)
+{
+    if (!out) return fail(SMM_ERR_INVALID, "%s: out is NULL", where);
+    *out = nullptr;
+    if (!c) return fail(SMM_ERR_INVALID, "%s: ctx is NULL", where);
+    if (dim < 1 || dim > IP_MAX_DIM) return fail(SMM_ERR_INVALID, "%s: dim must be 1, 2, 3 or 4, got %d", where, dim);
+    if (method != SMM_INTERP_LINEAR && method != SMM_INTERP_NEAREST) return fail(SMM_ERR_INVALID, "%s: unknown method %d", where, method);
+    if (outside != SMM_INTERP_REJECT && outside != SMM_INTERP_CLAMP && outside != SMM_INTERP_ZERO)
+        return fail(SMM_ERR_INVALID, "%s: unknown policy %d for points outside the grid", where, outside);
+    if (!axis_len || !axes) return fail(SMM_ERR_INVALID, "%s: axis_len or axes is NULL", where);
+    int64_t K = 1, nodes = 0;
+    for (int t = 0; t < dim; ++t) {
+        const int64_t m = axis_len[t];
+        if (m < 2) return fail(SMM_ERR_INVALID, "%s: axis %d has %lld nodes, an axis needs at least 2", where, t, (long long)m);
+        if (m >= INT32_MAX || K > (int64_t)(INT32_MAX - 1) / m)
+            return fail(SMM_ERR_INVALID, "%s: the grid must have fewer than 2^31 - 1 nodes (an operand's columns)", where);
+        const double *a = axes + nodes;
+        for (int64_t j = 0; j < m; ++j) {
+            if (!std::isfinite(a[j])) return fail(SMM_ERR_INVALID, "%s: node %lld of axis %d is not finite", where, (long long)j, t);
+            if (j > 0 && !(a[j] > a[j - 1]))
+                return fail(SMM_ERR_INVALID, "%s: axis %d is not strictly ascending at node %lld", where, t, (long long)j);
+        }
+        A->m[t] = (int)m; A->off[t] = (int)nodes; A->lo[t] = a[0]; A->hi[t] = a[m - 1];
+        K *= m;
+        nodes += m;
+    }
+    for (int t = dim - 1, s = 1; t >= 0; --t) { A->stride[t] = s; s *= A->m[t]; }          // (row-major, axis 0 slowest; ends at K)
+    A->nodes = (int)nodes; A->K = (int)K; A->outside = outside;
+    if (n < 0 || n >= INT32_MAX) return fail(SMM_ERR_INVALID, "%s: the number of points must be in [0, 2^31 - 1), got %lld", where, (long long)n);
+    if (ldp < dim) return fail(SMM_ERR_INVALID, "%s: need ldp >= dim (dim %d, ldp %lld)", where, dim, (long long)ldp);
+    if (n > 0 && !pts) return fail(SMM_ERR_INVALID, "%s: the points are NULL", where);
+    const int64_t per_row = method == SMM_INTERP_NEAREST ? 1 : (int64_t)1 << dim;
+    if (n > (int64_t)(INT32_MAX - 1) / per_row)
+        return fail(SMM_ERR_OVERFLOW, "%s: %lld rows of %lld entries do not fit an operand (int32 row pointers, nnz <= 2^31 - 2)", where,
+                    (long long)n, (long long)per_row);
+    A->n = n; A->ldp = ldp; A->pts = pts;
+    HIPCHK(hipSetDevice(c->device));
+    return SMM_OK;
+}
+
+template <int DIM>
+static int interp_impl(smm_ctx *c, InterpArgs A, const double *axes, int method, const char *where, CsrPtr *out)
+{
+    const int64_t per_row = method == SMM_INTERP_NEAREST ? 1 : (int64_t)1 << DIM;
+    PoolBuf<double> d_axes(c);
+    PoolBuf<unsigned long long> counts(c);
+    CHK(d_axes.alloc((size_t)A.nodes));
+    CHK(counts.alloc(2));
+    HIPCHK(hipMemcpyAsync(d_axes, axes, (size_t)A.nodes * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    A.axes = d_axes; A.counts = counts; A.err = c->d_err;
+    const int cgrid = (int)std::min<int64_t>((A.n + 255) / 256, (int64_t)c->n_cu * 8);
+    LAUNCH(c, "smm_interp_check", smm_interp_check<DIM>, cgrid, 256, 0, A);
+    LAUNCH_CHECK();
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h[0] > 0) return fail(SMM_ERR_INVALID, "%s: %llu coordinates are not finite (NaN or inf)", where, h[0]);
+    if (h[1] > 0 && A.outside == SMM_INTERP_REJECT)
+        return fail(SMM_ERR_INVALID, "%s: %llu points lie outside the grid (SMM_INTERP_CLAMP or SMM_INTERP_ZERO accept them)", where, h[1]);
+
+    CsrPtr m = new_csr(c, A.n, A.K, A.n * per_row);
+    CHK(alloc_owned(c, m.get(), "the interpolation operand"));
+    A.optr = m->own_ptr; A.oidx = m->own_idx; A.oval = m->own_val;
+    const int64_t chunks = (m->nnz + 3) / 4;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((std::max(chunks, A.n + 1) + 255) / 256, (int64_t)c->n_cu * 8));
+    const bool stage = c->interp_stage && A.nodes <= IP_STAGE_NODES;
+    const size_t lds = stage ? (size_t)A.nodes * sizeof(double) : 0;
+    if (method == SMM_INTERP_NEAREST) {
+        if (stage) LAUNCH(c, "smm_interp_fill", (smm_interp_fill<DIM, true, true>), grid, 256, lds, A);
+        else LAUNCH(c, "smm_interp_fill", (smm_interp_fill<DIM, true, false>), grid, 256, lds, A);
+    } else {
+        if (stage) LAUNCH(c, "smm_interp_fill", (smm_interp_fill<DIM, false, true>), grid, 256, lds, A);
+        else LAUNCH(c, "smm_interp_fill", (smm_interp_fill<DIM, false, false>), grid, 256, lds, A);
+    }
+    LAUNCH_CHECK();
+    CHK(take_plan_error(c, where));                          // (synchronises: the temporaries may go back to the pool)
+    // The flags smm_validate would find, by construction: ptr is i * per_row, and inside a row the columns ascend strictly
+    // with the entry number (stride_t >= 2 stride_{t+1}); the fill has just reported that every column is inside [0, K).
+    m->validated = true;
+    m->vflags = 0;
+    *out = std::move(m);
+    return SMM_OK;
+}
+
+static int interp_dispatch(smm_ctx *c, int dim, const InterpArgs &A, const double *axes, int method, const char *where, smm_csr **out)
+{
+    CsrPtr m;
+    if (A.n == 0) CHK(empty_csr(c, 0, A.K, &m));
+    else if (dim == 1) CHK(interp_impl<1>(c, A, axes, method, where, &m));
+    else if (dim == 2) CHK(interp_impl<2>(c, A, axes, method, where, &m));
+    else if (dim == 3) CHK(interp_impl<3>(c, A, axes, method, where, &m));
+    else CHK(interp_impl<4>(c, A, axes, method, where, &m));
+    *out = m.release();
+    return SMM_OK;
+}
+
+extern "C" int smm_interp_build(smm_ctx *c, int dim, const int64_t *axis_len, const double *axes, int method, int outside, int64_t n,
+                                const double *d_pts, int64_t ldp, smm_csr **out)
+{
+    InterpArgs A{};
+    CHK(interp_args(c, dim, axis_len, axes, method, outside, n, d_pts, ldp, out, "smm_interp_build", &A));
+    CTX_LOCK(c);
+    return interp_dispatch(c, dim, A, axes, method, "smm_interp_build", out);
+}
+
+// Same with the points in host memory.
+extern "C" int smm_interp_build_host(smm_ctx *c, int dim, const int64_t *axis_len, const double *axes, int method, int outside, int64_t n,
+                                     const double *pts, int64_t ldp, smm_csr **out)
+{
+    InterpArgs A{};
+    CHK(interp_args(c, dim, axis_len, axes, method, outside, n, pts, ldp, out, "smm_interp_build_host", &A));
+    CTX_LOCK(c);
+    PoolBuf<double> dp(c);
+    if (n > 0) {
+        CHK(dp.alloc((size_t)n * dim));
+        CHK(upload_rows(c, dp, pts, n, dim, ldp));
+        A.pts = dp; A.ldp = dim;
+    }
+    return interp_dispatch(c, dim, A, axes, method, "smm_interp_build_host", out);
 }
 
 // ------------------------------------------------------------------------------ triple product, sparse output

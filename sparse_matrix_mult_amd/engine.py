@@ -9,23 +9,33 @@ import threading
 
 import numpy as np
 
-from ._lib import (SMM_EXACT, SMM_FULL_MATRIX, SMM_MIRROR, SMM_SCALE_BY_MASK, SMM_SYMMETRIC, SMM_TAPER_BOXCAR, SMM_TAPER_GASPARI_COHN,
-                   SMM_TRANSPOSE, SmmError, SmmLibrary, check)
+from ._lib import (SMM_EXACT, SMM_FULL_MATRIX, SMM_INTERP_CLAMP, SMM_INTERP_LINEAR, SMM_INTERP_NEAREST, SMM_INTERP_REJECT, SMM_INTERP_ZERO,
+                   SMM_MIRROR, SMM_SCALE_BY_MASK, SMM_SYMMETRIC, SMM_TAPER_BOXCAR, SMM_TAPER_GASPARI_COHN, SMM_TRANSPOSE, SmmError, SmmLibrary,
+                   check)
 
 __all__ = ["Context", "DeviceCSR", "default_context", "SmmError",
            "SMM_SYMMETRIC", "SMM_FULL_MATRIX", "SMM_EXACT", "SMM_MIRROR", "SMM_TRANSPOSE", "SMM_SCALE_BY_MASK",
-           "SMM_TAPER_BOXCAR", "SMM_TAPER_GASPARI_COHN", "TAPER_KINDS"]
+           "SMM_TAPER_BOXCAR", "SMM_TAPER_GASPARI_COHN", "TAPER_KINDS",
+           "SMM_INTERP_LINEAR", "SMM_INTERP_NEAREST", "SMM_INTERP_REJECT", "SMM_INTERP_CLAMP", "SMM_INTERP_ZERO", "INTERP_METHODS",
+           "INTERP_OUTSIDE"]
 
 TAPER_KINDS = {"boxcar": SMM_TAPER_BOXCAR, "gaspari_cohn": SMM_TAPER_GASPARI_COHN}
+INTERP_METHODS = {"linear": SMM_INTERP_LINEAR, "nearest": SMM_INTERP_NEAREST}
+INTERP_OUTSIDE = {"error": SMM_INTERP_REJECT, "clamp": SMM_INTERP_CLAMP, "zero": SMM_INTERP_ZERO}
+
+
+def _named(value, table, what):
+    """The number of a name of `table`, or the number itself."""
+    if isinstance(value, str):
+        if value not in table:
+            raise ValueError(f"unknown {what} {value!r}: expected one of {sorted(table)}")
+        return table[value]
+    return int(value)
 
 
 def _taper_kind(kind):
     """SMM_TAPER_* for a name of TAPER_KINDS or the number itself."""
-    if isinstance(kind, str):
-        if kind not in TAPER_KINDS:
-            raise ValueError(f"unknown taper {kind!r}: expected one of {sorted(TAPER_KINDS)}")
-        return TAPER_KINDS[kind]
-    return int(kind)
+    return _named(kind, TAPER_KINDS, "taper")
 
 
 def _flags(symmetric=False, exact=False, full=False, mirror=False):
@@ -534,6 +544,42 @@ class Context:
         check(self.lib, self.lib.smm_taper_build(self.handle, int(dim), kind, float(cutoff), int(na), ctypes.c_void_p(_dptr(d_a)), int(lda),
                                                  int(nb), ctypes.c_void_p(_dptr(d_b)), int(ldb), ctypes.byref(h)))
         return DeviceCSR(self, h, int(na), int(nb), int(self.lib.smm_csr_nnz(h)))
+
+    # ------------------------------------------------------------------ observation operator from coordinates
+    @staticmethod
+    def _host_axes(axes, dim):
+        """(axis_len int64[dim], nodes float64[sum]) of a sequence of 1-D arrays (one array: a line): the two host arrays of
+        smm_interp_build.  Only the shapes are checked here; the library checks the values."""
+        if isinstance(axes, np.ndarray) and axes.ndim == 1:
+            axes = [axes]
+        axes = [np.asarray(a, dtype=np.float64) for a in axes]
+        if len(axes) != dim or any(a.ndim != 1 for a in axes):
+            raise ValueError(f"the points have {dim} coordinates, axes holds {len(axes)} arrays (each must be 1-D)")
+        return np.array([a.size for a in axes], dtype=np.int64), np.ascontiguousarray(np.concatenate(axes) if axes else np.zeros(0))
+
+    def interp_host(self, points, axes, method="linear", outside="error"):
+        """The matrix that interpolates a field on the rectilinear grid `axes` (a sequence of 1-D ascending arrays, axis 0
+        slowest) to the numpy points (n x dim, or n on a line): 2^dim multilinear weights per row, or one 1.0 at the
+        nearest node, rows strictly ascending, as a new DeviceCSR (smm_interp_build_host)."""
+        method, outside = _named(method, INTERP_METHODS, "method"), _named(outside, INTERP_OUTSIDE, "policy")
+        p, dim = self._host_points(points, "points")
+        lens, nodes = self._host_axes(axes, dim)
+        h = ctypes.c_void_p()
+        check(self.lib, self.lib.smm_interp_build_host(self.handle, dim, _ptr(lens), _ptr(nodes), method, outside, p.shape[0], _ptr(p), dim,
+                                                       ctypes.byref(h)))
+        return DeviceCSR(self, h, p.shape[0], int(self.lib.smm_csr_cols(h)), int(self.lib.smm_csr_nnz(h)))
+
+    def interp_into(self, d_pts, ldp, n, dim, axes, method="linear", outside="error"):
+        """interp_host on a device buffer: the points (n x dim, leading dimension ldp) at d_pts, used where they are
+        (smm_interp_build); the axes stay host arrays.  An int (device address) or a torch tensor; stream rules as
+        spmm_into.  Returns the DeviceCSR, which the library owns: nothing of the caller's is kept."""
+        method, outside = _named(method, INTERP_METHODS, "method"), _named(outside, INTERP_OUTSIDE, "policy")
+        lens, nodes = self._host_axes(axes, int(dim))
+        self._sync_all(d_pts)
+        h = ctypes.c_void_p()
+        check(self.lib, self.lib.smm_interp_build(self.handle, int(dim), _ptr(lens), _ptr(nodes), method, outside, int(n),
+                                                  ctypes.c_void_p(_dptr(d_pts)), int(ldp), ctypes.byref(h)))
+        return DeviceCSR(self, h, int(n), int(self.lib.smm_csr_cols(h)), int(self.lib.smm_csr_nnz(h)))
 
     # ------------------------------------------------------------------ Kronecker operand Q = D (x) E
     def kron_build(self, d, e):

@@ -22,7 +22,7 @@ import numpy as np
 from scipy.sparse import csr_matrix, isspmatrix_csr
 
 from ._lib import SMM_ERR_ALLOC, SmmError, SmmLibrary
-from .engine import TAPER_KINDS, SolveInfo, default_context
+from .engine import INTERP_METHODS, INTERP_OUTSIDE, TAPER_KINDS, SolveInfo, default_context
 
 _INT32_MAX = np.iinfo(np.int32).max
 
@@ -583,6 +583,115 @@ def localization_taper(coords, cutoff, coords_b=None, taper="gaspari_cohn", pin=
     handle = _on_device(ctx, lambda: ctx.taper_into(da, max(int(da.stride(0)), dim), db, max(int(db.stride(0)), dim), na, nb, dim,
                                                     cutoff, taper))
     return _taper_result(handle, (na, nb), pin)
+
+
+# ------------------------------------------------------------------ observation operator from coordinates
+def _interp_axes(axes, what):
+    """The grid as a list of 1-D float64 arrays; `axes` is a sequence of 1-D arrays, or one array for a line.  ValueError
+    for anything the library would refuse."""
+    if type(axes).__module__.split(".")[0] == "torch":
+        raise ValueError(f"{what}: axes are host arrays (a sequence of 1-D numpy arrays), not tensors")
+    if isinstance(axes, np.ndarray) and axes.ndim == 1 and axes.dtype != object:
+        axes = [axes]
+    try:
+        axes = [np.asarray(a, dtype=np.float64) for a in axes]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: axes must be a sequence of 1-D arrays of numbers") from None
+    if not 1 <= len(axes) <= 4:
+        raise ValueError(f"{what}: the grid has {len(axes)} axes, expected 1 to 4")
+    for t, a in enumerate(axes):
+        if a.ndim != 1:
+            raise ValueError(f"{what}: axis {t} must be 1-D, got {a.ndim} dimensions")
+        if a.size < 2:
+            raise ValueError(f"{what}: axis {t} has {a.size} nodes, an axis needs at least 2")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{what}: axis {t} has nodes that are not finite")
+        if not np.all(a[1:] > a[:-1]):
+            raise ValueError(f"{what}: axis {t} is not strictly ascending")
+    return axes
+
+
+def interpolation_operator(points, axes, method="linear", outside="error", pin=False):
+    """The observation operator H of a rectilinear grid, built on the GPU: the n x K matrix that interpolates a field given
+    on the grid's K nodes to n points -- the matrix_h of triple_product_apply, innovation_solve and innovation_logdet.
+
+    points  : n x dim (dim 1 to 4) or 1-D (n points on a line); a numpy array (cast to float64) or a float64 CUDA tensor
+              on the library's device with unit column stride (a column slice of a wider tensor is used in place).
+    axes    : a sequence of dim 1-D arrays, or one array for a line: the nodes of every axis, finite and strictly
+              ascending, at least 2 each, spacing free.  K = the product of their lengths; node (j_0, ..., j_{dim-1}) is
+              column (j_0 * m_1 + j_1) * m_2 + ... -- `field.ravel()` of a C-ordered field[j_0, ..., j_{dim-1}].  With time
+              as axis 0 these are the columns of KroneckerOperand(D, E).
+    method  : "linear" -- 2^dim multilinear weights per row, at the corners of the point's cell -- or "nearest" -- one
+              entry 1.0 at the nearest node (a tie goes to the lower node).
+    outside : what a point outside [first node, last node] in some axis does.  "error" (default): the call fails
+              (SmmError) and says how many there are.  "clamp": constant extrapolation from the edge.  "zero": the row
+              keeps its columns and holds zeros -- the observation sees nothing.
+    pin     : False returns a scipy CSR (int32 indices, canonical), or a DeviceCSRResult under set_result_device(True).
+              True returns a PinnedOperand that adopts the library's operand where it is -- no copy to the host.
+    Pattern and values are bit-identical to the order written out in include/smm_hip.h; the row pointer is i * 2^dim (or
+    i).  Argument errors are ValueError before any device call; NaN or infinite coordinates are refused by the library
+    (SmmError).  Without points the result is empty and no device is touched.  Nothing is printed.
+    """
+    what = "interpolation_operator"
+    for value, table, name in ((method, INTERP_METHODS, "method"), (outside, INTERP_OUTSIDE, "policy")):
+        if not isinstance(value, str) or value not in table:
+            raise ValueError(f"{what}: unknown {name} {value!r}, expected one of {sorted(table)}")
+    axes = _interp_axes(axes, what)
+    is_torch = type(points).__module__.split(".")[0] == "torch"
+    if is_torch:
+        import torch
+        if points.dtype != torch.float64 or not points.is_cuda:
+            raise ValueError(f"{what}: a torch points must be a float64 CUDA tensor")
+        ndim = points.dim()
+    else:
+        points = np.asarray(points, dtype=np.float64)
+        ndim = points.ndim
+    if ndim not in (1, 2):
+        raise ValueError(f"{what}: points must be 1-D (points on a line) or 2-D (n x dim), got {ndim} dimensions")
+    n, dim = int(points.shape[0]), (1 if ndim == 1 else int(points.shape[1]))
+    if dim != len(axes):
+        raise ValueError(f"{what}: points has {dim} coordinates per point, the grid has {len(axes)} axes")
+    K = 1
+    for a in axes:
+        K *= a.size
+    per_row = 1 if method == "nearest" else 2 ** dim
+    if K >= _INT32_MAX or n >= _INT32_MAX:
+        raise ValueError(f"{what}: {n} points on {K} nodes: both must be below 2^31 - 1 (an operand's dimensions)")
+    if n * per_row > _INT32_MAX - 1:
+        raise ValueError(f"{what}: {n} rows of {per_row} entries do not fit one operand (int32 row pointers, at most 2^31 - 2)")
+    shape = (n, K)
+    if n == 0:
+        return PinnedOperand._adopt(None, None, shape) if pin else _zero_result(shape)
+    ctx = default_context()
+    if not is_torch:
+        def build():
+            return ctx.interp_host(np.ascontiguousarray(points.reshape(n, dim)), axes, method, outside)
+    else:
+        dev = torch.device("cuda", ctx.device)
+        if points.device != dev:
+            raise ValueError(f"{what}: points is on {points.device}, the library works on {dev}")
+        if points.stride(0) < dim or (ndim == 2 and points.stride(1) != 1):      # (an expanded or transposed view)
+            points = points.contiguous()
+        ldp = int(points.stride(0))
+
+        def build():
+            return ctx.interp_into(points, ldp, n, dim, axes, method, outside)
+    if pin or not _result_device:
+        return _taper_result(_on_device(ctx, build) if is_torch else build(), shape, pin)
+    import torch
+    dev = torch.device("cuda", ctx.device)
+
+    def call():
+        handle = build()
+        try:
+            indptr, indices = handle.pattern_torch()
+            data = torch.empty(handle.nnz, dtype=torch.float64, device=dev)
+            handle.values_into(data)
+            return DeviceCSRResult(indptr.to(torch.int64), indices, data, shape)
+        finally:
+            handle.close()
+
+    return _on_device(ctx, call)
 
 
 # ------------------------------------------------------------------ Kronecker operand Q = D (x) E
