@@ -251,7 +251,12 @@ void smm_plan_destroy(smm_plan *plan);
  * (the reference's first-touch order).  Any row length: mirrored segments of up to 8192 entries are sorted in LDS,
  * longer ones (results as full as the BASELINE configs') are placed by rank -- the columns of a segment are distinct,
  * so an entry's sorted position is the number of set bits below its column in a bitmap of the segment.  Entries left
- * of the diagonal in the input are refused with SMM_ERR_INVALID. */
+ * of the diagonal in the input are refused with SMM_ERR_INVALID.
+ * An input without entries: _symbolic reads d_indices only through the row pointer, so it may be NULL there; it writes
+ * n+1 zeros and returns nnz_full = 0, and that row pointer IS the result.  _fill has nothing to do then and is not to be
+ * called: for n > 0 it refuses a NULL d_indices, d_data, d_full_indices or d_full_data with SMM_ERR_INVALID ("NULL CSR
+ * array") whatever the row pointers say, without reading them.  A caller whose buffers of zero elements have no address
+ * (Context.spgemm_mirrored_torch) returns the zero row pointer and two empty arrays itself. */
 int  smm_csr_mirror_symbolic(smm_ctx *ctx, int64_t n, const int64_t *d_indptr, const int32_t *d_indices,
                              int64_t *d_full_indptr, int64_t *nnz_full);
 int  smm_csr_mirror_fill(smm_ctx *ctx, int64_t n, const int64_t *d_indptr, const int32_t *d_indices, const double *d_data,

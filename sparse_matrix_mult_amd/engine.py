@@ -247,7 +247,16 @@ class Context:
         n = a.rows
         dev = torch.device("cuda", self.device)
         plan = self.spgemm_plan(a, b, symmetric=True, exact=exact)
+
+        def empty():
+            # the mirror of an upper triangle without entries is the empty n x n matrix; smm_csr_mirror_fill wants arrays
+            # that exist (include/smm_hip.h), and a torch tensor of no elements has none
+            return (torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                    torch.empty(0, dtype=torch.float64, device=dev))
+
         try:
+            if plan.nnz == 0:
+                return empty()
             up = torch.empty(n + 1, dtype=torch.int64, device=dev)
             ui = torch.empty(plan.nnz, dtype=torch.int32, device=dev)
             uv = torch.empty(plan.nnz, dtype=torch.float64, device=dev)
@@ -258,6 +267,8 @@ class Context:
         nnz = ctypes.c_int64()
         vp = ctypes.c_void_p
         check(self.lib, self.lib.smm_csr_mirror_symbolic(self.handle, n, vp(up.data_ptr()), vp(ui.data_ptr()), vp(fp.data_ptr()), ctypes.byref(nnz)))
+        if nnz.value == 0:
+            return empty()
         fi = torch.empty(nnz.value, dtype=torch.int32, device=dev)
         fv = torch.empty(nnz.value, dtype=torch.float64, device=dev)
         check(self.lib, self.lib.smm_csr_mirror_fill(self.handle, n, vp(up.data_ptr()), vp(ui.data_ptr()), vp(uv.data_ptr()), vp(fp.data_ptr()),
