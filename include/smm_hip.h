@@ -181,7 +181,9 @@ int64_t smm_csr_nnz(const smm_csr *m);
  * again on them: a product with an unchanged pattern costs the numeric phase only.
  * _device: the new values are already in HBM at d_data (copied, for operands made by smm_csr_from_host), or
  * d_data is NULL / the operand's own borrowed array, which the caller has rewritten in place (operands made
- * by smm_csr_from_device): only the cached copies are refreshed. */
+ * by smm_csr_from_device): only the cached copies are refreshed.  The stream rule of smm_csr_from_device applies to the
+ * values: the refresh is queued on the context's stream without a wait of the host, so they must be complete on that
+ * stream, or the caller synchronises first. */
 int  smm_csr_update_values(smm_ctx *ctx, smm_csr *m, const double *data);
 int  smm_csr_update_values_device(smm_ctx *ctx, smm_csr *m, const double *d_data);
 /* A^T as a new operand owned by the caller (smm_csr_destroy), built on the device: its arrays are exactly those of
@@ -214,7 +216,10 @@ int  smm_row_products(smm_ctx *ctx, const smm_csr *a, const smm_csr *b, int64_t 
  * c_indices / c_data (device) of that size; numeric fills indptr (int64, a.rows+1),
  * indices (int32, reference order) and data.
  * a_row_offset: global index of A's row 0 when A is one contiguous row shard of a larger
- * matrix (only the SMM_SYMMETRIC filter i <= col looks at it). */
+ * matrix (only the SMM_SYMMETRIC filter i <= col looks at it).
+ * The stream rule of smm_csr_from_device applies to the output buffers of smm_spgemm_numeric: it fills them on the
+ * context's stream and may return before they are complete, so nothing on another stream may still use them when it is
+ * called, and the caller orders its reads behind that stream (smm_ctx_synchronize, which also reports a plan error). */
 int  smm_spgemm_symbolic(smm_ctx *ctx, smm_csr *a, smm_csr *b, int flags, int64_t a_row_offset,
                          smm_plan **plan, int64_t *nnz_out);
 int  smm_spgemm_numeric(smm_ctx *ctx, smm_plan *plan,

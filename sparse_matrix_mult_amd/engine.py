@@ -187,10 +187,7 @@ class Context:
         """Borrow int32/int32/float64 CUDA tensors already in HBM (kept alive by the handle).  The
         tensors must be complete before the library reads them: when the context does not launch on
         torch's current stream, that stream is synchronised here."""
-        import torch
-        cur = torch.cuda.current_stream(indices.device)
-        if self.stream is None or int(cur.cuda_stream) != self.stream:
-            cur.synchronize()
+        self._wait_for_torch(indices.device)
         nnz = int(indices.numel())
         h = ctypes.c_void_p()
         check(self.lib, self.lib.smm_csr_from_device(self.handle, rows, cols, nnz, ctypes.c_void_p(indptr.data_ptr()),
@@ -225,7 +222,7 @@ class Context:
             plan.close()
 
     def spgemm_torch(self, a, b, symmetric=False, row_offset=0, exact=False):
-        """Same product with the result left in HBM as torch tensors (indptr int64)."""
+        """Same product with the result left in HBM as torch tensors (indptr int64); stream rule: _wait_for_torch."""
         import torch
         plan = self.spgemm_plan(a, b, symmetric, row_offset, exact)
         try:
@@ -233,14 +230,16 @@ class Context:
             indptr = torch.empty(a.rows + 1, dtype=torch.int64, device=dev)
             indices = torch.empty(plan.nnz, dtype=torch.int32, device=dev)
             data = torch.empty(plan.nnz, dtype=torch.float64, device=dev)
+            self._wait_for_torch(dev)                 # (the allocator may hand out a block torch's stream still uses)
             plan.numeric_into(indptr.data_ptr(), indices.data_ptr(), data.data_ptr())
+            self._finish_for_torch(dev)
         finally:
             plan.close()
         return indptr, indices, data
 
     def spgemm_mirrored_torch(self, a, b, exact=False):
         """spgemm_host_mirrored with the full symmetric CSR left in HBM: (indptr int64, indices int32, data float64)
-        torch tensors."""
+        torch tensors; stream rule: _wait_for_torch, before each of the two halves writes into torch's memory."""
         import torch
         if a.rows != b.cols:
             raise ValueError("For symmetric output, the resulting matrix must be square.")
@@ -260,10 +259,11 @@ class Context:
             up = torch.empty(n + 1, dtype=torch.int64, device=dev)
             ui = torch.empty(plan.nnz, dtype=torch.int32, device=dev)
             uv = torch.empty(plan.nnz, dtype=torch.float64, device=dev)
+            fp = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            self._wait_for_torch(dev)
             plan.numeric_into(up.data_ptr(), ui.data_ptr(), uv.data_ptr())
         finally:
             plan.close()
-        fp = torch.empty(n + 1, dtype=torch.int64, device=dev)
         nnz = ctypes.c_int64()
         vp = ctypes.c_void_p
         check(self.lib, self.lib.smm_csr_mirror_symbolic(self.handle, n, vp(up.data_ptr()), vp(ui.data_ptr()), vp(fp.data_ptr()), ctypes.byref(nnz)))
@@ -271,9 +271,10 @@ class Context:
             return empty()
         fi = torch.empty(nnz.value, dtype=torch.int32, device=dev)
         fv = torch.empty(nnz.value, dtype=torch.float64, device=dev)
+        self._wait_for_torch(dev)
         check(self.lib, self.lib.smm_csr_mirror_fill(self.handle, n, vp(up.data_ptr()), vp(ui.data_ptr()), vp(uv.data_ptr()), vp(fp.data_ptr()),
                                                      vp(fi.data_ptr()), vp(fv.data_ptr())))
-        self.synchronize()
+        self._finish_for_torch(dev)
         return fp, fi, fv
 
     def _dmalloc(self, nbytes):
@@ -380,7 +381,8 @@ class Context:
             self.lib.smm_result_destroy(r)
 
     def triple_sparse_torch(self, h, q, full=False, row_begin=0, row_end=None, exact=False, mask=None):
-        """triple_sparse_host with the result left in HBM: (indptr int64, indices int32, data float64) torch tensors."""
+        """triple_sparse_host with the result left in HBM: (indptr int64, indices int32, data float64) torch tensors;
+        stream rule: _wait_for_torch."""
         import torch
         r, rows, nnz = self._triple_sparse(h, q, full, row_begin, row_end, exact, mask)
         try:
@@ -388,8 +390,10 @@ class Context:
             indptr = torch.empty(rows + 1, dtype=torch.int64, device=dev)
             indices = torch.empty(nnz, dtype=torch.int32, device=dev)
             data = torch.empty(nnz, dtype=torch.float64, device=dev)
+            self._wait_for_torch(dev)
             check(self.lib, self.lib.smm_result_copy_device(self.handle, r, ctypes.c_void_p(indptr.data_ptr()),
                                                             ctypes.c_void_p(indices.data_ptr()), ctypes.c_void_p(data.data_ptr())))
+            self._finish_for_torch(dev)
             return indptr, indices, data
         finally:
             self.lib.smm_result_destroy(r)
@@ -419,15 +423,31 @@ class Context:
         long class) and the bytes of triple_apply's two intermediates per column block (0 = default, 1 GiB)."""
         check(self.lib, self.lib.smm_ctx_tune_spmm(self.handle, int(mode), int(apply_budget_bytes)))
 
+    # The stream rule, for every torch tensor the library reads, writes or returns.  Shared stream (the context launches on
+    # torch's current stream): nothing to do, stream order holds and the host does not wait.  Different streams: torch's
+    # current stream is drained before the library reads torch's memory or writes into it (_wait_for_torch), and the
+    # context is synchronised before a torch tensor goes back to the caller (_finish_for_torch).
+    def _torch_stream_apart(self, device=None):
+        """Torch's current stream on the device, or None when the context launches on that very stream."""
+        import torch
+        cur = torch.cuda.current_stream(torch.device("cuda", self.device) if device is None else device)
+        return cur if self.stream is None or int(cur.cuda_stream) != self.stream else None
+
+    def _wait_for_torch(self, device=None):
+        cur = self._torch_stream_apart(device)
+        if cur is not None:
+            cur.synchronize()
+
+    def _finish_for_torch(self, device=None):
+        if self._torch_stream_apart(device) is not None:
+            self.synchronize()
+
     def _sync_all(self, *tensors):
-        """Torch's current stream finished with every torch tensor among these before the library reads it (csr_from_torch's
-        rule); an int is a device address, whose ordering is the caller's."""
+        """_wait_for_torch for every torch tensor among these; an int is a device address, whose ordering is the
+        caller's."""
         for t in tensors:
             if hasattr(t, "data_ptr"):
-                import torch
-                cur = torch.cuda.current_stream(t.device)
-                if self.stream is None or int(cur.cuda_stream) != self.stream:
-                    cur.synchronize()
+                self._wait_for_torch(t.device)
 
     @staticmethod
     def _host_x(x):
@@ -738,7 +758,11 @@ class DeviceCSR:
 
     def values_changed(self, d_ptr=None):
         """The values in HBM were rewritten by the caller (borrowed operands: csr_from_torch), or are at device
-        pointer d_ptr (copied over the operand's own array): refresh the cached copies."""
+        pointer d_ptr (copied over the operand's own array): refresh the cached copies.  A borrowed operand's tensors were
+        rewritten on torch's current stream: the stream rule (Context._wait_for_torch) holds for them; a d_ptr's ordering
+        is the caller's."""
+        if self._keep is not None:
+            self.ctx._wait_for_torch(self._keep[2].device)
         check(self.ctx.lib, self.ctx.lib.smm_csr_update_values_device(self.ctx.handle, self.handle,
                                                                       ctypes.c_void_p(d_ptr or 0)))
 
@@ -757,15 +781,19 @@ class DeviceCSR:
         dev = torch.device("cuda", self.ctx.device)
         indptr = torch.empty(self.rows + 1, dtype=torch.int32, device=dev)
         indices = torch.empty(self.nnz, dtype=torch.int32, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
+        self.ctx._wait_for_torch(dev)                                # (smm_csr_copy_device synchronises the context itself)
         check(self.ctx.lib, self.ctx.lib.smm_csr_copy_device(self.ctx.handle, self.handle, ctypes.c_void_p(indptr.data_ptr()),
                                                              ctypes.c_void_p(indices.data_ptr()), None))
         return indptr, indices
 
     def values_into(self, d_data):
         """The operand's values copied into a float64 CUDA tensor (or device address) of nnz entries, device to device
-        (smm_csr_copy_device)."""
+        (smm_csr_copy_device).  A tensor follows the stream rule (Context._wait_for_torch); an address's ordering is the
+        caller's."""
+        self.ctx._sync_all(d_data)
         check(self.ctx.lib, self.ctx.lib.smm_csr_copy_device(self.ctx.handle, self.handle, None, None, ctypes.c_void_p(_dptr(d_data))))
+        if hasattr(d_data, "data_ptr"):
+            self.ctx._finish_for_torch(d_data.device)
 
     def device_bytes(self):
         return int(self.ctx.lib.smm_csr_device_bytes(self.handle)) if self.handle else 0
