@@ -36,7 +36,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "big":
     torch.cuda.empty_cache()
     A, B = mats
     # round 3: what the full-content operand key costs on this host (both operands, all three arrays each)
-    from sparse_matrix_mult_amd.matrix_ops import _operand_key, cache_stats
+    from sparse_matrix_mult_amd.operand_cache import _operand_key, cache_stats
     _, dt_key = timed(lambda: (_operand_key(A), _operand_key(B)))
     _, dt_key2 = timed(lambda: (_operand_key(A), _operand_key(B)))
     print(json.dumps({"operand_keys_both_operands_s": [round(dt_key, 4), round(dt_key2, 4)], "bytes_hashed": int(2 * (A.data.nbytes + A.indices.nbytes + A.indptr.nbytes))}), flush=True)

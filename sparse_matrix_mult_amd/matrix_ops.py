@@ -12,17 +12,15 @@ same argument meaning, same return types, same raised errors.  What differs:
     one swallowed case the reference's callers can observe on purpose, an unknown
     output_format, is kept: message printed, zeros returned.
 """
-import collections
 import os
-import threading
-import weakref
-import ctypes
 
 import numpy as np
 from scipy.sparse import csr_matrix, isspmatrix_csr
 
-from ._lib import SMM_ERR_ALLOC, SmmError, SmmLibrary
 from .engine import INTERP_METHODS, INTERP_OUTSIDE, TAPER_KINDS, SolveInfo, default_context
+# the operand and plan cache (operand_cache.py): the entry points lease their operands through with_leases and take
+# their plans from plan_for; the public names below are re-exported as the same objects
+from .operand_cache import PinnedOperand, cache_stats, clear_cache, plan_for, set_operand_cache, with_leases  # noqa: F401
 
 _INT32_MAX = np.iinfo(np.int32).max
 
@@ -98,380 +96,13 @@ def set_exact(flag):
     return old
 
 
-# ---------------------------------------------------------------------------------------------
-# Operand cache.  The reference re-marshals both operands from the caller's CURRENT arrays on
-# every call (matrix_ops.py:339-340, :187-202); its README's use case is many products on one sparsity
-# pattern (README.md:5,13: covariance matrices).  Here an uploaded operand stays resident in HBM together
-# with what the kernels derive from it (validation, tile index, packed payload, 16-bit columns, the
-# sliced-ELL copy of H), and the symbolic phase of a product stays resident as a plan:
-#   * an operand is recognised by the CONTENT of its three arrays -- a 64-bit hash of every byte
-#     (smm_host_hash64: a chain of bijective steps, so a change of any one element changes it), taken on
-#     every call.  An operand edited in place between two calls is therefore never served stale, and an
-#     equal matrix in other arrays is a hit.  Nothing is assumed from object identity;
-#   * same indptr/indices hashes, other data hash: only the values travel (smm_csr_update_values: the value
-#     array and the value halves of the cached copies are rewritten in place), and
-#   * a product whose two patterns and mode were seen before re-runs only the numeric phase of its cached
-#     plan: no smm_symbolic / smm_runs / smm_segptr launch at all.
-# Entries are dropped when the arrays they were made from have been garbage-collected, least recently used
-# first beyond SMM_OPERAND_CACHE entries (default 4; 0 = marshal afresh on every call, exactly as the
-# reference) or SMM_OPERAND_CACHE_GB of HBM (default 16; what the library reports for each handle and plan,
-# derived copies included), and all at once when an allocation fails (the product is then retried once).
-# pin_operand() is the explicit alternative: a handle the caller owns, no hashing at all.
-_cache_lock = threading.RLock()
-_cache = collections.OrderedDict()          # pattern key -> _Entry; most recently used last
-_plans = collections.OrderedDict()          # (pattern key A, pattern key B, symmetric, exact) -> _PlanEntry
-_cache_entries = int(os.environ.get("SMM_OPERAND_CACHE", "4"))
-_cache_max_bytes = int(float(os.environ.get("SMM_OPERAND_CACHE_GB", "16")) * (1 << 30))
-_plan_entries = int(os.environ.get("SMM_PLAN_CACHE", "2"))
-cache_stats = collections.Counter()         # 'upload', 'hit', 'values_update', 'plan_hit', 'plan_miss' (tests, diagnostics)
-
-
-def _hash(a):
-    a = np.ascontiguousarray(a)
-    return int(SmmLibrary().get_lib().smm_host_hash64(ctypes.c_void_p(a.ctypes.data), a.nbytes))
-
-
-def _operand_key(m):
-    """(pattern key, data key) of a scipy CSR matrix: full-content hashes of indptr / indices and of data.
-    Any in-place edit of any element changes the part it belongs to."""
-    nnz = int(m.indptr[-1]) if len(m.indptr) else 0
-    idx, dat = m.indices[:nnz], m.data[:nnz]
-    pattern = (tuple(m.shape), nnz, m.indptr.dtype.str, idx.dtype.str, _hash(m.indptr), _hash(idx))
-    return pattern, (dat.dtype.str, _hash(dat))
-
-
-class _Entry:
-    # nbytes: HBM of the handle and its cached copies as of its last use (refreshed OUTSIDE _cache_lock: the query takes
-    # the context's lock and would wait for a running product); dead: a PinnedOperand that was unpinned while leased
-    __slots__ = ("handle", "pattern", "data_key", "users", "refs", "nbytes", "dead")
-
-    def __init__(self, handle, pattern, data_key):
-        self.handle, self.pattern, self.data_key, self.users, self.refs = handle, pattern, data_key, 0, []
-        self.nbytes, self.dead = 0, False
-
-    def remember(self, arr):
-        self.refs = [r for r in self.refs if r() is not None]
-        if not any(r() is arr for r in self.refs):
-            try:
-                self.refs.append(weakref.ref(arr))
-            except TypeError:
-                pass
-
-    def orphaned(self):
-        return bool(self.refs) and all(r() is None for r in self.refs)
-
-
-class _PlanEntry:
-    __slots__ = ("plan", "a", "b", "users", "nbytes")
-
-    def __init__(self, plan, a, b, nbytes=0):
-        self.plan, self.a, self.b, self.users, self.nbytes = plan, a, b, 0, nbytes
-
-
-class _Lease:
-    """One call's hold on a device operand: .handle for the engine, .entry when it is a cache entry."""
-    __slots__ = ("handle", "entry", "_transient")
-
-    def __init__(self, handle, entry=None, transient=False):
-        self.handle, self.entry, self._transient = handle, entry, transient
-
-    def release(self):
-        if self.entry is not None:
-            ent = self.entry
-            nbytes = ent.handle.device_bytes() if ent.handle is not None else 0      # (library call: before taking _cache_lock)
-            close = None
-            with _cache_lock:
-                ent.nbytes = nbytes
-                ent.users -= 1
-                if ent.users == 0 and ent.dead:
-                    close = ent.handle               # unpinned while this call was using it
-                elif ent.users == 0 and ent.pattern in _cache:
-                    _trim_locked()                   # what had to stay while it was in use may go now
-            if close is not None:
-                close.close()
-            self.entry = None
-        elif self._transient and self.handle is not None:
-            self.handle.close()
-        self.handle = None
-
-
-def _drop_entry_locked(key):
-    ent = _cache.pop(key, None)
-    if ent is None:
-        return
-    for pk in [pk for pk, pe in _plans.items() if pe.a is ent or pe.b is ent]:
-        pe = _plans.pop(pk)
-        if pe.users == 0:
-            pe.plan.close()                      # (else: _release_plan closes it when the call that runs it ends)
-    if ent.users == 0:
-        ent.handle.close()
-    else:
-        ent.dead = True                          # leased by a running call: its release closes the handle
-
-
-def _cached_bytes_locked():
-    # (byte counts recorded on the entries: no library call -- it would take the context's lock -- under _cache_lock)
-    return sum(e.nbytes for e in _cache.values()) + sum(pe.nbytes for pe in _plans.values())
-
-
-_graveyard = []          # PinnedOperands dropped by the garbage collector: closed by the next _trim_locked (list.append is atomic)
-
-
-def _bury_locked():
-    while _graveyard:
-        ent = _graveyard.pop()
-        for pk in [pk for pk, pe in _plans.items() if pe.a is ent or pe.b is ent]:
-            pe = _plans.pop(pk)
-            if pe.users == 0:
-                pe.plan.close()                  # (a plan in use is closed by _release_plan when its call ends)
-        if ent.users == 0 and ent.handle is not None:
-            ent.handle.close()
-        else:
-            ent.dead = True                      # closed by the lease that still holds it
-
-
-def _trim_locked(keep=(), reserve=0, protect=()):
-    """Enforce the limits (entries idle and not in `keep` only); reserve = entries about to be added; protect =
-    pattern keys this call is about to look up (its other operand)."""
-    _bury_locked()
-    for key in [k for k, e in _cache.items() if e.users == 0 and e.orphaned() and e not in keep and k not in protect]:
-        _drop_entry_locked(key)                  # the arrays it was made from are gone
-
-    def idle_plan():
-        return next((k for k, pe in _plans.items() if pe.users == 0), None)
-
-    def idle_entry():
-        return next((k for k, e in _cache.items() if e.users == 0 and e not in keep and k not in protect), None)
-
-    while len(_plans) > max(_plan_entries, 0) and idle_plan() is not None:
-        _plans.pop(idle_plan()).plan.close()
-    while len(_cache) + reserve > _cache_entries and idle_entry() is not None:
-        _drop_entry_locked(idle_entry())
-    while _cached_bytes_locked() > _cache_max_bytes:
-        if idle_plan() is not None:              # plans (the symbolic phase's lists) go first
-            _plans.pop(idle_plan()).plan.close()
-        elif idle_entry() is not None:
-            _drop_entry_locked(idle_entry())
-        else:
-            break
-
-
-def _acquire(ctx, m, key=None, protect=()):
-    """Device operand for one call (a _Lease).  m: scipy CSR matrix, or a PinnedOperand; key = its
-    _operand_key when the caller has it already."""
-    if isinstance(m, PinnedOperand):
-        return m._lease(ctx)
-    if _cache_entries <= 0:
-        cache_stats["upload"] += 1
-        return _Lease(ctx.csr_from_scipy(m), transient=True)
-    pattern, data_key = key if key is not None else _operand_key(m)
-    with _cache_lock:
-        ent = _cache.get(pattern)
-        if ent is not None and (not ent.handle.handle or ent.handle.ctx is not ctx):
-            _drop_entry_locked(pattern)
-            ent = None
-        update = False
-        if ent is not None:
-            if ent.data_key != data_key:
-                if ent.users > 0:                # another call is multiplying with (or uploading) other values right now
-                    ent = None
-                else:
-                    update = True
-                    ent.data_key = None          # in flux: nobody else may take it for a hit until the values are in HBM
-            else:
-                cache_stats["hit"] += 1
-            if ent is not None:
-                ent.users += 1
-                ent.remember(m.data)
-                _cache.move_to_end(pattern)
-                if not update:
-                    _trim_locked(keep=(ent,), protect=protect)
-                    return _Lease(ent.handle, entry=ent)
-        elif pattern not in _cache:
-            _trim_locked(reserve=1, protect=protect)     # make room before the upload
-        busy = ent is None and pattern in _cache
-    if update:
-        # the host-to-device copy (200 MB at BASELINE configs[1]) runs WITHOUT _cache_lock: the entry is marked in use
-        try:
-            ent.handle.update_values(m.data[:ent.handle.nnz])
-        except BaseException:
-            with _cache_lock:
-                ent.users -= 1
-                if _cache.get(pattern) is ent:
-                    _drop_entry_locked(pattern)
-            raise
-        with _cache_lock:
-            ent.data_key = data_key
-            cache_stats["values_update"] += 1
-            _trim_locked(keep=(ent,), protect=protect)
-        return _Lease(ent.handle, entry=ent)
-    h = ctx.csr_from_scipy(m)
-    cache_stats["upload"] += 1
-    if busy:
-        return _Lease(h, transient=True)
-    nbytes = h.device_bytes()
-    with _cache_lock:
-        if pattern in _cache:                    # another thread was faster: use ours for this call only
-            return _Lease(h, transient=True)
-        ent = _Entry(h, pattern, data_key)
-        ent.nbytes = nbytes
-        ent.users = 1
-        ent.remember(m.data)
-        _cache[pattern] = ent
-        _trim_locked(keep=(ent,), protect=protect)
-        if pattern not in _cache:                # does not fit the cache at all
-            ent.users = 0
-            return _Lease(h, transient=True)
-    return _Lease(h, entry=ent)
-
-
-def _plan_for(ctx, la, lb, symmetric, exact):
-    """(plan, release) for the product of two leased operands: the cached plan of this pair of patterns when
-    there is one (numeric phase only), else a fresh symbolic phase, cached when both operands are."""
-    key = None
-    if la.entry is not None and lb.entry is not None and _plan_entries > 0:
-        key = (la.entry.pattern, lb.entry.pattern, bool(symmetric), bool(exact))
-        with _cache_lock:
-            pe = _plans.get(key)
-            if pe is not None and pe.a is la.entry and pe.b is lb.entry and pe.plan.handle:
-                pe.users += 1
-                _plans.move_to_end(key)
-                cache_stats["plan_hit"] += 1
-                return pe.plan, lambda: _release_plan(pe)
-    cache_stats["plan_miss"] += 1
-    plan = ctx.spgemm_plan(la.handle, lb.handle, symmetric=symmetric, exact=exact)
-    if key is None:
-        return plan, plan.close
-    nbytes = plan.device_bytes()
-    with _cache_lock:
-        old = _plans.pop(key, None)
-        if old is not None and old.users == 0:
-            old.plan.close()
-        pe = _PlanEntry(plan, la.entry, lb.entry, nbytes)
-        pe.users = 1
-        _plans[key] = pe
-        _trim_locked(keep=(la.entry, lb.entry))
-    return plan, lambda: _release_plan(pe)
-
-
-def _release_plan(pe):
-    with _cache_lock:
-        pe.users -= 1
-        if pe.users == 0 and not any(v is pe for v in _plans.values()):
-            pe.plan.close()                      # evicted while in use
-
-
-def clear_cache():
-    """Forget every cached operand and plan and return their HBM to the device: the handles are destroyed, and the
-    scratch of the closed plans -- which the library keeps pooled for reuse -- is released too (smm_ctx_release_pool).
-    Handles in use by a running call are released when that call ends."""
-    ctxs = {}
-    with _cache_lock:
-        _bury_locked()
-        for pk in list(_plans):
-            pe = _plans.pop(pk)
-            ctxs[id(getattr(pe.plan, "ctx", None))] = getattr(pe.plan, "ctx", None)
-            if pe.users == 0:
-                pe.plan.close()
-        for key in list(_cache):
-            ctxs[id(getattr(_cache[key].handle, "ctx", None))] = getattr(_cache[key].handle, "ctx", None)
-            _drop_entry_locked(key)              # (an entry still leased is closed by that lease's release)
-    for c in ctxs.values():
-        release = getattr(c, "release_pool", None)
-        if release is not None and getattr(c, "handle", None):
-            release()
-
-
-def set_operand_cache(entries):
-    """Number of operands kept resident between calls (0 switches the cache off: every call marshals both
-    operands afresh, as the reference does); returns the old value."""
-    global _cache_entries
-    old, _cache_entries = _cache_entries, int(entries)
-    if _cache_entries <= 0:
-        clear_cache()
-    return old
-
-
-class PinnedOperand:
-    """An operand the caller keeps resident explicitly (no hashing, no look-up): pass it to
-    sparse_matrix_multiply() in place of the matrix.  update_values() replaces the values on the same
-    sparsity pattern; unpin() (or garbage collection) releases the HBM."""
-
-    def __init__(self, ctx, matrix):
-        matrix = _as_csr(matrix)
-        self.shape, self.nnz = tuple(matrix.shape), int(matrix.nnz)
-        self._ctx = ctx
-        self._handle = ctx.csr_from_scipy(matrix) if self.nnz else None
-        self._entry = _Entry(self._handle, ("pinned", id(self)), None)
-
-    @classmethod
-    def _adopt(cls, ctx, handle, shape=None):
-        """The second way of making one: around an operand that is in HBM already (a DeviceCSR the library owns, or one
-        that borrows device tensors and keeps them alive).  No copy, no hash; the handle belongs to the PinnedOperand
-        from here on.  handle None (with shape): an operand without entries, which holds nothing."""
-        self = cls.__new__(cls)
-        if handle is not None and handle.nnz == 0:
-            shape = (handle.rows, handle.cols)
-            handle.close()
-            handle = None
-        self.shape = (handle.rows, handle.cols) if handle is not None else tuple(int(n) for n in shape)
-        self.nnz = handle.nnz if handle is not None else 0
-        self._ctx = ctx
-        self._handle = handle
-        self._entry = _Entry(handle, ("pinned", id(self)), None)
-        return self
-
-    def update_values(self, data):
-        if self._handle is not None:
-            self._handle.update_values(data)
-
-    def to_scipy(self):
-        """The operand's own arrays downloaded as a scipy CSR (int32 indices), whatever it was made from."""
-        if self._handle is None or not self._handle.handle:
-            if self.nnz:
-                raise ValueError("PinnedOperand: unpinned")
-            return csr_matrix(self.shape, dtype=np.float64)
-        return _result_csr(*self._handle.to_host(), self.shape)
-
-    def _lease(self, ctx):
-        if ctx is not self._ctx or self._handle is None or not self._handle.handle:
-            raise ValueError("PinnedOperand: unpinned, or pinned on another context")
-        with _cache_lock:
-            self._entry.users += 1
-        return _Lease(self._handle, entry=self._entry)
-
-    def unpin(self):
-        """Release the operand.  Plans made on it leave the cache (one that a running call is using is closed when that
-        call ends); the handle is closed now, or -- while a call still multiplies with it -- by that call's release."""
-        close = None
-        with _cache_lock:
-            for pk in [pk for pk, pe in _plans.items() if pe.a is self._entry or pe.b is self._entry]:
-                pe = _plans.pop(pk)
-                if pe.users == 0:
-                    pe.plan.close()
-            if self._entry.users > 0:
-                self._entry.dead = True
-            else:
-                close = self._handle
-            self._handle = None
-        if close is not None:
-            close.close()
-
-    def __del__(self):
-        # (may run inside any allocation, also while _trim_locked walks _plans: only leave a note; the next
-        # _trim_locked / clear_cache closes the plans and the handle)
-        if getattr(self, "_handle", None) is not None:
-            _graveyard.append(self._entry)
-
-
 def pin_operand(matrix):
     """Upload `matrix` once and keep it (and everything derived from it) in HBM until unpin().  A DeviceCSRResult -- a
     result left in HBM under set_result_device(True) -- is pinned where it is: its row pointer is narrowed to int32 on the
     device and the three tensors are borrowed (and kept alive) by the operand; nothing is copied to the host or hashed."""
     if isinstance(matrix, DeviceCSRResult):
         return _pin_device_result(matrix)
-    if isinstance(matrix, KroneckerOperand):
-        _as_csr(matrix)                                   # (refused, with the pointer to kronecker_product)
+    matrix = _as_csr(matrix)                              # (a KroneckerOperand is refused, with the pointer to kronecker_product)
     return PinnedOperand(default_context(), matrix)
 
 
@@ -774,7 +405,7 @@ def kronecker_product(D, E, pin=False):
 
         return _on_device(ctx, call)
 
-    return _with_leases(ctx, (D, E), body)
+    return with_leases(ctx, (D, E), body)
 
 
 def _device_zeros(ctx, shape, sparse):
@@ -823,7 +454,7 @@ def _product_on_device(ctx, la, lb, triple, output_format, symmetric, compute_fu
             return out
         if symmetric and _full_symmetric:
             return DeviceCSRResult(*ctx.spgemm_mirrored_torch(a, b, exact=_exact), (a.rows, b.cols))
-        plan, release = _plan_for(ctx, la, lb, symmetric, _exact)
+        plan, release = plan_for(ctx, la, lb, symmetric, _exact)
         try:
             indptr = torch.empty(a.rows + 1, dtype=torch.int64, device=dev)
             indices = torch.empty(plan.nnz, dtype=torch.int32, device=dev)
@@ -923,7 +554,7 @@ def sparse_matrix_multiply(matrix_a, matrix_b, output_format='sparse', symmetric
             # order, then the reference's upper-triangle row in its first-touch order)
             return _result_csr(*ctx.spgemm_host_mirrored(a, b, exact=_exact), out_shape)
         if output_format == 'sparse':                            # reference :338-351
-            plan, release = _plan_for(ctx, la, lb, bool(symmetric), _exact)
+            plan, release = plan_for(ctx, la, lb, bool(symmetric), _exact)
             try:
                 indptr, indices, data = plan.numeric_host()
             finally:
@@ -932,7 +563,7 @@ def sparse_matrix_multiply(matrix_a, matrix_b, output_format='sparse', symmetric
         return ctx.dense_host(a, b, symmetric=bool(symmetric), exact=_exact,  # reference :353-365
                               mirror=bool(symmetric) and _full_symmetric)
 
-    result = _with_leases(ctx, (matrix_a, matrix_b), product)
+    result = with_leases(ctx, (matrix_a, matrix_b), product)
 
     if _result_device and not isinstance(result, (np.ndarray, csr_matrix)):
         empty = result.nnz == 0 if isinstance(result, DeviceCSRResult) else not bool(result.any())
@@ -1000,7 +631,7 @@ def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False, mask=No
             return _on_device(ctx, lambda: DeviceCSRResult(*ctx.triple_sparse_torch(h, q, full=full, exact=_exact, mask=m), out_shape))
         return _result_csr(*ctx.triple_sparse_host(h, q, full=full, exact=_exact, mask=m), out_shape)
 
-    return _with_leases(ctx, mats, body)
+    return with_leases(ctx, mats, body)
 
 
 # ------------------------------------------------------------------ products on a given pattern
@@ -1046,31 +677,6 @@ def _pattern_result(ctx, indptr, indices, data, shape):
     return _result_csr(indptr, indices, data, shape)
 
 
-def _with_leases(ctx, mats, body):
-    """body(*leases) with every operand of `mats` leased (the operand cache applies to each), retried once after
-    clear_cache() when the device ran out of memory while resident operands / plans were in the way."""
-    def product():
-        cached = _cache_entries > 0
-        keys = [_operand_key(m) if cached and not isinstance(m, PinnedOperand) else None for m in mats]
-        leases = []
-        try:
-            for i, m in enumerate(mats):
-                protect = tuple(k[0] for k in keys[i + 1:] if k is not None)
-                leases.append(_acquire(ctx, m, keys[i], protect=protect))
-            return body(*leases)
-        finally:
-            for lease in reversed(leases):
-                lease.release()
-
-    try:
-        return product()
-    except SmmError as e:
-        if e.code != SMM_ERR_ALLOC or not (_cache or _plans):
-            raise
-        clear_cache()
-        return product()
-
-
 def masked_matrix_multiply(matrix_a, matrix_b, mask):
     """C = (A @ B) evaluated only at the positions of `mask` (GraphBLAS masked mxm / SDDMM with sparse operands).
 
@@ -1112,7 +718,7 @@ def masked_matrix_multiply(matrix_a, matrix_b, mask):
             return _pattern_result(ctx, indptr, indices, _on_device(ctx, call), out_shape)
         return _result_csr(indptr, indices, ctx.spgemm_masked_host(la.handle, lb.handle, lm.handle, exact=_exact), out_shape)
 
-    return _with_leases(ctx, (matrix_a, matrix_b, mask), body)
+    return with_leases(ctx, (matrix_a, matrix_b, mask), body)
 
 
 # ------------------------------------------------------------------ sparse x dense
@@ -1199,8 +805,8 @@ def sparse_dense_multiply(matrix_a, x, transpose=False):
                             lambda dx, ldx, dy, ldy: ctx.kron_apply_into(d, e, dx, ldx, k, dy, ldy, exact=_exact))
 
     if kron:
-        return _with_leases(ctx, matrix_a.factors, body_kron)
-    return _with_leases(ctx, (matrix_a,), body)
+        return with_leases(ctx, matrix_a.factors, body_kron)
+    return with_leases(ctx, (matrix_a,), body)
 
 
 def triple_product_apply(matrix_h, matrix_q, x):
@@ -1240,7 +846,7 @@ def triple_product_apply(matrix_h, matrix_q, x):
                             lambda xh: ctx.triple_apply_host(h, q[0], xh, exact=_exact),
                             lambda dx, ldx, dy, ldy: ctx.triple_apply_into(h, q[0], dx, ldx, k, dy, ldy, exact=_exact))
 
-    return _with_leases(ctx, (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)), body)
+    return with_leases(ctx, (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)), body)
 
 
 # ------------------------------------------------------------------ (X Y^T) on a pattern
@@ -1330,7 +936,7 @@ def sampled_dense_product(x, y, mask, scale_by_mask=False):
             return _pattern_result(ctx, indptr, indices, data, out_shape)
         return _result_csr(indptr, indices, data.cpu().numpy(), out_shape)
 
-    return _with_leases(ctx, (mask,), body)
+    return with_leases(ctx, (mask,), body)
 
 
 # ------------------------------------------------------------------ CG on (H Q H^T + R) Z = D
@@ -1436,7 +1042,7 @@ def _host_r_apply(matrix_r):
         return np.zeros_like
     if isinstance(matrix_r, PinnedOperand):
         ctx = default_context()
-        return lambda p: 0.0 + _with_leases(ctx, (matrix_r,), lambda lr: ctx.spmm_host(lr.handle, p, exact=True))
+        return lambda p: 0.0 + with_leases(ctx, (matrix_r,), lambda lr: ctx.spmm_host(lr.handle, p, exact=True))
     return lambda p: 0.0 + np.asarray(matrix_r @ p)
 
 
@@ -1506,7 +1112,7 @@ def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
         return z, info
 
     mats = (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)) + ((matrix_r,) if matrix_r is not None else ())
-    return _with_leases(ctx, mats, body)
+    return with_leases(ctx, mats, body)
 
 
 # ------------------------------------------------------------------ log det(H Q H^T + R) by stochastic Lanczos quadrature
@@ -1713,7 +1319,7 @@ def innovation_logdet(matrix_h, matrix_q, matrix_r, probes=32, seed=0, tol=1e-8,
         return z, info
 
     mats = (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)) + ((matrix_r,) if matrix_r is not None else ())
-    z, info = _with_leases(ctx, mats, body)
+    z, info = with_leases(ctx, mats, body)
     finish(z, info)
     if res.Z is not None:
         res.Z = to_kind(res.Z, on_device)

@@ -17,8 +17,8 @@ SYMBOLIC_KERNELS = ("smm_symbolic", "smm_symbolic_hash", "smm_runs", "smm_segptr
 def pkg():
     import sparse_matrix_mult_amd as p
     p.clear_cache()
-    from sparse_matrix_mult_amd import matrix_ops
-    assert matrix_ops._cache_entries == 4, "these tests run under the default cache setting"
+    from sparse_matrix_mult_amd.operand_cache import default_cache
+    assert default_cache.entries == 4, "these tests run under the default cache setting"
     old = p.set_exact(True)                      # reference-order sums: every comparison below is bit for bit
     yield p
     p.set_exact(old)
@@ -334,11 +334,37 @@ def test_pinned_operands(pkg, oracle):
     pa.unpin()
 
 
+def test_collected_pinned_operands_are_freed_by_the_next_call_into_the_package(pkg, oracle):
+    """Garbage collection of a PinnedOperand only leaves a note; the next call into the package -- here a pin_operand,
+    which never reaches the trim -- closes the handles and the plan made on them."""
+    import gc
+    from sparse_matrix_mult_amd.operand_cache import default_cache as cache
+    smm = pkg.sparse_matrix_multiply
+    A, B = rand_csr(300, 500, 0.05, 51), rand_csr(500, 500, 0.05, 52)
+    pa, pb = pkg.pin_operand(A), pkg.pin_operand(B)
+    _check(smm(pa, pb), A, B, oracle)
+    ha, hb = pa._handle, pb._handle
+
+    def plans_on_them():
+        return [pe for pe in cache.plans.values() if pe.a.handle in (ha, hb) or pe.b.handle in (ha, hb)]
+
+    assert len(plans_on_them()) == 1
+    del pa, pb
+    gc.collect()
+    assert ha.handle and hb.handle                     # __del__ itself closed nothing
+    small = pkg.pin_operand(rand_csr(4, 4, 0.5, 54))
+    assert small.nnz > 0
+    assert not ha.handle and not hb.handle
+    assert not plans_on_them() and not cache.graveyard
+    _check(smm(A, B), A, B, oracle)                    # the context is healthy
+    small.unpin()
+
+
 def test_cache_limits_and_orphans(pkg, oracle):
     """Entries whose arrays were garbage-collected go first; the entry limit holds; real HBM (derived copies
     included) is what the byte cap counts."""
     import gc
-    from sparse_matrix_mult_amd import matrix_ops
+    from sparse_matrix_mult_amd.operand_cache import default_cache as cache
     smm = pkg.sparse_matrix_multiply
     B = rand_csr(400, 400, 0.05, 61)
     for i in range(6):
@@ -346,20 +372,20 @@ def test_cache_limits_and_orphans(pkg, oracle):
         _check(smm(A, B), A, B, oracle)
         del A
         gc.collect()
-    assert len(matrix_ops._cache) <= 2                 # B and at most the last A (orphans are purged at the next call)
-    ent = max(matrix_ops._cache.values(), key=lambda e: e.handle.nnz)      # B: tile index, packed payload, 16-bit columns
+    assert len(cache.operands) <= 2                 # B and at most the last A (orphans are purged at the next call)
+    ent = max(cache.operands.values(), key=lambda e: e.handle.nnz)      # B: tile index, packed payload, 16-bit columns
     assert ent.handle.device_bytes() >= 14 * ent.handle.nnz     # the three CSR arrays (12 B per entry) AND the cached copies
     mats = [rand_csr(100, 400, 0.05, 80 + i) for i in range(6)]
     for A in mats:
         smm(A, B)
-    assert len(matrix_ops._cache) <= 4 and len(matrix_ops._plans) <= 2
-    old = matrix_ops._cache_max_bytes
-    matrix_ops._cache_max_bytes = 1                    # nothing fits: every call marshals afresh, results stay right
+    assert len(cache.operands) <= 4 and len(cache.plans) <= 2
+    old = cache.max_bytes
+    cache.max_bytes = 1                    # nothing fits: every call marshals afresh, results stay right
     try:
         _check(smm(mats[0], B), mats[0], B, oracle)
-        assert len(matrix_ops._cache) == 0 and len(matrix_ops._plans) == 0
+        assert len(cache.operands) == 0 and len(cache.plans) == 0
     finally:
-        matrix_ops._cache_max_bytes = old
+        cache.max_bytes = old
 
 
 def test_exact_guard(ctx):
