@@ -573,6 +573,31 @@ int  smm_innovation_solve_kron_host(smm_ctx *ctx, smm_csr *h, smm_csr *d, smm_cs
                                     int64_t ldb, double *x, int64_t ldx, double tol, int64_t maxiter, int *iterations, int *status,
                                     double *residual_sq, double *rhs_sq);
 
+/* ------------------------------------------------------------------ masked products with Q = D (x) E, Q never formed
+ * Entries of H (D (x) E) H^T and of A (D (x) E) at the positions of a mask, for a Q that cannot be held (a dense D of 40
+ * periods over 25 000 grid points is 2.7e9 entries).  Each entry is its CSR counterpart -- smm_triple_product_sparse_masked,
+ * smm_spgemm_masked[_host] -- called with Q = smm_kron_build(d, e): same arguments, flags, result object (smm_result, columns
+ * k >= i, SMM_FULL_MATRIX mirrors the upper part, row ranges), +0.0 where nothing reaches, never a product of a pair the
+ * operands do not store, within 1e-10 of (|H| |Q| |H|^T)[i,k] resp. (|A| |Q|)[i,c] in default mode.  No Q, no T = H Q and no
+ * transpose is allocated: the temporaries are 24 bytes per stored entry of H (A) and the row lists.
+ *   Factors: canonical (rows strictly ascending -- their entries are found by bisection; smm_csr_is_canonical), square for the
+ *   triple product, p r == H.cols (A.cols), p r and p' r' < 2^31 - 1; else SMM_ERR_INVALID before anything is allocated.  The
+ *   mask is canonical, n x n resp. A.rows x p' r'.  H and A may be any legal CSR (unsorted rows, repeated columns).  H, A or a
+ *   factor without entries: the pattern filled with +0.0, no value kernel.
+ *   SMM_EXACT: bit-identical to the counterpart on the explicit operand.  Written out:
+ *     (A Q)[i, c], c = t' r' + j':  over row i of A in stored order a, with (t, j) = divmod(A.idx[a], r), the term
+ *       A.val[a] * q, q = D[t,t'] * E[j,j'] rounded once (the value smm_kron_build stores), taken only when both factors
+ *       store their entry; the first term lands unchanged, later ones are added one rounded product at a time.
+ *     S[i, k]:  T[i, c] as above with A = H, "stored" iff some a reaches it (even if it cancels); then sum = 0.0;
+ *       sum += T[i, H.idx[a2]] * H.val[a2] over row k of H in stored order, an unstored T read as +0.0 and still multiplied.
+ *   Without SMM_EXACT: the same association with fused multiply-adds (q still rounded once).  No float atomics in either
+ *   mode: two runs agree bit for bit, and the value at a position depends on the two rows of H (the row of A) and the
+ *   factors only -- not on the mask, the row range or the launch shape. */
+int  smm_triple_product_sparse_masked_kron(smm_ctx *ctx, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *mask, int flags,
+                                           int64_t row_begin, int64_t row_end, smm_result **out);
+int  smm_spgemm_masked_kron(smm_ctx *ctx, smm_csr *a, smm_csr *d, smm_csr *e, smm_csr *mask, int flags, double *d_c_data);
+int  smm_spgemm_masked_kron_host(smm_ctx *ctx, smm_csr *a, smm_csr *d, smm_csr *e, smm_csr *mask, int flags, double *c_data);
+
 /* ------------------------------------------------------------------ log det(H Q H^T + R): probes and recorded CG coefficients
  * Stochastic Lanczos quadrature reads ln det Psi, Psi = H Q H^T + R, off the batched CG above: probes z_c with entries +-1,
  * CG on Psi x = z_c, the CG coefficients turned into the Lanczos tridiagonal T_c (m x m for a column with m iterations),

@@ -134,6 +134,9 @@ V2_PROTOTYPES = {
     "smm_triple_apply_kron_host": (ctypes.c_int, [_vp] * 4 + _BLOCKS),
     "smm_innovation_solve_kron": (ctypes.c_int, [_vp] * 5 + _SOLVE),
     "smm_innovation_solve_kron_host": (ctypes.c_int, [_vp] * 5 + _SOLVE),
+    "smm_triple_product_sparse_masked_kron": (ctypes.c_int, [_vp] * 5 + [ctypes.c_int, _c_i64, _c_i64, _pp]),
+    "smm_spgemm_masked_kron": (ctypes.c_int, [_vp] * 5 + [ctypes.c_int, _vp]),
+    "smm_spgemm_masked_kron_host": (ctypes.c_int, [_vp] * 5 + [ctypes.c_int, _vp]),
     "smm_probe_fill": (ctypes.c_int, [_vp, _c_i64, _c_i64, ctypes.c_uint64, _vp, _c_i64]),
     "smm_innovation_solve_coef": (ctypes.c_int, [_vp] * 4 + _SOLVE + [_vp, _vp]),
     "smm_innovation_solve_coef_kron": (ctypes.c_int, [_vp] * 5 + _SOLVE + [_vp, _vp]),

@@ -9,6 +9,7 @@
 #include "smm_masked.hpp"
 #include "smm_spmm.hpp"
 #include "smm_kron.hpp"
+#include "smm_kron_masked.hpp"
 #include "smm_cg.hpp"
 #include "smm_slq.hpp"
 #include "smm_sddmm.hpp"
@@ -3347,6 +3348,31 @@ static int triple_sparse_block(smm_ctx *c, smm_csr *h, smm_csr *q, smm_csr *ht, 
     return SMM_OK;
 }
 
+// SMM_FULL_MATRIX: the pieces of r (rows [0,n), k >= i) joined into one CSR and mirrored on the device; r then holds the one
+// full piece (rows stay ascending: mirrored part first, then k >= i).
+static int result_mirror(smm_ctx *c, smm_result *r, int64_t n)
+{
+    PoolBuf<int64_t> up_ptr(c), fp_ptr(c);
+    PoolBuf<int> up_idx(c), fp_idx(c);
+    PoolBuf<double> up_val(c), fp_val(c);
+    int64_t fnnz = 0;
+    CHK(up_ptr.alloc((size_t)n + 1));
+    CHK(up_idx.alloc((size_t)std::max<int64_t>(r->nnz, 1)));
+    CHK(up_val.alloc((size_t)std::max<int64_t>(r->nnz, 1)));
+    CHK(result_join(c, r, up_ptr, up_idx, up_val));
+    CHK(fp_ptr.alloc((size_t)n + 1));
+    CHK(smm_csr_mirror_symbolic(c, n, up_ptr, up_idx, fp_ptr, &fnnz));
+    CHK(fp_idx.alloc((size_t)std::max<int64_t>(fnnz, 1)));
+    CHK(fp_val.alloc((size_t)std::max<int64_t>(fnnz, 1)));
+    CHK(smm_csr_mirror_fill(c, n, up_ptr, up_idx, up_val, fp_ptr, fp_idx, fp_val));
+    (void)hipStreamSynchronize(c->stream);
+    for (auto &p : r->pieces) { pool_free(c, p.ptr); pool_free(c, p.idx); pool_free(c, p.val); }
+    up_ptr.reset(); up_idx.reset(); up_val.reset();
+    r->pieces.assign(1, smm_result::Piece{n, fnnz, fp_ptr.release(), fp_idx.release(), fp_val.release()});
+    r->nnz = fnnz;
+    return SMM_OK;
+}
+
 // mask == nullptr: smm_triple_product_sparse; else smm_triple_product_sparse_masked (mask validated, canonical, n x n)
 static int triple_sparse_impl(smm_ctx *c, smm_csr *h, smm_csr *q, const smm_csr *mask, int flags, int64_t row_begin, int64_t row_end,
                               smm_result **out)
@@ -3379,27 +3405,7 @@ static int triple_sparse_impl(smm_ctx *c, smm_csr *h, smm_csr *q, const smm_csr 
         b0 = b1;
     }
     CHK(take_plan_error(c, "smm_triple_product_sparse"));
-    if (full) {
-        // the upper triangle joined into one CSR, mirrored on the device (rows stay ascending: mirrored part first, then k >= i)
-        PoolBuf<int64_t> up_ptr(c), fp_ptr(c);
-        PoolBuf<int> up_idx(c), fp_idx(c);
-        PoolBuf<double> up_val(c), fp_val(c);
-        int64_t fnnz = 0;
-        CHK(up_ptr.alloc((size_t)n + 1));
-        CHK(up_idx.alloc((size_t)std::max<int64_t>(r->nnz, 1)));
-        CHK(up_val.alloc((size_t)std::max<int64_t>(r->nnz, 1)));
-        CHK(result_join(c, r.get(), up_ptr, up_idx, up_val));
-        CHK(fp_ptr.alloc((size_t)n + 1));
-        CHK(smm_csr_mirror_symbolic(c, n, up_ptr, up_idx, fp_ptr, &fnnz));
-        CHK(fp_idx.alloc((size_t)std::max<int64_t>(fnnz, 1)));
-        CHK(fp_val.alloc((size_t)std::max<int64_t>(fnnz, 1)));
-        CHK(smm_csr_mirror_fill(c, n, up_ptr, up_idx, up_val, fp_ptr, fp_idx, fp_val));
-        (void)hipStreamSynchronize(c->stream);
-        for (auto &p : r->pieces) { pool_free(c, p.ptr); pool_free(c, p.idx); pool_free(c, p.val); }
-        up_ptr.reset(); up_idx.reset(); up_val.reset();
-        r->pieces.assign(1, smm_result::Piece{n, fnnz, fp_ptr.release(), fp_idx.release(), fp_val.release()});
-        r->nnz = fnnz;
-    }
+    if (full) CHK(result_mirror(c, r.get(), n));
     *out = r.release();
     return SMM_OK;
 }
@@ -3905,6 +3911,202 @@ extern "C" int smm_kron_apply_host(smm_ctx *c, smm_csr *d, smm_csr *e, int flags
     if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
     CTX_LOCK(c);
     return kron_apply_entry(c, d, e, flags, k, x, ldx, y, ldy, ON_HOST, "smm_kron_apply_host");
+}
+
+// ------------------------------------------------------------------------------ masked products with Q = D (x) E
+// Kernels: smm_kron_masked.hpp; the contract is in include/smm_hip.h.  Q, T = H Q and their transposes are never formed.
+// What both entries ask of H (or A), the factors and the mask.  Everything that needs no launch comes first -- contexts, the
+// factors' shapes, the mask's shape (mask_cols: n for the triple product, p' r' for A Q) --, then the operands are validated
+// and the factors must be canonical.  check_mask, after this, validates the mask.
+static int kron_masked_operands(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *mask, bool square, const char *where)
+{
+    if (!h) return fail(SMM_ERR_INVALID, "%s: NULL operand", where);
+    if (h->ctx != c) return fail(SMM_ERR_INVALID, "%s: operand belongs to another context", where);
+    CHK(kron_factors(c, d, e, where));
+    if (square && (d->rows != d->cols || e->rows != e->cols))
+        return fail(SMM_ERR_INVALID, "%s: the factors must be square (D is %lld x %lld, E is %lld x %lld)", where, (long long)d->rows,
+                    (long long)d->cols, (long long)e->rows, (long long)e->cols);
+    if (d->rows * e->rows != h->cols)
+        return fail(SMM_ERR_INVALID, "%s: D (x) E has %lld rows, the left operand %lld columns", where, (long long)(d->rows * e->rows),
+                    (long long)h->cols);
+    const int64_t mask_cols = square ? h->rows : d->cols * e->cols;
+    if (!mask) return fail(SMM_ERR_INVALID, "%s: mask is NULL", where);
+    if (mask->ctx != c) return fail(SMM_ERR_INVALID, "%s: mask belongs to another context", where);
+    if (mask->rows != h->rows || mask->cols != mask_cols)
+        return fail(SMM_ERR_INVALID, "%s: mask is %lld x %lld, expected %lld x %lld", where, (long long)mask->rows, (long long)mask->cols,
+                    (long long)h->rows, (long long)mask_cols);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(validate(c, h));
+    CHK(validate(c, d));
+    CHK(validate(c, e));
+    if ((d->vflags | e->vflags) & (CSR_UNSORTED | CSR_HAS_EQUAL))
+        return fail(SMM_ERR_INVALID, "%s: a factor is not canonical (its rows must hold strictly ascending columns: the entries of D and E "
+                                     "are searched in sorted rows; sum_duplicates() of a host copy makes one)", where);
+    return SMM_OK;
+}
+
+template <typename PT>
+static KronMaskedArgs<PT> kron_masked_args(smm_ctx *c, const smm_csr *h, const smm_csr *d, const smm_csr *e)
+{
+    KronMaskedArgs<PT> A{};
+    A.h_ptr = h->ptr; A.h_idx = h->idx; A.h_val = h->val; A.n = (int)h->rows; A.K = (int)h->cols; A.nnz_h = (int)h->nnz;
+    A.p = (int)d->rows; A.pc = (int)d->cols; A.r = (int)e->rows; A.rc = (int)e->cols;
+    A.nnz_d = (int)d->nnz; A.nnz_e = (int)e->nnz;
+    A.dptr = d->ptr; A.didx = d->idx; A.dval = d->val;
+    A.eptr = e->ptr; A.eidx = e->idx; A.eval = e->val;
+    A.err = c->d_err;
+    return A;
+}
+
+// The values of a pattern (A.nb rows, A.s_ptr / s_idx / s_val set, at least one position, H and the factors with entries):
+// the per-entry table of H, the rows binned by their lanes per position, one launch per class.
+template <bool TRIPLE, typename PT>
+static int kron_masked_values(smm_ctx *c, KronMaskedArgs<PT> A, bool exact, PoolBuf<int> &scratch, int64_t nnz_h)
+{
+    const int64_t nb = A.nb;
+    PoolBuf<int> cls(c);
+    ClassLists bins(c);
+    CHK(scratch.alloc((size_t)6 * (size_t)nnz_h));
+    A.h_rng = reinterpret_cast<int4 *>((int *)scratch);               // (pool blocks are 256-byte aligned)
+    A.h_tj = reinterpret_cast<int2 *>((int *)scratch + 4 * (size_t)nnz_h);
+    CHK(cls.alloc((size_t)nb));
+    const int64_t cap = (int64_t)c->n_cu * 16;
+    const bool dlds = (int64_t)A.p * A.pc <= KM_DLDS;      // D as a table in LDS when p p' fits, else bisected from L2
+    LAUNCH(c, "smm_kron_masked_prep", smm_kron_masked_prep<PT>, std::max<int64_t>(1, std::min<int64_t>(((int64_t)A.n + 3) / 4, cap)), 256, 0, A);
+    LAUNCH_CHECK();
+    CHK(bin_rows(c, nb, MK_NCLS, bins, [&](int *lists, int *cnt) {
+        LAUNCH(c, "smm_kron_masked_class", (smm_kron_masked_class<TRIPLE, PT>), std::min<int64_t>((nb + 3) / 4, 16384), 256, 0, A, (int *)cls);
+        LAUNCH(c, "smm_masked_bin", smm_masked_bin, std::min<int64_t>((nb + 255) / 256, 4096), 256, 0, (int)nb, (const int *)cls, lists, cnt);
+    }));
+    for (int cl = 0; cl < 5; ++cl) {                   // G = 4 << cl lanes per position, one wave per pattern row
+        if (bins.count[cl] <= 0) continue;
+        A.rowlist = bins.list(cl); A.nrows = bins.count[cl];
+        const int64_t grid = std::min<int64_t>(((int64_t)A.nrows + 3) / 4, cap);
+        if constexpr (TRIPLE) {
+            if (dlds) { if (exact) LAUNCH(c, "smm_kron_masked_triple", (smm_kron_masked_triple<true, true>), grid, 256, 0, A, 4 << cl);
+                        else       LAUNCH(c, "smm_kron_masked_triple", (smm_kron_masked_triple<false, true>), grid, 256, 0, A, 4 << cl); }
+            else      { if (exact) LAUNCH(c, "smm_kron_masked_triple", (smm_kron_masked_triple<true, false>), grid, 256, 0, A, 4 << cl);
+                        else       LAUNCH(c, "smm_kron_masked_triple", (smm_kron_masked_triple<false, false>), grid, 256, 0, A, 4 << cl); }
+        } else {
+            if (dlds) { if (exact) LAUNCH(c, "smm_kron_masked_spgemm", (smm_kron_masked_spgemm<true, true>), grid, 256, 0, A, 4 << cl);
+                        else       LAUNCH(c, "smm_kron_masked_spgemm", (smm_kron_masked_spgemm<false, true>), grid, 256, 0, A, 4 << cl); }
+            else      { if (exact) LAUNCH(c, "smm_kron_masked_spgemm", (smm_kron_masked_spgemm<true, false>), grid, 256, 0, A, 4 << cl);
+                        else       LAUNCH(c, "smm_kron_masked_spgemm", (smm_kron_masked_spgemm<false, false>), grid, 256, 0, A, 4 << cl); }
+        }
+        LAUNCH_CHECK();
+    }
+    (void)hipStreamSynchronize(c->stream);              // the temporaries go back to the pool
+    return SMM_OK;
+}
+
+extern "C" int smm_triple_product_sparse_masked_kron(smm_ctx *c, smm_csr *h, smm_csr *d, smm_csr *e, smm_csr *mask, int flags,
+                                                     int64_t row_begin, int64_t row_end, smm_result **out)
+{
+    static const char *where = "smm_triple_product_sparse_masked_kron";
+    if (!out) return fail(SMM_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(kron_masked_operands(c, h, d, e, mask, /*square=*/true, where));
+    CHK(check_mask(c, mask, h->rows, h->rows, where));
+    const int64_t n = h->rows;
+    if (row_begin < 0 || row_end > n || row_begin > row_end) return fail(SMM_ERR_INVALID, "bad row range");
+    if (flags & SMM_MIRROR) return fail(SMM_ERR_INVALID, "%s: SMM_MIRROR is not a flag of this call (SMM_FULL_MATRIX mirrors)", where);
+    const bool full = (flags & SMM_FULL_MATRIX) != 0;
+    if (full && (row_begin != 0 || row_end != n)) return fail(SMM_ERR_INVALID, "SMM_FULL_MATRIX needs the whole row range [0,n)");
+    CHK(exact_guard(c, flags));
+    const int64_t nb = row_end - row_begin;
+    std::unique_ptr<smm_result, Destroyer<smm_result_destroy>> r(new smm_result());
+    r->ctx = c; r->rows = nb; r->cols = n;
+    if (nb == 0 || mask->nnz == 0) { *out = r.release(); return SMM_OK; }
+    // the pattern: the mask's rows [row_begin, row_end) filtered to k >= i (count, scan, copy), as the CSR form's stage 2
+    int64_t snnz = 0;
+    PoolBuf<int64_t> sptr(c);
+    PoolBuf<int> mcnt(c), sidx(c), scratch(c);
+    PoolBuf<double> sval(c);
+    CHK(mcnt.alloc((size_t)2 * nb + 2));
+    CHK(sptr.alloc((size_t)nb + 1));
+    LAUNCH(c, "smm_masked_tri_count", smm_masked_tri_count, (int)std::min<int64_t>((nb + 255) / 256, 4096), 256, 0, (int)nb, row_begin,
+           mask->ptr, mask->idx, mcnt, mcnt + nb + 1);
+    CHK(scan_launch<int>(c, nb, mcnt, sptr));
+    HIPCHK(hipMemcpyAsync(&snnz, sptr + nb, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    CHK(sidx.alloc((size_t)std::max<int64_t>(snnz, 1)));
+    CHK(sval.alloc((size_t)std::max<int64_t>(snnz, 1)));
+    if (snnz > 0) {
+        LAUNCH(c, "smm_masked_tri_copy", smm_masked_tri_copy, std::min<int64_t>((nb + 3) / 4, 16384), 256, 0, (int)nb,
+               (const int *)(mcnt + nb + 1), (const int *)mcnt, (const int64_t *)sptr, mask->idx, sidx);
+        LAUNCH_CHECK();
+        if (h->nnz == 0 || d->nnz == 0 || e->nnz == 0) {       // nothing reaches any position: +0.0
+            HIPCHK(hipMemsetAsync(sval, 0, (size_t)snnz * sizeof(double), c->stream));
+        } else {
+            KronMaskedArgs<int64_t> A = kron_masked_args<int64_t>(c, h, d, e);
+            A.nb = (int)nb; A.row0 = row_begin;
+            A.s_ptr = sptr; A.s_idx = sidx; A.s_val = sval; A.cols = (int)n;
+            CHK((kron_masked_values<true, int64_t>(c, A, (flags & SMM_EXACT) != 0, scratch, h->nnz)));
+        }
+    }
+    (void)hipStreamSynchronize(c->stream);
+    mcnt.reset(); scratch.reset();
+    r->pieces.push_back(smm_result::Piece{nb, snnz, sptr.release(), sidx.release(), sval.release()});
+    r->nnz = snnz;
+    CHK(take_plan_error(c, where));
+    if (full) CHK(result_mirror(c, r.get(), n));
+    *out = r.release();
+    return SMM_OK;
+}
+
+// nnz(mask) values of A * (D (x) E) on the mask's pattern into d_out (checked operands, canonical mask of A.rows x p' r').
+static int masked_kron_impl(smm_ctx *c, smm_csr *a, smm_csr *d, smm_csr *e, smm_csr *mask, int flags, double *d_out)
+{
+    const int64_t nm = mask->nnz;
+    if (nm == 0) return SMM_OK;
+    if (a->nnz == 0 || d->nnz == 0 || e->nnz == 0) {     // the mask's pattern filled with +0.0
+        HIPCHK(hipMemsetAsync(d_out, 0, (size_t)nm * sizeof(double), c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return SMM_OK;
+    }
+    PoolBuf<int> scratch(c);
+    KronMaskedArgs<int> A = kron_masked_args<int>(c, a, d, e);
+    A.nb = (int)a->rows; A.row0 = 0;
+    A.s_ptr = mask->ptr; A.s_idx = mask->idx; A.s_val = d_out; A.cols = (int)mask->cols;
+    CHK((kron_masked_values<false, int>(c, A, (flags & SMM_EXACT) != 0, scratch, a->nnz)));
+    scratch.reset();
+    return take_plan_error(c, "smm_spgemm_masked_kron");
+}
+
+static int masked_kron_args(smm_ctx *c, smm_csr *a, smm_csr *d, smm_csr *e, smm_csr *mask, int flags)
+{
+    static const char *where = "smm_spgemm_masked_kron";
+    if (flags & ~SMM_EXACT) return fail(SMM_ERR_INVALID, "%s: only SMM_EXACT is a flag of this call", where);
+    CHK(kron_masked_operands(c, a, d, e, mask, /*square=*/false, where));
+    CHK(check_mask(c, mask, a->rows, d->cols * e->cols, where));
+    CHK(exact_guard(c, flags));
+    return SMM_OK;
+}
+
+extern "C" int smm_spgemm_masked_kron(smm_ctx *c, smm_csr *a, smm_csr *d, smm_csr *e, smm_csr *mask, int flags, double *d_c_data)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(masked_kron_args(c, a, d, e, mask, flags));
+    if (mask->nnz > 0 && !d_c_data) return fail(SMM_ERR_INVALID, "d_c_data is NULL but nnz(mask) > 0");
+    return masked_kron_impl(c, a, d, e, mask, flags, d_c_data);
+}
+
+extern "C" int smm_spgemm_masked_kron_host(smm_ctx *c, smm_csr *a, smm_csr *d, smm_csr *e, smm_csr *mask, int flags, double *c_data)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CHK(masked_kron_args(c, a, d, e, mask, flags));
+    if (mask->nnz == 0) return SMM_OK;
+    if (!c_data) return fail(SMM_ERR_INVALID, "c_data is NULL but nnz(mask) > 0");
+    PoolBuf<double> dv(c);
+    CHK(dv.alloc((size_t)mask->nnz));
+    CHK(masked_kron_impl(c, a, d, e, mask, flags, dv));
+    CHK(download(c, c_data, dv, (size_t)mask->nnz * sizeof(double)));
+    (void)hipStreamSynchronize(c->stream);
+    return SMM_OK;
 }
 
 // The K x K operator in the middle of H Q H^T as the host code sees it: one CSR, or a pair of factors D (x) E (square, with

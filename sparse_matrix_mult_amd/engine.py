@@ -355,7 +355,13 @@ class Context:
     def _triple_sparse(self, h, q, full, row_begin, row_end, exact, mask=None):
         row_end = h.rows if row_end is None else row_end
         r = ctypes.c_void_p()
-        if mask is None:
+        if isinstance(q, tuple):            # (D, E): Q = D (x) E through its factors, on a mask only
+            if mask is None:
+                raise ValueError("the sparse triple product with a factor-form Q needs a mask (its pattern would need Q itself)")
+            check(self.lib, self.lib.smm_triple_product_sparse_masked_kron(self.handle, h.handle, q[0].handle, q[1].handle,
+                                                                           mask.handle, _flags(False, exact, full), int(row_begin),
+                                                                           int(row_end), ctypes.byref(r)))
+        elif mask is None:
             check(self.lib, self.lib.smm_triple_product_sparse(self.handle, h.handle, q.handle, _flags(False, exact, full),
                                                                int(row_begin), int(row_end), ctypes.byref(r)))
         else:
@@ -368,7 +374,8 @@ class Context:
         """Rows [row_begin, row_end) of S = H Q H^T as CSR (smm_triple_product_sparse): columns k >= i in ascending
         order (full=True: the whole symmetric matrix).  (indptr int64, indices int32 -- int64 when nnz >= 2^31 or
         index_dtype says so --, data float64) numpy arrays.  mask (a canonical n x n DeviceCSR): S on the positions of
-        the mask with k >= i only (smm_triple_product_sparse_masked)."""
+        the mask with k >= i only (smm_triple_product_sparse_masked).  q may be a pair (D, E) of canonical square DeviceCSR
+        factors, Q = D (x) E never formed (smm_triple_product_sparse_masked_kron): then a mask is required."""
         r, rows, nnz = self._triple_sparse(h, q, full, row_begin, row_end, exact, mask)
         try:
             wide = nnz > np.iinfo(np.int32).max if index_dtype is None else np.dtype(index_dtype) == np.int64
@@ -416,6 +423,19 @@ class Context:
         """spgemm_masked_host into caller-owned HBM (nnz(mask) float64 at d_ptr)."""
         check(self.lib, self.lib.smm_spgemm_masked(self.handle, a.handle, b.handle, mask.handle, _flags(False, exact),
                                                    ctypes.c_void_p(d_ptr or 0)))
+
+    def spgemm_masked_kron_host(self, a, d, e, mask, exact=False):
+        """spgemm_masked_host with B = D (x) E given by its canonical factors and never formed: the values of A (D (x) E) at
+        the positions of mask (a.rows x d.cols * e.cols), in the mask's order (smm_spgemm_masked_kron_host)."""
+        out = np.empty(mask.nnz, dtype=np.float64)
+        check(self.lib, self.lib.smm_spgemm_masked_kron_host(self.handle, a.handle, d.handle, e.handle, mask.handle,
+                                                             _flags(False, exact), _ptr(out)))
+        return out
+
+    def spgemm_masked_kron_into(self, a, d, e, mask, d_ptr, exact=False):
+        """spgemm_masked_kron_host into caller-owned HBM (nnz(mask) float64 at d_ptr); stream rule as spgemm_masked_into."""
+        check(self.lib, self.lib.smm_spgemm_masked_kron(self.handle, a.handle, d.handle, e.handle, mask.handle,
+                                                        _flags(False, exact), ctypes.c_void_p(d_ptr or 0)))
 
     # ------------------------------------------------------------------ sparse x dense
     def tune_spmm(self, mode=0, apply_budget_bytes=0):

@@ -337,8 +337,9 @@ def _kron_shape(d, e, what):
 class KroneckerOperand:
     """Q = D (x) E held as its two factors and never formed: D is p x p' (the temporal covariance), E is r x r' (the spatial
     one); row t * r + j of Q is the pair (t, j), column t' * r' + j' the pair (t', j').  Accepted as matrix_a of
-    sparse_dense_multiply (transpose=False) and as matrix_q of triple_product_apply and innovation_solve; every other call
-    wants the explicit matrix of kronecker_product(D, E).
+    sparse_dense_multiply (transpose=False), as matrix_q of triple_product_apply and innovation_solve, and -- for entries of
+    a product on a given pattern -- as matrix_q of sparse_triple_product(..., mask=L) and as matrix_b of
+    masked_matrix_multiply; every other call wants the explicit matrix of kronecker_product(D, E).
 
     D, E : scipy CSR, anything csr_matrix() accepts, or PinnedOperands.
     .shape, .nnz (of the explicit matrix), .factors == (D, E), .to_scipy() (scipy.sparse.kron of the factors, on the host).
@@ -359,6 +360,21 @@ class KroneckerOperand:
         for name, f in zip("DE", self.factors):
             if f.shape[0] != f.shape[1]:
                 raise ValueError(f"{what}: Q must be square, but its factor {name} is {f.shape[0]} x {f.shape[1]}")
+
+    def _canonical_factors(self, what):
+        """(D, E) with strictly ascending rows, as the masked products search them: a scipy factor that is not canonical is
+        canonicalised on a host copy (as masks are), a PinnedOperand must be canonical."""
+        out = []
+        for name, f in zip("DE", self.factors):
+            if isinstance(f, PinnedOperand):
+                if f.nnz and not f._handle.is_canonical():
+                    raise ValueError(f"{what}: the pinned factor {name} is not canonical (rows must hold strictly ascending "
+                                     "columns): pin it after sum_duplicates()")
+            elif not f.has_canonical_format:
+                f = f.copy()
+                f.sum_duplicates()
+            out.append(f)
+        return tuple(out)
 
 
 def kronecker_product(D, E, pin=False):
@@ -470,8 +486,9 @@ def _product_on_device(ctx, la, lb, triple, output_format, symmetric, compute_fu
 def _as_csr(x):
     # reference :307-310: anything csr_matrix() accepts; no sort, no dedup
     if isinstance(x, KroneckerOperand):
-        raise ValueError("a KroneckerOperand is accepted as matrix_a of sparse_dense_multiply and as matrix_q of "
-                         "triple_product_apply and innovation_solve only; build the explicit matrix with kronecker_product(D, E)")
+        raise ValueError("a KroneckerOperand is accepted as matrix_a of sparse_dense_multiply, as matrix_q of "
+                         "triple_product_apply, innovation_solve and sparse_triple_product(..., mask=) and as matrix_b of "
+                         "masked_matrix_multiply only; build the explicit matrix with kronecker_product(D, E)")
     return x if (isspmatrix_csr(x) or isinstance(x, PinnedOperand)) else csr_matrix(x)
 
 
@@ -594,9 +611,23 @@ def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False, mask=No
     mask (n x n; scipy CSR, anything csr_matrix() accepts, or a PinnedOperand): S only at the positions of the mask
     with k >= i (its values are ignored; positions without a structural contribution hold +0.0), without building the
     structural pattern.  compute_full_matrix=True mirrors that upper part; mask entries below the diagonal are ignored.
+
+    With a mask, matrix_q may be a KroneckerOperand(D, E) (square factors, p * r == K): the entries of H (D (x) E) H^T are
+    then built from the factors, and neither Q nor H Q is ever formed.  The values are those of the same call on
+    kronecker_product(D, E) -- bit for bit under set_exact(True).  The factors' rows are searched, so a scipy factor that is
+    not canonical is canonicalised on a host copy and a pinned one that is not canonical is a ValueError.  Without a mask a
+    KroneckerOperand is refused: the structural pattern needs the explicit matrix of kronecker_product(D, E).
     """
     matrix_h = _as_csr(matrix_h)
-    matrix_q = _as_csr(matrix_q)
+    kron = isinstance(matrix_q, KroneckerOperand)
+    if kron:
+        if mask is None:
+            raise ValueError("sparse_triple_product: a KroneckerOperand as matrix_q needs a pattern -- pass mask= (the structural "
+                             "pattern would need the symbolic phase of a Q that is never formed); without a mask, build the "
+                             "explicit matrix with kronecker_product(D, E)")
+        matrix_q._square("sparse_triple_product")
+    else:
+        matrix_q = _as_csr(matrix_q)
     if matrix_q.shape[0] != matrix_q.shape[1]:
         raise ValueError(f"sparse_triple_product: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
     if matrix_h.shape[1] != matrix_q.shape[0]:
@@ -623,10 +654,12 @@ def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False, mask=No
     elif matrix_h.nnz == 0 or matrix_q.nnz == 0:
         return _zero_result(out_shape)
     ctx = default_context()
-    mats = (matrix_h, matrix_q) if mask is None else (matrix_h, matrix_q, _canonical_mask(mask))
+    qs = matrix_q._canonical_factors("sparse_triple_product") if kron else (matrix_q,)
+    mats = (matrix_h,) + qs + (() if mask is None else (_canonical_mask(mask),))
 
-    def body(lh, lq, lm=None):
-        h, q, m = lh.handle, lq.handle, (lm.handle if lm is not None else None)
+    def body(lh, *rest):
+        h, m = lh.handle, (rest[-1].handle if mask is not None else None)
+        q = (rest[0].handle, rest[1].handle) if kron else rest[0].handle
         if _result_device:
             return _on_device(ctx, lambda: DeviceCSRResult(*ctx.triple_sparse_torch(h, q, full=full, exact=_exact, mask=m), out_shape))
         return _result_csr(*ctx.triple_sparse_host(h, q, full=full, exact=_exact, mask=m), out_shape)
@@ -687,9 +720,15 @@ def masked_matrix_multiply(matrix_a, matrix_b, mask):
     sparse_matrix_multiply(A, B) stores is reproduced bit for bit; otherwise within 1e-10 relative.  A pair (k, j)
     that row i of A does not store is never multiplied.  Returns a scipy CSR (a DeviceCSRResult under
     set_result_device(True)).  Nothing is printed.
+
+    matrix_b may be a KroneckerOperand(D, E) with p * r == K (the mask is then m x p' r'): the entries of A (D (x) E) are built
+    from the factors and Q is never formed; the values are those of the same call on kronecker_product(D, E), bit for bit
+    under set_exact(True).  Factors that are not canonical: as in sparse_triple_product.
     """
     matrix_a = _as_csr(matrix_a)
-    matrix_b = _as_csr(matrix_b)
+    kron = isinstance(matrix_b, KroneckerOperand)
+    if not kron:
+        matrix_b = _as_csr(matrix_b)
     mask = _as_csr(mask)
     if matrix_a.shape[1] != matrix_b.shape[0]:
         raise ValueError("Matrix dimensions are incompatible for multiplication.")
@@ -704,21 +743,24 @@ def masked_matrix_multiply(matrix_a, matrix_b, mask):
         return _pattern_result(ctx, indptr, indices, np.zeros(len(indices), dtype=np.float64), out_shape)
     ctx = default_context()
     mask = _canonical_mask(mask)
+    bs = matrix_b._canonical_factors("masked_matrix_multiply") if kron else (matrix_b,)
 
-    def body(la, lb, lm):
+    def body(la, *rest):
+        lm, b = rest[-1], [lease.handle for lease in rest[:-1]]
+        into, host = (ctx.spgemm_masked_kron_into, ctx.spgemm_masked_kron_host) if kron else (ctx.spgemm_masked_into, ctx.spgemm_masked_host)
         indptr, indices = _mask_pattern(mask)
         if _result_device:
             import torch
 
             def call():
                 data = torch.empty(lm.handle.nnz, dtype=torch.float64, device=torch.device("cuda", ctx.device))
-                ctx.spgemm_masked_into(la.handle, lb.handle, lm.handle, data.data_ptr(), exact=_exact)
+                into(la.handle, *b, lm.handle, data.data_ptr(), exact=_exact)
                 return data
 
             return _pattern_result(ctx, indptr, indices, _on_device(ctx, call), out_shape)
-        return _result_csr(indptr, indices, ctx.spgemm_masked_host(la.handle, lb.handle, lm.handle, exact=_exact), out_shape)
+        return _result_csr(indptr, indices, host(la.handle, *b, lm.handle, exact=_exact), out_shape)
 
-    return with_leases(ctx, (matrix_a, matrix_b, mask), body)
+    return with_leases(ctx, (matrix_a,) + bs + (mask,), body)
 
 
 # ------------------------------------------------------------------ sparse x dense
