@@ -116,18 +116,67 @@ def _pin_device_result(res):
     if nnz == 0:
         return PinnedOperand._adopt(ctx, None, (rows, cols))
     import torch
-    dev = torch.device("cuda", ctx.device)
-    if res.indices.device != dev:
-        raise ValueError(f"pin_operand: the result is on {res.indices.device}, the library works on {dev}")
+    indices = _to_device(ctx, res.indices, True, "pin_operand", "the result")
     indptr = res.indptr.to(torch.int32)                  # (on the device; csr_from_torch waits for torch's stream)
-    return PinnedOperand._adopt(ctx, ctx.csr_from_torch(rows, cols, indptr, res.indices.contiguous(), res.data.contiguous()))
+    return PinnedOperand._adopt(ctx, ctx.csr_from_torch(rows, cols, indptr, indices.contiguous(), res.data.contiguous()))
 
 
-# ------------------------------------------------------------------ localisation taper from coordinates
-def _taper_points(x, what, name):
-    """(points, n, dim, is_torch): a C-contiguous float64 n x dim numpy array, or a float64 CUDA tensor (1-D, or 2-D with
-    unit column stride).  1-D means points on a line.  ValueError before any device work."""
-    is_torch = type(x).__module__.split(".")[0] == "torch"
+# ------------------------------------------------------------------ numpy, tensors and the library's device
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _torch_device(ctx):
+    import torch
+    return torch.device("cuda", ctx.device)
+
+
+def _to_device(ctx, x, is_torch, what, name):
+    """x as a tensor on the library's device: a numpy array is uploaded, a tensor must be there already."""
+    dev = _torch_device(ctx)
+    if not is_torch:
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    if x.device != dev:
+        raise ValueError(f"{what}: {name} is on {x.device}, the library works on {dev}")
+    return x
+
+
+def _as_kind(z, on_device, ctx=None):
+    """z, numpy or a tensor the library made, as the kind the caller gets: a tensor on the library's device (of ctx, or
+    of the default context, which is not touched otherwise) or a numpy array."""
+    if on_device == _is_torch(z):
+        return z
+    if not on_device:
+        return z.cpu().numpy()
+    return _to_device(default_context() if ctx is None else ctx, z, False, None, None)
+
+
+def _dense_zeros(shape, on_device):
+    if on_device:
+        import torch
+        return torch.zeros(shape, dtype=torch.float64, device=_torch_device(default_context()))
+    return np.zeros(shape, dtype=np.float64)
+
+
+def _on_device(ctx, call):
+    """call() with its result left in HBM (torch tensors).  The library works on the context's own stream: torch's
+    current stream is drained first (its allocator may hand out memory that kernels queued there still use) and the
+    context is synchronised before the result is returned -- which also reports anything the kernels' bounds clamps
+    recorded (SMM_ERR_INTERNAL)."""
+    import torch
+    torch.cuda.current_stream(_torch_device(ctx)).synchronize()
+    out = call()
+    ctx.synchronize()
+    return out
+
+
+# ------------------------------------------------------------------ points given by coordinates
+def _points(x, what, name):
+    """(points, n, dim, is_torch): a C-contiguous float64 n x dim numpy array, or a float64 CUDA tensor (1-D or 2-D, any
+    strides: _points_on_device decides what is used in place).  1-D means points on a line.  ValueError before any device
+    work; how many coordinates a point may have is the caller's check."""
+    is_torch = _is_torch(x)
     if is_torch:
         import torch
         if x.dtype != torch.float64 or not x.is_cuda:
@@ -139,16 +188,50 @@ def _taper_points(x, what, name):
     if ndim not in (1, 2):
         raise ValueError(f"{what}: {name} must be 1-D (points on a line) or 2-D (n x dim), got {ndim} dimensions")
     n, dim = int(x.shape[0]), (1 if ndim == 1 else int(x.shape[1]))
-    if dim < 1 or dim > 3:
-        raise ValueError(f"{what}: {name} has {dim} coordinates per point, expected 1, 2 or 3")
     if not is_torch:
         x = np.ascontiguousarray(x.reshape(n, dim))
     return x, n, dim, is_torch
 
 
-def _taper_result(handle, shape, pin):
+def _row_layout(shape, strides, dim):
+    """(copy_needed, ld) of n points of dim coordinates held in a device view of this shape and these strides (in
+    elements).  The kernels read coordinate t of point i at x + i * ld + t, so a view is used in place iff its column
+    stride is 1 (2-D) and its row stride is at least dim; anything else -- an expanded view with row stride 0, a
+    transpose -- is copied contiguous, and then ld = dim.  A strided 1-D view (x[::2]) stays in place."""
+    if (len(shape) == 2 and strides[1] != 1) or strides[0] < dim:
+        return True, dim
+    return False, int(strides[0])
+
+
+def _points_on_device(ctx, x, dim, is_torch, what, name):
+    """(tensor, ld): the points of _points on the library's device, in place where _row_layout allows it."""
+    t = _to_device(ctx, x, is_torch, what, name)
+    copy_needed, ld = _row_layout(tuple(t.shape), t.stride(), dim)
+    return (t.contiguous() if copy_needed else t), ld
+
+
+def _deliver_operand(ctx, build, shape, pin, torch_input, to_device):
+    """The DeviceCSR that build() returns, which the library owns, as the caller's result: adopted where it is by a
+    PinnedOperand (pin), copied device to device into a DeviceCSRResult (to_device), or downloaded into a scipy CSR.  The
+    handle is closed unless it is adopted.  build() runs under _on_device when it reads a caller's tensor (torch_input)
+    or when the result stays in HBM."""
+    if to_device and not pin:
+        import torch
+
+        def call():
+            handle = build()
+            try:
+                indptr, indices = handle.pattern_torch()
+                data = torch.empty(handle.nnz, dtype=torch.float64, device=_torch_device(ctx))
+                handle.values_into(data)
+                return DeviceCSRResult(indptr.to(torch.int64), indices, data, shape)
+            finally:
+                handle.close()
+
+        return _on_device(ctx, call)
+    handle = _on_device(ctx, build) if torch_input else build()
     if pin:
-        return PinnedOperand._adopt(handle.ctx, handle)
+        return PinnedOperand._adopt(ctx, handle)
     try:
         return _result_csr(*handle.to_host(), shape)
     finally:
@@ -183,11 +266,17 @@ def localization_taper(coords, cutoff, coords_b=None, taper="gaspari_cohn", pin=
         raise ValueError(f"{what}: cutoff must be a finite positive number") from None
     if not (cutoff > 0.0 and np.isfinite(cutoff)):
         raise ValueError(f"{what}: cutoff must be a finite positive number, got {cutoff}")
-    a, na, dim, a_torch = _taper_points(coords, what, "coords")
+    def points(x, name):
+        x, n, dim, is_torch = _points(x, what, name)
+        if dim < 1 or dim > 3:
+            raise ValueError(f"{what}: {name} has {dim} coordinates per point, expected 1, 2 or 3")
+        return x, n, dim, is_torch
+
+    a, na, dim, a_torch = points(coords, "coords")
     if coords_b is None:
         b, nb, b_torch = a, na, a_torch
     else:
-        b, nb, dim_b, b_torch = _taper_points(coords_b, what, "coords_b")
+        b, nb, dim_b, b_torch = points(coords_b, "coords_b")
         if dim_b != dim:
             raise ValueError(f"{what}: coords has {dim} coordinates per point, coords_b has {dim_b}")
     if na >= _INT32_MAX or nb >= _INT32_MAX:
@@ -196,31 +285,23 @@ def localization_taper(coords, cutoff, coords_b=None, taper="gaspari_cohn", pin=
         return PinnedOperand._adopt(None, None, (na, nb)) if pin else csr_matrix((na, nb), dtype=np.float64)
     ctx = default_context()
     if not (a_torch or b_torch):
-        return _taper_result(ctx.taper_host(a, None if b is a else b, cutoff, taper), (na, nb), pin)
-    import torch
-    dev = torch.device("cuda", ctx.device)
+        def build():
+            return ctx.taper_host(a, None if b is a else b, cutoff, taper)
+    else:
+        da, lda = _points_on_device(ctx, a, dim, a_torch, what, "coords")
+        db, ldb = (da, lda) if b is a else _points_on_device(ctx, b, dim, b_torch, what, "coords_b")
 
-    def on_dev(t, is_torch, name):
-        if not is_torch:
-            return torch.from_numpy(t).to(dev)
-        if t.device != dev:
-            raise ValueError(f"{what}: {name} is on {t.device}, the library works on {dev}")
-        if t.dim() == 2 and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
-            t = t.contiguous()
-        return t
-
-    da = on_dev(a, a_torch, "coords")
-    db = da if b is a else on_dev(b, b_torch, "coords_b")
-    handle = _on_device(ctx, lambda: ctx.taper_into(da, max(int(da.stride(0)), dim), db, max(int(db.stride(0)), dim), na, nb, dim,
-                                                    cutoff, taper))
-    return _taper_result(handle, (na, nb), pin)
+        def build():
+            return ctx.taper_into(da, lda, db, ldb, na, nb, dim, cutoff, taper)
+    # (a taper stays a scipy CSR under set_result_device(True): to_device is never asked for)
+    return _deliver_operand(ctx, build, (na, nb), pin, a_torch or b_torch, False)
 
 
 # ------------------------------------------------------------------ observation operator from coordinates
 def _interp_axes(axes, what):
     """The grid as a list of 1-D float64 arrays; `axes` is a sequence of 1-D arrays, or one array for a line.  ValueError
     for anything the library would refuse."""
-    if type(axes).__module__.split(".")[0] == "torch":
+    if _is_torch(axes):
         raise ValueError(f"{what}: axes are host arrays (a sequence of 1-D numpy arrays), not tensors")
     if isinstance(axes, np.ndarray) and axes.ndim == 1 and axes.dtype != object:
         axes = [axes]
@@ -268,18 +349,7 @@ def interpolation_operator(points, axes, method="linear", outside="error", pin=F
         if not isinstance(value, str) or value not in table:
             raise ValueError(f"{what}: unknown {name} {value!r}, expected one of {sorted(table)}")
     axes = _interp_axes(axes, what)
-    is_torch = type(points).__module__.split(".")[0] == "torch"
-    if is_torch:
-        import torch
-        if points.dtype != torch.float64 or not points.is_cuda:
-            raise ValueError(f"{what}: a torch points must be a float64 CUDA tensor")
-        ndim = points.dim()
-    else:
-        points = np.asarray(points, dtype=np.float64)
-        ndim = points.ndim
-    if ndim not in (1, 2):
-        raise ValueError(f"{what}: points must be 1-D (points on a line) or 2-D (n x dim), got {ndim} dimensions")
-    n, dim = int(points.shape[0]), (1 if ndim == 1 else int(points.shape[1]))
+    points, n, dim, is_torch = _points(points, what, "points")
     if dim != len(axes):
         raise ValueError(f"{what}: points has {dim} coordinates per point, the grid has {len(axes)} axes")
     K = 1
@@ -296,33 +366,13 @@ def interpolation_operator(points, axes, method="linear", outside="error", pin=F
     ctx = default_context()
     if not is_torch:
         def build():
-            return ctx.interp_host(np.ascontiguousarray(points.reshape(n, dim)), axes, method, outside)
+            return ctx.interp_host(points, axes, method, outside)
     else:
-        dev = torch.device("cuda", ctx.device)
-        if points.device != dev:
-            raise ValueError(f"{what}: points is on {points.device}, the library works on {dev}")
-        if points.stride(0) < dim or (ndim == 2 and points.stride(1) != 1):      # (an expanded or transposed view)
-            points = points.contiguous()
-        ldp = int(points.stride(0))
+        d_points, ldp = _points_on_device(ctx, points, dim, True, what, "points")
 
         def build():
-            return ctx.interp_into(points, ldp, n, dim, axes, method, outside)
-    if pin or not _result_device:
-        return _taper_result(_on_device(ctx, build) if is_torch else build(), shape, pin)
-    import torch
-    dev = torch.device("cuda", ctx.device)
-
-    def call():
-        handle = build()
-        try:
-            indptr, indices = handle.pattern_torch()
-            data = torch.empty(handle.nnz, dtype=torch.float64, device=dev)
-            handle.values_into(data)
-            return DeviceCSRResult(indptr.to(torch.int64), indices, data, shape)
-        finally:
-            handle.close()
-
-    return _on_device(ctx, call)
+            return ctx.interp_into(d_points, ldp, n, dim, axes, method, outside)
+    return _deliver_operand(ctx, build, shape, pin, is_torch, _result_device)
 
 
 # ------------------------------------------------------------------ Kronecker operand Q = D (x) E
@@ -401,74 +451,39 @@ def kronecker_product(D, E, pin=False):
         return PinnedOperand._adopt(None, None, shape) if pin else _zero_result(shape)
     ctx = default_context()
 
-    def body(ld, le):
-        if pin:
-            return PinnedOperand._adopt(ctx, ctx.kron_build(ld.handle, le.handle))
-        if not _result_device:
-            return _taper_result(ctx.kron_build(ld.handle, le.handle), shape, False)
-        import torch
-        dev = torch.device("cuda", ctx.device)
-
-        def call():
-            handle = ctx.kron_build(ld.handle, le.handle)
-            try:
-                indptr, indices = handle.pattern_torch()
-                data = torch.empty(handle.nnz, dtype=torch.float64, device=dev)
-                handle.values_into(data)
-                return DeviceCSRResult(indptr.to(torch.int64), indices, data, shape)
-            finally:
-                handle.close()
-
-        return _on_device(ctx, call)
-
-    return with_leases(ctx, (D, E), body)
-
-
-def _device_zeros(ctx, shape, sparse):
-    import torch
-    dev = torch.device("cuda", ctx.device)
-    if not sparse:
-        return torch.zeros(shape, dtype=torch.float64, device=dev)
-    return DeviceCSRResult(torch.zeros(shape[0] + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
-                           torch.empty(0, dtype=torch.float64, device=dev), shape)
+    return with_leases(ctx, (D, E), lambda ld, le: _deliver_operand(ctx, lambda: ctx.kron_build(ld.handle, le.handle), shape, pin,
+                                                                    False, _result_device))
 
 
 def _zero_result(shape, sparse=True):
     """An all-zero product: on the device under set_result_device(True), else a scipy CSR (sparse) or numpy array."""
-    if _result_device:
-        return _device_zeros(default_context(), shape, sparse)
-    return csr_matrix(shape) if sparse else np.zeros(shape)
-
-
-def _on_device(ctx, call):
-    """call() with its result left in HBM (torch tensors).  The library works on the context's own stream: torch's
-    current stream is drained first (its allocator may hand out memory that kernels queued there still use) and the
-    context is synchronised before the result is returned -- which also reports anything the kernels' bounds clamps
-    recorded (SMM_ERR_INTERNAL)."""
+    if not sparse:
+        return _dense_zeros(shape, _result_device)
+    if not _result_device:
+        return csr_matrix(shape)
     import torch
-    torch.cuda.current_stream(torch.device("cuda", ctx.device)).synchronize()
-    out = call()
-    ctx.synchronize()
-    return out
+    dev = _torch_device(default_context())
+    return DeviceCSRResult(torch.zeros(shape[0] + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                           torch.empty(0, dtype=torch.float64, device=dev), shape)
 
 
-def _product_on_device(ctx, la, lb, triple, output_format, symmetric, compute_full_matrix):
-    """The product of two leased operands with the result left in HBM (torch tensors), through _on_device."""
+def _product_on_device(ctx, la, lb, triple, dense, symmetric, full, mirror):
+    """The product of two leased operands with the result left in HBM (torch tensors), through _on_device; the flags are
+    those sparse_matrix_multiply worked out."""
     import torch
-    dev = torch.device("cuda", ctx.device)
+    dev = _torch_device(ctx)
     a, b = la.handle, lb.handle
 
     def call():
         if triple:
-            mirror = compute_full_matrix == 'mirror' or (_full_symmetric and compute_full_matrix == 0)
             out = torch.empty((a.rows, a.rows), dtype=torch.float64, device=dev)
-            ctx.triple_into(a, b, out.data_ptr(), full=(compute_full_matrix == 1), exact=_exact, mirror=mirror)
+            ctx.triple_into(a, b, out.data_ptr(), full=full, exact=_exact, mirror=mirror)
             return out
-        if output_format == 'dense':
+        if dense:
             out = torch.empty((a.rows, b.cols), dtype=torch.float64, device=dev)
-            ctx.dense_into(a, b, out.data_ptr(), symmetric=symmetric, exact=_exact, mirror=symmetric and _full_symmetric)
+            ctx.dense_into(a, b, out.data_ptr(), symmetric=symmetric, exact=_exact, mirror=mirror)
             return out
-        if symmetric and _full_symmetric:
+        if mirror:
             return DeviceCSRResult(*ctx.spgemm_mirrored_torch(a, b, exact=_exact), (a.rows, b.cols))
         plan, release = plan_for(ctx, la, lb, symmetric, _exact)
         try:
@@ -490,6 +505,31 @@ def _as_csr(x):
                          "triple_product_apply, innovation_solve and sparse_triple_product(..., mask=) and as matrix_b of "
                          "masked_matrix_multiply only; build the explicit matrix with kronecker_product(D, E)")
     return x if (isspmatrix_csr(x) or isinstance(x, PinnedOperand)) else csr_matrix(x)
+
+
+def _hq_operands(matrix_h, matrix_q, what):
+    """(H, Q, kron) of a call on H Q H^T: H as CSR or PinnedOperand, Q the same or -- kron -- a KroneckerOperand with square
+    factors.  ValueError unless Q is square and H's columns are Q's rows."""
+    matrix_h = _as_csr(matrix_h)
+    kron = isinstance(matrix_q, KroneckerOperand)
+    if kron:
+        matrix_q._square(what)
+    else:
+        matrix_q = _as_csr(matrix_q)
+    if matrix_q.shape[0] != matrix_q.shape[1]:
+        raise ValueError(f"{what}: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
+    if matrix_h.shape[1] != matrix_q.shape[0]:
+        raise ValueError("Matrix dimensions are incompatible for multiplication.")
+    return matrix_h, matrix_q, kron
+
+
+def _q_operands(matrix_q, kron, canonical_for=None):
+    """What a call leases for Q: the matrix, or the two factors of a KroneckerOperand -- as they are, or canonical for the
+    masked product `canonical_for`, which searches their rows.  The engine's twin methods then take the handles as
+    fn(h, *q, ...)."""
+    if not kron:
+        return (matrix_q,)
+    return matrix_q._canonical_factors(canonical_for) if canonical_for else matrix_q.factors
 
 
 def _result_csr(indptr, indices, data, shape):
@@ -558,27 +598,30 @@ def sparse_matrix_multiply(matrix_a, matrix_b, output_format='sparse', symmetric
         return np.zeros(out_shape)
 
     ctx = default_context()
+    symmetric, dense, full = bool(symmetric), output_format == 'dense', compute_full_matrix == 1
+    if use_triple_product:
+        mirror = compute_full_matrix == 'mirror' or (_full_symmetric and compute_full_matrix == 0)
+    else:
+        mirror = symmetric and _full_symmetric
 
     def product(la, lb):
         a, b = la.handle, lb.handle
         if _result_device:
-            return _product_on_device(ctx, la, lb, use_triple_product, output_format, bool(symmetric), compute_full_matrix)
+            return _product_on_device(ctx, la, lb, use_triple_product, dense, symmetric, full, mirror)
         if use_triple_product:                                   # reference :325-336
-            mirror = compute_full_matrix == 'mirror' or (_full_symmetric and compute_full_matrix == 0)
-            return ctx.triple_host(a, b, full=(compute_full_matrix == 1), exact=_exact, mirror=mirror)
-        if output_format == 'sparse' and symmetric and _full_symmetric:
+            return ctx.triple_host(a, b, full=full, exact=_exact, mirror=mirror)
+        if dense:                                                # reference :353-365
+            return ctx.dense_host(a, b, symmetric=symmetric, exact=_exact, mirror=mirror)
+        if mirror:
             # opt-in mirror epilogue: the full symmetric CSR (row i = mirrored entries in ascending column
             # order, then the reference's upper-triangle row in its first-touch order)
             return _result_csr(*ctx.spgemm_host_mirrored(a, b, exact=_exact), out_shape)
-        if output_format == 'sparse':                            # reference :338-351
-            plan, release = plan_for(ctx, la, lb, bool(symmetric), _exact)
-            try:
-                indptr, indices, data = plan.numeric_host()
-            finally:
-                release()
-            return _result_csr(indptr, indices, data, out_shape)
-        return ctx.dense_host(a, b, symmetric=bool(symmetric), exact=_exact,  # reference :353-365
-                              mirror=bool(symmetric) and _full_symmetric)
+        plan, release = plan_for(ctx, la, lb, symmetric, _exact)  # reference :338-351
+        try:
+            indptr, indices, data = plan.numeric_host()
+        finally:
+            release()
+        return _result_csr(indptr, indices, data, out_shape)
 
     result = with_leases(ctx, (matrix_a, matrix_b), product)
 
@@ -618,44 +661,26 @@ def sparse_triple_product(matrix_h, matrix_q, compute_full_matrix=False, mask=No
     not canonical is canonicalised on a host copy and a pinned one that is not canonical is a ValueError.  Without a mask a
     KroneckerOperand is refused: the structural pattern needs the explicit matrix of kronecker_product(D, E).
     """
-    matrix_h = _as_csr(matrix_h)
-    kron = isinstance(matrix_q, KroneckerOperand)
-    if kron:
-        if mask is None:
-            raise ValueError("sparse_triple_product: a KroneckerOperand as matrix_q needs a pattern -- pass mask= (the structural "
-                             "pattern would need the symbolic phase of a Q that is never formed); without a mask, build the "
-                             "explicit matrix with kronecker_product(D, E)")
-        matrix_q._square("sparse_triple_product")
-    else:
-        matrix_q = _as_csr(matrix_q)
-    if matrix_q.shape[0] != matrix_q.shape[1]:
-        raise ValueError(f"sparse_triple_product: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
-    if matrix_h.shape[1] != matrix_q.shape[0]:
-        raise ValueError("Matrix dimensions are incompatible for multiplication.")
+    what = "sparse_triple_product"
+    if mask is None and isinstance(matrix_q, KroneckerOperand):
+        raise ValueError("sparse_triple_product: a KroneckerOperand as matrix_q needs a pattern -- pass mask= (the structural "
+                         "pattern would need the symbolic phase of a Q that is never formed); without a mask, build the "
+                         "explicit matrix with kronecker_product(D, E)")
+    matrix_h, matrix_q, kron = _hq_operands(matrix_h, matrix_q, what)
     n = matrix_h.shape[0]
     out_shape = (n, n)
     full = bool(compute_full_matrix)
     if mask is not None:
         mask = _as_csr(mask)
-        _check_mask_shape(mask, out_shape, "sparse_triple_product")
+        _check_mask_shape(mask, out_shape, what)
         if mask.nnz == 0:
             return _zero_result(out_shape)
         if matrix_h.nnz == 0 or matrix_q.nnz == 0:
-            # the mask's upper part (mirrored when full) filled with +0.0, on the host
-            ctx = default_context() if (_result_device or isinstance(mask, PinnedOperand)) else None
-            indptr, indices = _mask_pattern(_canonical_mask(mask))
-            rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
-            keep = indices >= rows
-            up = csr_matrix((np.ones(int(keep.sum())), (rows[keep], indices[keep])), shape=out_shape)
-            if full:
-                up = (up + up.T).tocsr()
-            up.sort_indices()
-            return _pattern_result(ctx, up.indptr.astype(np.int32), up.indices.astype(np.int32), np.zeros(up.nnz), out_shape)
+            return _zeros_on_mask(mask, out_shape, upper=True, mirror=full)
     elif matrix_h.nnz == 0 or matrix_q.nnz == 0:
         return _zero_result(out_shape)
     ctx = default_context()
-    qs = matrix_q._canonical_factors("sparse_triple_product") if kron else (matrix_q,)
-    mats = (matrix_h,) + qs + (() if mask is None else (_canonical_mask(mask),))
+    mats = (matrix_h,) + _q_operands(matrix_q, kron, what) + (() if mask is None else (_canonical_mask(mask),))
 
     def body(lh, *rest):
         h, m = lh.handle, (rest[-1].handle if mask is not None else None)
@@ -702,12 +727,45 @@ def _pattern_result(ctx, indptr, indices, data, shape):
     """A result on a host pattern: scipy CSR, or a DeviceCSRResult under set_result_device(True) (data may be a
     torch tensor already)."""
     if _result_device:
-        import torch
-        dev = torch.device("cuda", ctx.device)
-        if not torch.is_tensor(data):
-            data = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
-        return DeviceCSRResult(torch.from_numpy(indptr.astype(np.int64)).to(dev), torch.from_numpy(indices).to(dev), data, shape)
+        return DeviceCSRResult(*(_as_kind(x, True, ctx) for x in (indptr.astype(np.int64), indices, data)), shape)
     return _result_csr(indptr, indices, data, shape)
+
+
+def _zeros_on_mask(mask, shape, upper=False, mirror=False, scale=False):
+    """The product on a pattern when an operand has no entries: the canonical mask's pattern filled with +0.0, built on
+    the host -- no device unless the result lives there or a pinned mask must be read.  upper: only the positions with
+    column >= row (the masked triple product), mirrored into the lower triangle too with mirror.  scale: w * (+0.0) for
+    the mask's stored weights (sampled_dense_product's scale_by_mask)."""
+    ctx = default_context() if (_result_device or isinstance(mask, PinnedOperand)) else None
+    mask = _canonical_mask(mask)
+    indptr, indices = _mask_pattern(mask)
+    if upper:
+        rows = np.repeat(np.arange(shape[0], dtype=np.int64), np.diff(indptr))
+        keep = indices >= rows
+        up = csr_matrix((np.ones(int(keep.sum())), (rows[keep], indices[keep])), shape=shape)
+        if mirror:
+            up = (up + up.T).tocsr()
+        up.sort_indices()
+        indptr, indices = up.indptr.astype(np.int32), up.indices.astype(np.int32)
+    data = np.zeros(len(indices), dtype=np.float64)
+    if scale:
+        weights = mask._handle.to_host()[2] if isinstance(mask, PinnedOperand) else mask.data[:len(indices)]
+        with np.errstate(invalid="ignore"):
+            data = np.asarray(weights, dtype=np.float64) * data      # (w * +0.0: the weight's sign stays, inf gives NaN)
+    return _pattern_result(ctx, indptr, indices, data, shape)
+
+
+def _values_on_mask(ctx, mask, lease, data, shape):
+    """The result of a product on a pattern: `data`, a numpy array or a tensor left in HBM, in the order of the canonical
+    mask (leased as `lease`).  A pinned mask whose result stays in HBM hands its pattern over device to device; every
+    other case goes through the host pattern."""
+    if _result_device and isinstance(mask, PinnedOperand):
+        import torch
+        indptr, indices = lease.handle.pattern_torch()
+        return DeviceCSRResult(indptr.to(torch.int64), indices, data, shape)
+    if _is_torch(data) and not _result_device:
+        data = data.cpu().numpy()
+    return _pattern_result(ctx, *_mask_pattern(mask), data, shape)
 
 
 def masked_matrix_multiply(matrix_a, matrix_b, mask):
@@ -737,37 +795,32 @@ def masked_matrix_multiply(matrix_a, matrix_b, mask):
     if mask.nnz == 0:
         return _zero_result(out_shape)
     if matrix_a.nnz == 0 or matrix_b.nnz == 0:
-        ctx = default_context() if (_result_device or isinstance(mask, PinnedOperand)) else None
-        mask = _canonical_mask(mask)
-        indptr, indices = _mask_pattern(mask)
-        return _pattern_result(ctx, indptr, indices, np.zeros(len(indices), dtype=np.float64), out_shape)
+        return _zeros_on_mask(mask, out_shape)
     ctx = default_context()
     mask = _canonical_mask(mask)
-    bs = matrix_b._canonical_factors("masked_matrix_multiply") if kron else (matrix_b,)
+    into, host = (ctx.spgemm_masked_kron_into, ctx.spgemm_masked_kron_host) if kron else (ctx.spgemm_masked_into, ctx.spgemm_masked_host)
 
     def body(la, *rest):
         lm, b = rest[-1], [lease.handle for lease in rest[:-1]]
-        into, host = (ctx.spgemm_masked_kron_into, ctx.spgemm_masked_kron_host) if kron else (ctx.spgemm_masked_into, ctx.spgemm_masked_host)
-        indptr, indices = _mask_pattern(mask)
-        if _result_device:
-            import torch
+        if not _result_device:
+            return _values_on_mask(ctx, mask, lm, host(la.handle, *b, lm.handle, exact=_exact), out_shape)
+        import torch
 
-            def call():
-                data = torch.empty(lm.handle.nnz, dtype=torch.float64, device=torch.device("cuda", ctx.device))
-                into(la.handle, *b, lm.handle, data.data_ptr(), exact=_exact)
-                return data
+        def call():
+            data = torch.empty(lm.handle.nnz, dtype=torch.float64, device=_torch_device(ctx))
+            into(la.handle, *b, lm.handle, data.data_ptr(), exact=_exact)
+            return data
 
-            return _pattern_result(ctx, indptr, indices, _on_device(ctx, call), out_shape)
-        return _result_csr(indptr, indices, host(la.handle, *b, lm.handle, exact=_exact), out_shape)
+        return _values_on_mask(ctx, mask, lm, _on_device(ctx, call), out_shape)
 
-    return with_leases(ctx, (matrix_a,) + bs + (mask,), body)
+    return with_leases(ctx, (matrix_a,) + _q_operands(matrix_b, kron, "masked_matrix_multiply") + (mask,), body)
 
 
 # ------------------------------------------------------------------ sparse x dense
 def _dense_operand(x, rows, what, name="X"):
     """(X, k, is_torch): X a float64 C-contiguous numpy array, or a float64 CUDA tensor with unit column stride; 1-D or
     2-D with `rows` rows.  ValueError before any device work (`name`: what the messages call the operand)."""
-    is_torch = type(x).__module__.split(".")[0] == "torch"
+    is_torch = _is_torch(x)
     if is_torch:
         import torch
         if x.dtype != torch.float64 or not x.is_cuda:
@@ -785,27 +838,16 @@ def _dense_operand(x, rows, what, name="X"):
     return x, (1 if ndim == 1 else int(x.shape[1])), is_torch
 
 
-def _dense_apply(ctx, x, k, is_torch, out_rows, host_call, device_call):
+def _dense_apply(ctx, x, k, is_torch, out_rows, what, host_call, device_call):
     """One sparse x dense product: numpy in and out through host_call(x) -> y, or on the device (torch X, or
-    set_result_device(True)) through device_call(d_x, ldx, d_y, ldy) into a torch result."""
+    set_result_device(True)) through device_call(d_x, ldx, k, d_y, ldy) into a torch result."""
     if not (is_torch or _result_device):
         return host_call(x)
     import torch
-    dev = torch.device("cuda", ctx.device)
-    if not is_torch:
-        x = torch.from_numpy(x).to(dev)
-    elif x.device != dev:
-        raise ValueError(f"X is on {x.device}, the library works on {dev}")
-    y = torch.empty((out_rows,) if x.dim() == 1 else (out_rows, k), dtype=torch.float64, device=dev)
-    device_call(x, 1 if x.dim() == 1 else x.stride(0), y, k)
+    x = _to_device(ctx, x, is_torch, what, "X")
+    y = torch.empty((out_rows,) if x.dim() == 1 else (out_rows, k), dtype=torch.float64, device=x.device)
+    device_call(x, 1 if x.dim() == 1 else x.stride(0), k, y, k)
     return y
-
-
-def _dense_zeros(shape, on_device):
-    if on_device:
-        import torch
-        return torch.zeros(shape, dtype=torch.float64, device=torch.device("cuda", default_context().device))
-    return np.zeros(shape, dtype=np.float64)
 
 
 def sparse_dense_multiply(matrix_a, x, transpose=False):
@@ -833,22 +875,15 @@ def sparse_dense_multiply(matrix_a, x, transpose=False):
     if matrix_a.nnz == 0 or k == 0 or m == 0:
         return _dense_zeros(out_shape, is_torch or _result_device)
     ctx = default_context()
+    host, into = (ctx.kron_apply_host, ctx.kron_apply_into) if kron else (ctx.spmm_host, ctx.spmm_into)
+    flags = {"exact": _exact} if kron else {"transpose": transpose, "exact": _exact}
 
-    def body(la):
-        a = la.handle
-        return _dense_apply(ctx, x, k, is_torch, m,
-                            lambda xh: ctx.spmm_host(a, xh, transpose=transpose, exact=_exact),
-                            lambda dx, ldx, dy, ldy: ctx.spmm_into(a, dx, ldx, k, dy, ldy, transpose=transpose, exact=_exact))
+    def body(*leases):
+        a = [lease.handle for lease in leases]
+        return _dense_apply(ctx, x, k, is_torch, m, "sparse_dense_multiply",
+                            lambda xh: host(*a, xh, **flags), lambda *dev: into(*a, *dev, **flags))
 
-    def body_kron(ld, le):
-        d, e = ld.handle, le.handle
-        return _dense_apply(ctx, x, k, is_torch, m,
-                            lambda xh: ctx.kron_apply_host(d, e, xh, exact=_exact),
-                            lambda dx, ldx, dy, ldy: ctx.kron_apply_into(d, e, dx, ldx, k, dy, ldy, exact=_exact))
-
-    if kron:
-        return with_leases(ctx, matrix_a.factors, body_kron)
-    return with_leases(ctx, (matrix_a,), body)
+    return with_leases(ctx, _q_operands(matrix_a, kron), body)
 
 
 def triple_product_apply(matrix_h, matrix_q, x):
@@ -861,40 +896,28 @@ def triple_product_apply(matrix_h, matrix_q, x):
     H @ (Q @ (H.T @ X)); otherwise within rounding.  X is processed in column blocks whose two K x block intermediates fit
     the context's budget (Context.tune_spmm; blocking changes no bit).
     """
-    matrix_h = _as_csr(matrix_h)
-    kron = isinstance(matrix_q, KroneckerOperand)
-    if kron:
-        matrix_q._square("triple_product_apply")
-    else:
-        matrix_q = _as_csr(matrix_q)
-    if matrix_q.shape[0] != matrix_q.shape[1]:
-        raise ValueError(f"triple_product_apply: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
-    if matrix_h.shape[1] != matrix_q.shape[0]:
-        raise ValueError("Matrix dimensions are incompatible for multiplication.")
+    what = "triple_product_apply"
+    matrix_h, matrix_q, kron = _hq_operands(matrix_h, matrix_q, what)
     n = matrix_h.shape[0]
-    x, k, is_torch = _dense_operand(x, n, "triple_product_apply")
+    x, k, is_torch = _dense_operand(x, n, what)
     out_shape = (n,) if len(x.shape) == 1 else (n, k)
     if matrix_h.nnz == 0 or matrix_q.nnz == 0 or k == 0 or n == 0:
         return _dense_zeros(out_shape, is_torch or _result_device)
     ctx = default_context()
+    host, into = (ctx.triple_apply_kron_host, ctx.triple_apply_kron_into) if kron else (ctx.triple_apply_host, ctx.triple_apply_into)
 
-    def body(lh, *lq):
-        h, q = lh.handle, [lease.handle for lease in lq]
-        if kron:
-            return _dense_apply(ctx, x, k, is_torch, n,
-                                lambda xh: ctx.triple_apply_kron_host(h, q[0], q[1], xh, exact=_exact),
-                                lambda dx, ldx, dy, ldy: ctx.triple_apply_kron_into(h, q[0], q[1], dx, ldx, k, dy, ldy, exact=_exact))
-        return _dense_apply(ctx, x, k, is_torch, n,
-                            lambda xh: ctx.triple_apply_host(h, q[0], xh, exact=_exact),
-                            lambda dx, ldx, dy, ldy: ctx.triple_apply_into(h, q[0], dx, ldx, k, dy, ldy, exact=_exact))
+    def body(*leases):
+        hq = [lease.handle for lease in leases]
+        return _dense_apply(ctx, x, k, is_torch, n, what,
+                            lambda xh: host(*hq, xh, exact=_exact), lambda *dev: into(*hq, *dev, exact=_exact))
 
-    return with_leases(ctx, (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)), body)
+    return with_leases(ctx, (matrix_h,) + _q_operands(matrix_q, kron), body)
 
 
 # ------------------------------------------------------------------ (X Y^T) on a pattern
 def _dense_2d(x, rows, what, name):
     """_dense_operand for an operand that must be 2-D: (X, k, is_torch)."""
-    ndim = x.dim() if type(x).__module__.split(".")[0] == "torch" else np.ndim(x)
+    ndim = x.dim() if _is_torch(x) else np.ndim(x)
     if ndim != 2:
         raise ValueError(f"{what}: {name} must be 2-D, got {ndim} dimensions")
     return _dense_operand(x, rows, what, name)
@@ -933,50 +956,24 @@ def sampled_dense_product(x, y, mask, scale_by_mask=False):
     if mask.nnz == 0:
         return _zero_result(out_shape)
     if k == 0:
-        ctx = default_context() if (_result_device or isinstance(mask, PinnedOperand)) else None
-        mask = _canonical_mask(mask)
-        indptr, indices = _mask_pattern(mask)
-        data = np.zeros(len(indices), dtype=np.float64)
-        if scale_by_mask:
-            weights = mask._handle.to_host()[2] if isinstance(mask, PinnedOperand) else mask.data[:len(indices)]
-            with np.errstate(invalid="ignore"):
-                data = np.asarray(weights, dtype=np.float64) * data      # (w * +0.0: the weight's sign stays, inf gives NaN)
-        return _pattern_result(ctx, indptr, indices, data, out_shape)
+        return _zeros_on_mask(mask, out_shape, scale=scale_by_mask)
     ctx = default_context()
     mask = _canonical_mask(mask)
 
     def body(lm):
-        # a pinned mask whose result stays in HBM hands its pattern over on the device; every other case as before
-        on_device_pattern = _result_device and isinstance(mask, PinnedOperand)
-        indptr, indices = (None, None) if on_device_pattern else _mask_pattern(mask)
         if not (x_torch or y_torch or _result_device):
             data = ctx.sddmm_host(lm.handle, x, None if y is x else y, scale=scale_by_mask, exact=_exact)
-            return _result_csr(indptr, indices, data, out_shape)
+            return _values_on_mask(ctx, mask, lm, data, out_shape)
         import torch
-        dev = torch.device("cuda", ctx.device)
-
-        def on_dev(t, is_torch, name):
-            if not is_torch:
-                return torch.from_numpy(t).to(dev)
-            if t.device != dev:
-                raise ValueError(f"{what}: {name} is on {t.device}, the library works on {dev}")
-            return t
-
-        dx = on_dev(x, x_torch, "X")
-        dy = dx if y is x else on_dev(y, y_torch, "Y")
+        dx = _to_device(ctx, x, x_torch, what, "X")
+        dy = dx if y is x else _to_device(ctx, y, y_torch, what, "Y")
 
         def call():
-            data = torch.empty(lm.handle.nnz, dtype=torch.float64, device=dev)
+            data = torch.empty(lm.handle.nnz, dtype=torch.float64, device=dx.device)
             ctx.sddmm_into(lm.handle, dx, dx.stride(0), dy, dy.stride(0), k, data, scale=scale_by_mask, exact=_exact)
             return data
 
-        data = _on_device(ctx, call)
-        if on_device_pattern:
-            d_indptr, d_indices = lm.handle.pattern_torch()
-            return DeviceCSRResult(d_indptr.to(torch.int64), d_indices, data, out_shape)
-        if _result_device:
-            return _pattern_result(ctx, indptr, indices, data, out_shape)
-        return _result_csr(indptr, indices, data.cpu().numpy(), out_shape)
+        return _values_on_mask(ctx, mask, lm, _on_device(ctx, call), out_shape)
 
     return with_leases(ctx, (mask,), body)
 
@@ -1043,17 +1040,9 @@ def _cg_on_host(apply, d, tol, maxiter, record=False):
 
 def _innovation_operands(matrix_h, matrix_q, matrix_r, what):
     """(H, Q, R, kron, n) of a call on H Q H^T + R: H and Q as CSR or PinnedOperand (Q a KroneckerOperand when kron), R the
-    same, built from its diagonal when a vector, or None.  ValueError for shapes that do not fit."""
-    matrix_h = _as_csr(matrix_h)
-    kron = isinstance(matrix_q, KroneckerOperand)
-    if kron:
-        matrix_q._square(what)
-    else:
-        matrix_q = _as_csr(matrix_q)
-    if matrix_q.shape[0] != matrix_q.shape[1]:
-        raise ValueError(f"{what}: Q must be square, got {matrix_q.shape[0]} x {matrix_q.shape[1]}")
-    if matrix_h.shape[1] != matrix_q.shape[0]:
-        raise ValueError("Matrix dimensions are incompatible for multiplication.")
+    same, built from its diagonal when a vector, or None (also for an R without entries).  ValueError for shapes that do
+    not fit."""
+    matrix_h, matrix_q, kron = _hq_operands(matrix_h, matrix_q, what)
     n = matrix_h.shape[0]
     if matrix_r is not None:
         if not (isspmatrix_csr(matrix_r) or isinstance(matrix_r, PinnedOperand) or hasattr(matrix_r, "tocsr")):
@@ -1065,7 +1054,21 @@ def _innovation_operands(matrix_h, matrix_q, matrix_r, what):
         matrix_r = _as_csr(matrix_r)
         if tuple(matrix_r.shape) != (n, n):
             raise ValueError(f"{what}: R must be {n} x {n}, got {matrix_r.shape[0]} x {matrix_r.shape[1]}")
+        if matrix_r.nnz == 0:
+            matrix_r = None
     return matrix_h, matrix_q, matrix_r, kron, n
+
+
+def _innovation_leased(matrix_h, matrix_q, matrix_r, kron):
+    """The operands an innovation call leases: H, Q or its two factors, then R unless it is None."""
+    return (matrix_h,) + _q_operands(matrix_q, kron) + (() if matrix_r is None else (matrix_r,))
+
+
+def _innovation_handles(leases, kron):
+    """(h, q, r) of the leases of _innovation_leased: q a list of one handle or two, r None without R."""
+    handles = [lease.handle for lease in leases]
+    nq = 2 if kron else 1
+    return handles[0], handles[1:1 + nq], (handles[1 + nq] if len(handles) > 1 + nq else None)
 
 
 def _innovation_tol(tol, what):
@@ -1114,47 +1117,25 @@ def innovation_solve(matrix_h, matrix_q, matrix_r, d, tol=1e-8, maxiter=None):
         raise ValueError(f"innovation_solve: maxiter must be a non-negative integer, got {maxiter}")
     maxiter = int(maxiter)
     on_device = is_torch or _result_device
-    if matrix_r is not None and matrix_r.nnz == 0:
-        matrix_r = None
     if k == 0 or n == 0:
         return _dense_zeros(tuple(d.shape), on_device), SolveInfo(k)
     if matrix_h.nnz == 0 or matrix_q.nnz == 0:           # S = 0: R Z = D, iterated on the host
-        dh = (d.cpu().numpy() if is_torch else d).reshape(n, k)
-        z, info = _cg_on_host(_host_r_apply(matrix_r), dh, tol, maxiter)
-        z = z.reshape(tuple(d.shape))
-        if on_device:
-            import torch
-            z = torch.from_numpy(z).to(torch.device("cuda", default_context().device))
-        return z, info
+        z, info = _cg_on_host(_host_r_apply(matrix_r), _as_kind(d, False).reshape(n, k), tol, maxiter)
+        return _as_kind(z.reshape(tuple(d.shape)), on_device), info
     ctx = default_context()
+    host, into = (ctx.innovation_solve_kron_host, ctx.innovation_solve_kron_into) if kron else (ctx.innovation_solve_host, ctx.innovation_solve_into)
 
-    nq = 2 if kron else 1
-
-    def body(lh, *rest):
-        h, q, lr = lh.handle, [lease.handle for lease in rest[:nq]], rest[nq:]
-        r = lr[0].handle if lr else None
+    def body(*leases):
+        h, q, r = _innovation_handles(leases, kron)
         if not on_device:
-            if kron:
-                return ctx.innovation_solve_kron_host(h, q[0], q[1], r, d, tol, maxiter, exact=_exact)
-            return ctx.innovation_solve_host(h, q[0], r, d, tol, maxiter, exact=_exact)
+            return host(h, *q, r, d, tol, maxiter, exact=_exact)
         import torch
-        dev = torch.device("cuda", ctx.device)
-        if not is_torch:
-            b = torch.from_numpy(d).to(dev)
-        elif d.device != dev:
-            raise ValueError(f"D is on {d.device}, the library works on {dev}")
-        else:
-            b = d
-        z = torch.empty(tuple(b.shape), dtype=torch.float64, device=dev)
-        ldb = 1 if b.dim() == 1 else b.stride(0)
-        if kron:
-            info = ctx.innovation_solve_kron_into(h, q[0], q[1], r, b, ldb, k, z, k, tol, maxiter, exact=_exact)
-        else:
-            info = ctx.innovation_solve_into(h, q[0], r, b, ldb, k, z, k, tol, maxiter, exact=_exact)
+        b = _to_device(ctx, d, is_torch, "innovation_solve", "D")
+        z = torch.empty(tuple(b.shape), dtype=torch.float64, device=b.device)
+        info = into(h, *q, r, b, 1 if b.dim() == 1 else b.stride(0), k, z, k, tol, maxiter, exact=_exact)
         return z, info
 
-    mats = (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)) + ((matrix_r,) if matrix_r is not None else ())
-    return with_leases(ctx, mats, body)
+    return with_leases(ctx, _innovation_leased(matrix_h, matrix_q, matrix_r, kron), body)
 
 
 # ------------------------------------------------------------------ log det(H Q H^T + R) by stochastic Lanczos quadrature
@@ -1292,28 +1273,20 @@ def innovation_logdet(matrix_h, matrix_q, matrix_r, probes=32, seed=0, tol=1e-8,
     if d is not None:
         d, m, is_torch = _dense_operand(d, n, what, "D")
     on_device = is_torch or _result_device
-    if matrix_r is not None and matrix_r.nnz == 0:
-        matrix_r = None
     res = LogdetResult()
 
     def finish(z, info):
-        """Split the batch (numpy, or a tensor on the device path) into d's columns and the probes'."""
+        """Split the batch (numpy, or a tensor on the device path) into d's columns and the probes', each of the kind
+        the caller gets."""
+        def part(cols, on_device):
+            return _as_kind(cols.contiguous() if _is_torch(cols) else np.ascontiguousarray(cols), on_device)
+
         if d is not None:
-            zd = z[:, :m].reshape(tuple(d.shape))
-            res.Z = zd.contiguous() if hasattr(zd, "contiguous") else np.ascontiguousarray(zd)
+            res.Z = part(z[:, :m].reshape(tuple(d.shape)), on_device)
             res.info_d = _info_columns(info, slice(0, m))
         if return_solutions:
-            zs = z[:, m:]
-            res.solutions = zs.contiguous() if hasattr(zs, "contiguous") else np.ascontiguousarray(zs)
+            res.solutions = part(z[:, m:], _result_device)
         return _slq_result(res, _info_columns(info, slice(m, m + probes)), n)
-
-    def to_kind(z, want_device):
-        if want_device == hasattr(z, "is_cuda"):
-            return z
-        if want_device:
-            import torch
-            return torch.from_numpy(np.ascontiguousarray(z)).to(torch.device("cuda", default_context().device))
-        return z.cpu().numpy()
 
     if n == 0:
         res.info = SolveInfo(probes, maxiter)
@@ -1329,42 +1302,23 @@ def innovation_logdet(matrix_h, matrix_q, matrix_r, probes=32, seed=0, tol=1e-8,
             raise ValueError(f"{what}: H Q H^T has no entries and R is None: the matrix is singular")
         batch = _probe_signs(n, probes, seed)
         if d is not None:
-            dh = (d.cpu().numpy() if is_torch else d).reshape(n, m)
-            batch = np.concatenate([dh, batch], axis=1)
-        z, info = _cg_on_host(_host_r_apply(matrix_r), np.ascontiguousarray(batch), tol, maxiter, record=True)
-        finish(z, info)
-        if res.Z is not None:
-            res.Z = to_kind(res.Z, on_device)
-        if res.solutions is not None:
-            res.solutions = to_kind(res.solutions, _result_device)
-        return res
+            batch = np.concatenate([_as_kind(d, False).reshape(n, m), batch], axis=1)
+        return finish(*_cg_on_host(_host_r_apply(matrix_r), np.ascontiguousarray(batch), tol, maxiter, record=True))
     ctx = default_context()
-    nq = 2 if kron else 1
+    solve = ctx.innovation_solve_coef_kron_into if kron else ctx.innovation_solve_coef_into
 
-    def body(lh, *rest):
+    def body(*leases):
         import torch
-        h, q, lr = lh.handle, [lease.handle for lease in rest[:nq]], rest[nq:]
-        r = lr[0].handle if lr else None
-        dev = torch.device("cuda", ctx.device)
-        if is_torch and d.device != dev:
-            raise ValueError(f"D is on {d.device}, the library works on {dev}")
+        h, q, r = _innovation_handles(leases, kron)
+        dev = _torch_device(ctx)
+        d_rhs = None if d is None else _to_device(ctx, d, is_torch, what, "D")
         k = m + probes
         b = torch.empty((n, k), dtype=torch.float64, device=dev)
         if m:
-            b[:, :m] = (d if is_torch else torch.from_numpy(d).to(dev)).reshape(n, m)
+            b[:, :m] = d_rhs.reshape(n, m)
         ctx.probe_fill_into(b.data_ptr() + 8 * m, k, n, probes, seed)
         z = torch.empty((n, k), dtype=torch.float64, device=dev)
-        if kron:
-            info = ctx.innovation_solve_coef_kron_into(h, q[0], q[1], r, b, k, k, z, k, tol, maxiter, exact=_exact)
-        else:
-            info = ctx.innovation_solve_coef_into(h, q[0], r, b, k, k, z, k, tol, maxiter, exact=_exact)
+        info = solve(h, *q, r, b, k, k, z, k, tol, maxiter, exact=_exact)
         return z, info
 
-    mats = (matrix_h,) + (matrix_q.factors if kron else (matrix_q,)) + ((matrix_r,) if matrix_r is not None else ())
-    z, info = with_leases(ctx, mats, body)
-    finish(z, info)
-    if res.Z is not None:
-        res.Z = to_kind(res.Z, on_device)
-    if res.solutions is not None:
-        res.solutions = to_kind(res.solutions, _result_device)
-    return res
+    return finish(*with_leases(ctx, _innovation_leased(matrix_h, matrix_q, matrix_r, kron), body))

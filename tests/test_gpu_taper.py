@@ -105,6 +105,41 @@ def test_column_slice_in_place_and_own_buffer_against_a_copy(ctx, dim):
     _assert_same((rect.indptr, rect.indices, rect.data), restate(host[:50], host, 0.8, "boxcar"), "numpy against a tensor")
 
 
+def test_an_expanded_view_is_copied_and_a_strided_one_is_used_in_place(ctx):
+    """Points on a line as 1-D views of a wider device tensor.  Row stride 0 (seven copies of one point) is copied, never
+    read as seven consecutive doubles; row stride 2 of a column (every other row) is read where it is.  Each result is, bit
+    for bit, that of the same points as a numpy array (or a contiguous copy) and the restatement's."""
+    import torch
+    from sparse_matrix_mult_amd import localization_taper
+    dev = torch.device("cuda", ctx.device)
+    cutoff = 0.8
+    wide = torch.from_numpy(np.random.default_rng(45).random((300, 5)) * 3.0).to(dev)
+    same = wide[3:4, 1].expand(7)                                    # cut from the middle of the storage
+    assert same.stride() == (0,)
+    point = wide[3, 1].item()
+    copies = np.full(7, point)
+    other5 = point + np.array([-1.0, -0.2, 0.0, 0.3, 2.0])            # three inside the cutoff, two outside
+
+    def arrays(L):
+        assert sp.isspmatrix_csr(L) and L.has_canonical_format
+        return L.indptr, L.indices, L.data
+
+    square = arrays(localization_taper(same, cutoff))
+    _assert_same(square, arrays(localization_taper(copies, cutoff)), "expanded view, square: against numpy")
+    _assert_same(square, restate(copies, None, cutoff, "gaspari_cohn"), "expanded view, square")
+    assert square[1].size == 49 and np.all(square[2] == 1.0)
+    rect = arrays(localization_taper(other5, cutoff, coords_b=same))
+    _assert_same(rect, arrays(localization_taper(other5, cutoff, coords_b=copies)), "expanded view as coords_b: against numpy")
+    _assert_same(rect, restate(other5, copies, cutoff, "gaspari_cohn"), "expanded view as coords_b")
+    assert np.array_equal(np.diff(rect[0]), [0, 7, 7, 7, 0])
+
+    strided = wide[::2, 1]
+    assert strided.stride() == (10,)
+    in_place = arrays(localization_taper(strided, cutoff))
+    _assert_same(in_place, arrays(localization_taper(strided.contiguous(), cutoff)), "strided view: against its copy")
+    _assert_same(in_place, restate(wide.cpu().numpy()[::2, 1], None, cutoff, "gaspari_cohn"), "strided view")
+
+
 def test_non_finite_coordinates_are_refused_and_the_context_stays_usable(ctx):
     from sparse_matrix_mult_amd.engine import SmmError
     good = uniform(100, 2, 11)

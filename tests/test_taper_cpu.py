@@ -184,6 +184,22 @@ def test_argument_errors_before_any_device_work(monkeypatch):
         mo.localization_taper(P, 1.0, coords_b=torch.ones((6, 2), dtype=torch.float64))      # a CPU tensor
 
 
+@pytest.mark.parametrize("shape, strides, dim, want", [
+    ((7,), (0,), 1, (True, 1)),              # seven copies of one point (an expanded view): never read as seven doubles
+    ((7,), (1,), 1, (False, 1)),
+    ((7,), (2,), 1, (False, 2)),             # x[::2] stays where it is
+    ((300, 2), (5, 1), 2, (False, 5)),       # a column slice of a wider tensor
+    ((300, 2), (1, 300), 2, (True, 2)),      # a transpose
+    ((1, 3), (0, 1), 3, (True, 3)),
+    ((4, 3), (3, 1), 3, (False, 3)),
+])
+def test_row_layout_decides_between_in_place_and_a_copy(shape, strides, dim, want):
+    """The one rule by which localization_taper and interpolation_operator hand a device view to the kernels, which read
+    coordinate t of point i at x + i * ld + t: (copy_needed, ld)."""
+    from sparse_matrix_mult_amd.matrix_ops import _row_layout
+    assert _row_layout(shape, strides, dim) == want
+
+
 def test_empty_inputs_without_a_device(monkeypatch):
     mo = _no_device(monkeypatch)
     for a, b, shape in ((np.ones((0, 3)), None, (0, 0)), (np.ones((0, 2)), np.ones((5, 2)), (0, 5)), (np.ones(4), np.ones(0), (4, 0))):
