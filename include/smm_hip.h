@@ -440,6 +440,53 @@ int  smm_taper_build(smm_ctx *ctx, int dim, int kind, double cutoff, int64_t na,
 int  smm_taper_build_host(smm_ctx *ctx, int dim, int kind, double cutoff, int64_t na, const double *a, int64_t lda,
                           int64_t nb, const double *b, int64_t ldb, smm_csr **out);
 
+/* ------------------------------------------------------------------ parametric covariance on a given pattern
+ * For every stored entry p = (i, j) of `pattern` (na x nb; any legal CSR of this context: rows may be unsorted, repeat
+ * columns, be empty) a covariance value variance * c(h) and / or its derivative with respect to a correlation length,
+ * from the coordinates a_i and b_j, written at position p of the caller-owned arrays d_val / d_dval (nnz(pattern) float64
+ * each, in the pattern's stored order; either may be NULL, not both).  The pattern comes from an operand the library can
+ * already build -- a taper (smm_taper_build), Q's pattern, or H's for cross-covariances; this call searches nothing and
+ * writes neither the pattern operand nor anything cached for it.  a: na x dim, b: nb x dim, row-major float64 with leading
+ * dimensions lda, ldb >= dim; dim is 1, 2 or 3; 64-bit offsets; d_b may be d_a's own buffer.  length: dim doubles in HOST
+ * memory, the correlation length of every coordinate.  Distances are Euclidean in the scaled coordinates.
+ * Every product is rounded before its add; there is one mode, no SMM_EXACT flag and no other order.
+ *   Distance    u_t = (a[i,t] - b[j,t]) / length[t] (IEEE division); h2 = +0.0; h2 = h2 + u_t * u_t for t = 0 .. dim-1;
+ *               h = sqrt(h2) (IEEE square root).  The sign of u_t cannot matter: the square case on a symmetric pattern
+ *               is symmetric bit for bit.
+ *   Models      c = the correlation, g = -dc/dh; e = exp(x) is the device library's double exp.
+ *               SMM_COV_SPHERICAL    h < 1: c = ((0.5 * h) * h - 1.5) * h + 1.0, g = 1.5 - 1.5 * (h * h); h >= 1: both +0.0
+ *               SMM_COV_EXPONENTIAL  e = exp(-h);  c = e;  g = e
+ *               SMM_COV_GAUSSIAN     e = exp(-h2); c = e;  g = (2.0 * h) * e
+ *               SMM_COV_MATERN32     s = sqrt3 * h (sqrt3 = 1.7320508075688772, the nearest double); e = exp(-s);
+ *                                    c = (1.0 + s) * e;  g = (3.0 * h) * e
+ *               SMM_COV_MATERN52     s = sqrt5 * h (sqrt5 = 2.23606797749979); e = exp(-s);
+ *                                    c = ((1.0 + s) + (5.0 / 3.0) * h2) * e;  g = (((5.0 / 3.0) * h) * (1.0 + s)) * e
+ *   Value       val[p] = variance * c: exactly variance at h = 0 in every model.
+ *   Derivative  wrt = t in 0 .. dim-1, d/d length[t]: +0.0 when h == 0, else ((variance * g) * (u_t * u_t)) / (h * length[t]).
+ *               wrt = SMM_COV_WRT_ALL, d/d of one common length: +0.0 when h == 0, else ((variance * g) * h) / length[0];
+ *               accepted only when all dim lengths are the same double.  wrt = SMM_COV_WRT_NONE: no derivative.
+ *   SMM_COV_SCALE_BY_PATTERN (the only flag): each output is multiplied last by the pattern's stored value w[p], the
+ *               multiply always carried out (0 * inf = NaN).  With w a Gaspari-Cohn taper this is Q = L o C, compactly
+ *               supported and still positive semidefinite; the taper does not depend on the length, so dQ takes the same factor.
+ *   The spherical model is bit-identical to that recipe in IEEE double; the others are within the device exp's error (a
+ *   few ulp) of it; two calls give the same bits.  No float atomics.
+ * Coordinates are not screened: an infinite one gives what the recipe gives (inf - inf = NaN), a NaN gives NaN at its
+ * entries in every model (the spherical one included: neither h < 1 nor h >= 1 holds).
+ * SMM_ERR_INVALID, before any launch: an unknown flag or model, dim outside 1..3, a length that is not finite or <= 0, a
+ * variance that is not finite (0 is allowed), wrt outside {SMM_COV_WRT_NONE, 0 .. dim-1, SMM_COV_WRT_ALL}, SMM_COV_WRT_ALL
+ * with unequal lengths, d_dval without wrt or wrt without d_dval, both outputs NULL, lda or ldb < dim, a NULL coordinate
+ * buffer with rows > 0, na or nb other than the pattern's rows and columns, SMM_COV_SCALE_BY_PATTERN on a pattern without
+ * values, an output that overlaps the other output or the coordinates.  nnz(pattern) == 0: no launch, SMM_OK.  A column
+ * outside [0, nb) (reachable only through smm_csr_from_device) is skipped and reported as SMM_ERR_INTERNAL. */
+enum smm_cov_model { SMM_COV_SPHERICAL = 0, SMM_COV_EXPONENTIAL = 1, SMM_COV_GAUSSIAN = 2, SMM_COV_MATERN32 = 3, SMM_COV_MATERN52 = 4 };
+enum smm_cov_wrt { SMM_COV_WRT_NONE = -1, SMM_COV_WRT_ALL = 3 };
+enum smm_cov_flags { SMM_COV_SCALE_BY_PATTERN = 32 };
+int  smm_cov_eval(smm_ctx *ctx, smm_csr *pattern, int flags, int model, int dim, const double *length, double variance, int wrt,
+                  int64_t na, const double *d_a, int64_t lda, int64_t nb, const double *d_b, int64_t ldb, double *d_val, double *d_dval);
+/* Same with a, b, val and dval in host memory (through pool temporaries; b == a with ldb == lda is uploaded once). */
+int  smm_cov_eval_host(smm_ctx *ctx, smm_csr *pattern, int flags, int model, int dim, const double *length, double variance, int wrt,
+                       int64_t na, const double *a, int64_t lda, int64_t nb, const double *b, int64_t ldb, double *val, double *dval);
+
 /* ------------------------------------------------------------------ observation operator from point coordinates
  * H (n x K): the matrix that interpolates a field on a rectilinear grid to n points, as a new operand owned by the caller
  * (smm_csr_destroy), as smm_taper_build returns one -- the H of smm_triple_apply, smm_innovation_solve and their _kron forms,

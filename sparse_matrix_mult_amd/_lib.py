@@ -24,6 +24,14 @@ SMM_TRANSPOSE = 16
 SMM_SCALE_BY_MASK = 32
 SMM_TAPER_BOXCAR = 0
 SMM_TAPER_GASPARI_COHN = 1
+SMM_COV_SPHERICAL = 0
+SMM_COV_EXPONENTIAL = 1
+SMM_COV_GAUSSIAN = 2
+SMM_COV_MATERN32 = 3
+SMM_COV_MATERN52 = 4
+SMM_COV_WRT_NONE = -1
+SMM_COV_WRT_ALL = 3
+SMM_COV_SCALE_BY_PATTERN = 32
 SMM_INTERP_LINEAR = 0
 SMM_INTERP_NEAREST = 1
 SMM_INTERP_REJECT = 0
@@ -41,6 +49,8 @@ _pp = ctypes.POINTER(ctypes.c_void_p)
 # the argument tails of the entries that take one row-major block in and give one out, behind the context and the operands
 _BLOCKS = [ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]                  # flags, k, in, ld_in, out, ld_out
 _SOLVE = _BLOCKS + [ctypes.c_double, _c_i64, _vp, _vp, _vp, _vp]            # tol, maxiter, the four per-column outputs
+# smm_cov_eval[_host] behind the context and the pattern: flags, model, dim, length, variance, wrt, na, a, lda, nb, b, ldb, val, dval
+_COV = [ctypes.c_int] * 3 + [_vp, ctypes.c_double, ctypes.c_int, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp]
 
 # name -> (restype, argtypes); every v2 symbol declared in include/smm_hip.h
 V2_PROTOTYPES = {
@@ -123,6 +133,8 @@ V2_PROTOTYPES = {
     "smm_taper_build": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64, _pp]),
     "smm_taper_build_host": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64,
                                             _pp]),
+    "smm_cov_eval": (ctypes.c_int, [_vp, _vp] + _COV),
+    "smm_cov_eval_host": (ctypes.c_int, [_vp, _vp] + _COV),
     "smm_interp_build": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, _c_i64, _vp, _c_i64, _pp]),
     "smm_interp_build_host": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, _c_i64, _vp, _c_i64, _pp]),
     "smm_innovation_solve": (ctypes.c_int, [_vp] * 4 + _SOLVE),

@@ -15,6 +15,7 @@
 #include "smm_sddmm.hpp"
 #include "smm_taper.hpp"
 #include "smm_interp.hpp"
+#include "smm_cov.hpp"
 #include "../../include/smm_hip.h"
 
 #include <sys/mman.h>
@@ -4307,6 +4308,105 @@ extern "C" int smm_sddmm_host(smm_ctx *c, smm_csr *mask, int flags, int64_t k, c
     CHK(sddmm_impl(c, mask, flags, k, dx, k, same ? (const double *)dx : (const double *)dy, k, dc));
     CHK(take_plan_error(c, "smm_sddmm_host"));
     return download(c, c_data, dc, (size_t)mask->nnz * sizeof(double));
+}
+
+// ------------------------------------------------------------------------------ parametric covariance on a pattern
+// (kernel: smm_cov.hpp; contract: include/smm_hip.h)
+
+// Everything smm_cov_eval[_host] refuse before any launch; on success A holds the model, the lengths and the pattern.
+static int cov_args(smm_ctx *c, smm_csr *pat, int flags, int model, int dim, const double *length, double variance, int wrt, int64_t na,
+                    const double *a, int64_t lda, int64_t nb, const double *b, int64_t ldb, const double *val, const double *dval,
+                    const char *where, CovArgs *A)
+{
+    if (flags & ~SMM_COV_SCALE_BY_PATTERN) return fail(SMM_ERR_INVALID, "%s: only SMM_COV_SCALE_BY_PATTERN is a flag of this call", where);
+    if (!pat) return fail(SMM_ERR_INVALID, "%s: pattern is NULL", where);
+    if (pat->ctx != c) return fail(SMM_ERR_INVALID, "%s: pattern belongs to another context", where);
+    if (model < SMM_COV_SPHERICAL || model > SMM_COV_MATERN52) return fail(SMM_ERR_INVALID, "%s: unknown model %d", where, model);
+    if (dim < 1 || dim > 3) return fail(SMM_ERR_INVALID, "%s: dim must be 1, 2 or 3, got %d", where, dim);
+    if (!length) return fail(SMM_ERR_INVALID, "%s: length is NULL", where);
+    for (int t = 0; t < dim; ++t)
+        if (!(length[t] > 0.0) || !std::isfinite(length[t]))
+            return fail(SMM_ERR_INVALID, "%s: length[%d] must be finite and positive, got %g", where, t, length[t]);
+    if (!std::isfinite(variance)) return fail(SMM_ERR_INVALID, "%s: variance must be finite, got %g", where, variance);
+    if (wrt != SMM_COV_WRT_NONE && wrt != SMM_COV_WRT_ALL && (wrt < 0 || wrt >= dim))
+        return fail(SMM_ERR_INVALID, "%s: wrt must be SMM_COV_WRT_NONE, a coordinate 0 .. %d or SMM_COV_WRT_ALL, got %d", where, dim - 1, wrt);
+    if (wrt == SMM_COV_WRT_ALL)
+        for (int t = 1; t < dim; ++t)
+            if (length[t] != length[0]) return fail(SMM_ERR_INVALID, "%s: SMM_COV_WRT_ALL needs one common length, got %g and %g", where, length[0], length[t]);
+    if ((dval != nullptr) != (wrt != SMM_COV_WRT_NONE)) return fail(SMM_ERR_INVALID, "%s: dval and wrt go together (dval %s, wrt %d)", where, dval ? "given" : "NULL", wrt);
+    if (!val && !dval) return fail(SMM_ERR_INVALID, "%s: val and dval are both NULL", where);
+    if (lda < dim || ldb < dim) return fail(SMM_ERR_INVALID, "%s: need lda, ldb >= dim (dim %d, lda %lld, ldb %lld)", where, dim, (long long)lda, (long long)ldb);
+    if ((na > 0 && !a) || (nb > 0 && !b)) return fail(SMM_ERR_INVALID, "%s: a or b is NULL", where);
+    if (na != pat->rows || nb != pat->cols)
+        return fail(SMM_ERR_INVALID, "%s: the pattern is %lld x %lld, the points are %lld and %lld", where, (long long)pat->rows, (long long)pat->cols,
+                    (long long)na, (long long)nb);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(validate(c, pat));
+    if ((flags & SMM_COV_SCALE_BY_PATTERN) && pat->nnz > 0 && !pat->val) return fail(SMM_ERR_INVALID, "%s: SMM_COV_SCALE_BY_PATTERN needs the pattern's values", where);
+    *A = CovArgs{};
+    A->m = (int)pat->rows; A->n = (int)pat->cols; A->nnz = (int)pat->nnz;
+    A->ptr = pat->ptr; A->idx = pat->idx; A->w = pat->val;
+    for (int t = 0; t < 3; ++t) A->len[t] = t < dim ? length[t] : 1.0;
+    A->variance = variance; A->model = model; A->wrt = wrt;
+    A->scale = (flags & SMM_COV_SCALE_BY_PATTERN) ? 1 : 0;
+    A->err = c->d_err;
+    return SMM_OK;
+}
+
+// One launch on the context's stream (nnz > 0; the device arrays set by the caller): no allocation, no synchronisation.
+static int cov_launch(smm_ctx *c, int dim, const CovArgs &A)
+{
+    const int64_t waves = ((int64_t)A.nnz + CV_RUN - 1) / CV_RUN;
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)c->n_cu * 8));
+    if (dim == 1) LAUNCH(c, "smm_cov_eval", smm_cov_eval<1>, grid, 256, 0, A);
+    else if (dim == 2) LAUNCH(c, "smm_cov_eval", smm_cov_eval<2>, grid, 256, 0, A);
+    else LAUNCH(c, "smm_cov_eval", smm_cov_eval<3>, grid, 256, 0, A);
+    LAUNCH_CHECK();
+    return SMM_OK;
+}
+
+extern "C" int smm_cov_eval(smm_ctx *c, smm_csr *pattern, int flags, int model, int dim, const double *length, double variance, int wrt,
+                            int64_t na, const double *d_a, int64_t lda, int64_t nb, const double *d_b, int64_t ldb, double *d_val, double *d_dval)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CovArgs A;
+    CHK(cov_args(c, pattern, flags, model, dim, length, variance, wrt, na, d_a, lda, nb, d_b, ldb, d_val, d_dval, "smm_cov_eval", &A));
+    const int64_t ab = span_bytes(na, dim, lda), bb = span_bytes(nb, dim, ldb), ob = pattern->nnz * (int64_t)sizeof(double);
+    for (const double *out : {(const double *)d_val, (const double *)d_dval})
+        if (out && (ranges_overlap(out, ob, d_a, ab) || ranges_overlap(out, ob, d_b, bb)))
+            return fail(SMM_ERR_INVALID, "smm_cov_eval: an output's device range overlaps the coordinates");
+    if (d_val && d_dval && ranges_overlap(d_val, ob, d_dval, ob)) return fail(SMM_ERR_INVALID, "smm_cov_eval: val and dval overlap");
+    if (pattern->nnz == 0) return SMM_OK;
+    A.a = d_a; A.lda = lda; A.b = d_b; A.ldb = ldb; A.val = d_val; A.dval = d_dval;
+    CHK(cov_launch(c, dim, A));
+    return take_plan_error(c, "smm_cov_eval");
+}
+
+// Same with host coordinates and outputs; b == a with ldb == lda (a square pattern) is uploaded once.
+extern "C" int smm_cov_eval_host(smm_ctx *c, smm_csr *pattern, int flags, int model, int dim, const double *length, double variance, int wrt,
+                                 int64_t na, const double *a, int64_t lda, int64_t nb, const double *b, int64_t ldb, double *val, double *dval)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    CovArgs A;
+    CHK(cov_args(c, pattern, flags, model, dim, length, variance, wrt, na, a, lda, nb, b, ldb, val, dval, "smm_cov_eval_host", &A));
+    const int64_t nnz = pattern->nnz;
+    if (nnz == 0) return SMM_OK;
+    const bool same = a == b && lda == ldb && na == nb;
+    PoolBuf<double> da(c), db(c), dv(c), dd(c);
+    CHK(da.alloc((size_t)na * dim));
+    if (!same) CHK(db.alloc((size_t)nb * dim));
+    if (val) CHK(dv.alloc((size_t)nnz));
+    if (dval) CHK(dd.alloc((size_t)nnz));
+    CHK(upload_rows(c, da, a, na, dim, lda));
+    if (!same) CHK(upload_rows(c, db, b, nb, dim, ldb));
+    A.a = da; A.lda = dim; A.b = same ? (const double *)da : (const double *)db; A.ldb = dim; A.val = dv; A.dval = dd;
+    CHK(cov_launch(c, dim, A));
+    CHK(take_plan_error(c, "smm_cov_eval_host"));
+    if (val) CHK(download(c, val, dv, (size_t)nnz * sizeof(double)));
+    if (dval) CHK(download(c, dval, dd, (size_t)nnz * sizeof(double)));
+    return SMM_OK;
 }
 
 // ------------------------------------------------------------------------------ CG on (H Q H^T + R) Z = D

@@ -9,7 +9,8 @@ import threading
 
 import numpy as np
 
-from ._lib import (SMM_EXACT, SMM_FULL_MATRIX, SMM_INTERP_CLAMP, SMM_INTERP_LINEAR, SMM_INTERP_NEAREST, SMM_INTERP_REJECT, SMM_INTERP_ZERO,
+from ._lib import (SMM_COV_EXPONENTIAL, SMM_COV_GAUSSIAN, SMM_COV_MATERN32, SMM_COV_MATERN52, SMM_COV_SCALE_BY_PATTERN, SMM_COV_SPHERICAL,
+                   SMM_COV_WRT_ALL, SMM_COV_WRT_NONE, SMM_EXACT, SMM_FULL_MATRIX, SMM_INTERP_CLAMP, SMM_INTERP_LINEAR, SMM_INTERP_NEAREST, SMM_INTERP_REJECT, SMM_INTERP_ZERO,
                    SMM_MIRROR, SMM_SCALE_BY_MASK, SMM_SYMMETRIC, SMM_TAPER_BOXCAR, SMM_TAPER_GASPARI_COHN, SMM_TRANSPOSE, SmmError, SmmLibrary,
                    check)
 
@@ -17,9 +18,11 @@ __all__ = ["Context", "DeviceCSR", "default_context", "SmmError",
            "SMM_SYMMETRIC", "SMM_FULL_MATRIX", "SMM_EXACT", "SMM_MIRROR", "SMM_TRANSPOSE", "SMM_SCALE_BY_MASK",
            "SMM_TAPER_BOXCAR", "SMM_TAPER_GASPARI_COHN", "TAPER_KINDS",
            "SMM_INTERP_LINEAR", "SMM_INTERP_NEAREST", "SMM_INTERP_REJECT", "SMM_INTERP_CLAMP", "SMM_INTERP_ZERO", "INTERP_METHODS",
-           "INTERP_OUTSIDE"]
+           "INTERP_OUTSIDE", "COV_MODELS"]
 
 TAPER_KINDS = {"boxcar": SMM_TAPER_BOXCAR, "gaspari_cohn": SMM_TAPER_GASPARI_COHN}
+COV_MODELS = {"spherical": SMM_COV_SPHERICAL, "exponential": SMM_COV_EXPONENTIAL, "gaussian": SMM_COV_GAUSSIAN,
+              "matern32": SMM_COV_MATERN32, "matern52": SMM_COV_MATERN52}
 INTERP_METHODS = {"linear": SMM_INTERP_LINEAR, "nearest": SMM_INTERP_NEAREST}
 INTERP_OUTSIDE = {"error": SMM_INTERP_REJECT, "clamp": SMM_INTERP_CLAMP, "zero": SMM_INTERP_ZERO}
 
@@ -595,6 +598,50 @@ class Context:
         check(self.lib, self.lib.smm_taper_build(self.handle, int(dim), kind, float(cutoff), int(na), ctypes.c_void_p(_dptr(d_a)), int(lda),
                                                  int(nb), ctypes.c_void_p(_dptr(d_b)), int(ldb), ctypes.byref(h)))
         return DeviceCSR(self, h, int(na), int(nb), int(self.lib.smm_csr_nnz(h)))
+
+    # ------------------------------------------------------------------ parametric covariance on a pattern
+    @staticmethod
+    def _cov_args(model, length, dim, variance, wrt, scale):
+        """(flags, model, dim, length, variance, wrt) as smm_cov_eval takes them.  length: a scalar (every coordinate) or dim
+        numbers; wrt: None, "length" (the common length) or a coordinate's index.  The library checks the values."""
+        length = np.ascontiguousarray(np.broadcast_to(np.asarray(length, dtype=np.float64), (dim,)))
+        wrt = SMM_COV_WRT_NONE if wrt is None else (SMM_COV_WRT_ALL if isinstance(wrt, str) and wrt == "length" else int(wrt))
+        return [SMM_COV_SCALE_BY_PATTERN if scale else 0, _named(model, COV_MODELS, "model"), int(dim), _ptr(length), float(variance), wrt], length
+
+    def cov_host(self, pattern, a, b, model, length, variance=1.0, wrt=None, scale=False, value=True):
+        """variance * c(h) at every stored entry (i, j) of pattern (a DeviceCSR, any legal CSR) from the numpy points a
+        (rows x dim, or rows on a line) and b (cols x dim; None means b = a), h the distance in coordinates divided by
+        `length`; with wrt also the derivative with respect to that length; times the entry's value with scale
+        (smm_cov_eval_host).  Returns (val, dval): float64 numpy arrays of nnz(pattern) in the pattern's stored order, None
+        for the one not asked for (value=False: the derivative alone)."""
+        a, dim = self._host_points(a, "a")
+        if b is None:
+            b = a
+        else:
+            b, dim_b = self._host_points(b, "b")
+            if dim_b != dim:
+                raise ValueError(f"a has {dim} coordinates per point, b has {dim_b}")
+        head, keep = self._cov_args(model, length, dim, variance, wrt, scale)
+        # (an output that is asked for has an address, also for a pattern without entries: NULL means "not asked for")
+        val = np.empty(max(pattern.nnz, 1), dtype=np.float64)[:pattern.nnz] if value else None
+        dval = np.empty(max(pattern.nnz, 1), dtype=np.float64)[:pattern.nnz] if wrt is not None else None
+        out = [ctypes.c_void_p(x.ctypes.data) if x is not None else ctypes.c_void_p(0) for x in (val, dval)]
+        check(self.lib, self.lib.smm_cov_eval_host(self.handle, pattern.handle, *head, a.shape[0], _ptr(a), dim, b.shape[0], _ptr(b), dim, *out))
+        del keep
+        return val, dval
+
+    def cov_into(self, pattern, d_a, lda, d_b, ldb, dim, model, length, variance, d_val, d_dval=None, wrt=None, scale=False):
+        """cov_host on device buffers: a (pattern.rows x dim, leading dimension lda) at d_a, b (pattern.cols x dim, leading
+        dimension ldb) at d_b -- the same buffer for the square case --, nnz(pattern) float64 written at d_val and / or
+        d_dval, None for an output not wanted (smm_cov_eval).  Ints (device addresses) or torch tensors; stream rules as
+        spmm_into."""
+        head, keep = self._cov_args(model, length, dim, variance, wrt, scale)
+        self._sync_all(d_a, d_b, d_val, d_dval)
+        check(self.lib, self.lib.smm_cov_eval(self.handle, pattern.handle, *head, pattern.rows, ctypes.c_void_p(_dptr(d_a)), int(lda),
+                                              pattern.cols, ctypes.c_void_p(_dptr(d_b)), int(ldb), ctypes.c_void_p(_dptr(d_val)),
+                                              ctypes.c_void_p(_dptr(d_dval))))
+        del keep
+        self.synchronize()
 
     # ------------------------------------------------------------------ observation operator from coordinates
     @staticmethod

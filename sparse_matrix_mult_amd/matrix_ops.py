@@ -17,7 +17,7 @@ import os
 import numpy as np
 from scipy.sparse import csr_matrix, isspmatrix_csr
 
-from .engine import INTERP_METHODS, INTERP_OUTSIDE, TAPER_KINDS, SolveInfo, default_context
+from .engine import COV_MODELS, INTERP_METHODS, INTERP_OUTSIDE, TAPER_KINDS, SolveInfo, default_context
 # the operand and plan cache (operand_cache.py): the entry points lease their operands through with_leases and take
 # their plans from plan_for; the public names below are re-exported as the same objects
 from .operand_cache import PinnedOperand, cache_stats, clear_cache, plan_for, set_operand_cache, with_leases  # noqa: F401
@@ -295,6 +295,122 @@ def localization_taper(coords, cutoff, coords_b=None, taper="gaspari_cohn", pin=
             return ctx.taper_into(da, lda, db, ldb, na, nb, dim, cutoff, taper)
     # (a taper stays a scipy CSR under set_result_device(True): to_device is never asked for)
     return _deliver_operand(ctx, build, (na, nb), pin, a_torch or b_torch, False)
+
+
+# ------------------------------------------------------------------ parametric covariance on a pattern
+def _cov_lengths(length, dim, what):
+    """(lengths float64[dim], scalar): `length` as one correlation length per coordinate, and whether it was given as one
+    number.  ValueError for anything the library would refuse."""
+    try:
+        arr = np.asarray(length, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: length must be a positive number, or one per coordinate") from None
+    scalar = arr.ndim == 0
+    if scalar:
+        arr = np.full(dim, float(arr))
+    elif arr.shape != (dim,):
+        raise ValueError(f"{what}: length must be a scalar or hold one number per coordinate ({dim}), got shape {arr.shape}")
+    if not np.all(np.isfinite(arr) & (arr > 0.0)):
+        raise ValueError(f"{what}: every length must be finite and positive, got {arr.tolist()}")
+    return np.ascontiguousarray(arr), scalar
+
+
+def covariance_on_pattern(pattern, coords, model, length, variance=1.0, coords_b=None, scale_by_pattern=False, derivative=None,
+                          pin=False):
+    """A parametric covariance evaluated at the stored positions of `pattern`, on the GPU: Q[i, j] = variance * c(h) with
+    h = |(coords[i] - coords_b[j]) / length|, and optionally dQ/dlength on the same positions -- the prior of a
+    likelihood search over variances and correlation lengths, and the dQ of its gradient's trace term.
+
+    pattern  : na x nb; scipy CSR, anything csr_matrix() accepts, or a PinnedOperand -- a taper from localization_taper,
+               Q's pattern, or H's for cross-covariances.  It is used as stored (rows may be unsorted and repeat columns)
+               and is never written, nor is anything cached for it.
+    coords   : na x dim (dim 1, 2 or 3) or 1-D; numpy (cast to float64) or a float64 CUDA tensor on the library's device
+               with unit column stride (a column slice of a wider tensor is used in place), as in localization_taper.
+    coords_b : the same kinds, nb x dim; None means coords itself.
+    model    : "spherical", "exponential", "gaussian", "matern32" or "matern52"; the formulas, operation by operation, are
+               in include/smm_hip.h.  c(0) = 1 in each; the spherical one is exactly 0 from h = 1 on.
+    length   : a positive number, or one per coordinate (anisotropy).
+    variance : finite; the value at distance 0.
+    scale_by_pattern : multiply every result by the pattern's stored value: with a Gaspari-Cohn taper L as the pattern this
+               is Q = L o C, compactly supported and still positive semidefinite, and dQ = L o dC.
+    derivative : None; "length" -- with respect to the common length, which needs a scalar `length` --; or a coordinate's
+               index t -- with respect to length[t].  The call then returns the pair (Q, dQ) from one pass.
+    pin      : False returns scipy CSR matrices (DeviceCSRResults under set_result_device(True)) with the pattern's
+               structure.  True returns PinnedOperands over the arrays the kernel wrote, by the path of
+               pin_operand(DeviceCSRResult): nothing is copied to the host.
+    A new length is a new call that writes new arrays; nothing is refreshed in place.  Coordinates are not screened: a NaN
+    gives NaN at its entries.  Argument errors are ValueError before any device call; a pattern without entries returns
+    without one.  Nothing is printed.
+    """
+    what = "covariance_on_pattern"
+    pattern = _as_csr(pattern)
+    if not isinstance(model, str) or model not in COV_MODELS:
+        raise ValueError(f"{what}: unknown model {model!r}, expected one of {sorted(COV_MODELS)}")
+
+    def points(x, name):
+        x, n, dim, is_torch = _points(x, what, name)
+        if dim < 1 or dim > 3:
+            raise ValueError(f"{what}: {name} has {dim} coordinates per point, expected 1, 2 or 3")
+        return x, n, dim, is_torch
+
+    a, na, dim, a_torch = points(coords, "coords")
+    if coords_b is None:
+        b, nb, b_torch = a, na, a_torch
+    else:
+        b, nb, dim_b, b_torch = points(coords_b, "coords_b")
+        if dim_b != dim:
+            raise ValueError(f"{what}: coords has {dim} coordinates per point, coords_b has {dim_b}")
+    shape = (int(pattern.shape[0]), int(pattern.shape[1]))
+    if (na, nb) != shape:
+        raise ValueError(f"{what}: the pattern is {shape[0]} x {shape[1]}, the points are {na} and {nb}")
+    lengths, scalar = _cov_lengths(length, dim, what)
+    try:
+        variance = float(variance)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: variance must be a finite number") from None
+    if not np.isfinite(variance):
+        raise ValueError(f"{what}: variance must be a finite number, got {variance}")
+    if derivative is None or (isinstance(derivative, str) and derivative == "length"):
+        if derivative is not None and not scalar:
+            raise ValueError(f'{what}: derivative="length" is with respect to one common length: pass a scalar length, '
+                             "or a coordinate's index")
+    elif isinstance(derivative, (int, np.integer)) and not isinstance(derivative, bool):
+        if not 0 <= derivative < dim:
+            raise ValueError(f"{what}: derivative {derivative} is not a coordinate of {dim}-dimensional points")
+        derivative = int(derivative)
+    else:
+        raise ValueError(f'{what}: derivative must be None, "length" or a coordinate\'s index, got {derivative!r}')
+    both = derivative is not None
+    if pattern.nnz == 0:
+        empty = [PinnedOperand._adopt(None, None, shape) if pin else _zero_result(shape) for _ in range(1 + both)]
+        return tuple(empty) if both else empty[0]
+    ctx = default_context()
+    args = dict(model=model, length=lengths, variance=variance, wrt=derivative, scale=scale_by_pattern)
+
+    def body(lp):
+        if not (a_torch or b_torch or _result_device or pin):
+            data = ctx.cov_host(lp.handle, a, None if b is a else b, **args)
+            return [_result_csr(*_mask_pattern(pattern), d, shape) for d in data if d is not None]
+        import torch
+        da, lda = _points_on_device(ctx, a, dim, a_torch, what, "coords")
+        db, ldb = (da, lda) if b is a else _points_on_device(ctx, b, dim, b_torch, what, "coords_b")
+
+        def call():
+            data = [torch.empty(lp.handle.nnz, dtype=torch.float64, device=da.device) for _ in range(1 + both)]
+            ctx.cov_into(lp.handle, da, lda, db, ldb, dim, d_val=data[0], d_dval=data[1] if both else None, **args)
+            indptr, indices = lp.handle.pattern_torch()
+            indptr = indptr.to(torch.int64)
+            # (each result owns its pattern tensors: a caller may sort or pin one of the pair and not the other)
+            return [DeviceCSRResult(indptr if i == 0 else indptr.clone(), indices if i == 0 else indices.clone(), d, shape)
+                    for i, d in enumerate(data)]
+
+        out = _on_device(ctx, call)
+        if pin:
+            return [_pin_device_result(r) for r in out]
+        return out if _result_device else [r.to_scipy() for r in out]
+
+    out = with_leases(ctx, (pattern,), body)
+    return tuple(out) if both else out[0]
 
 
 # ------------------------------------------------------------------ observation operator from coordinates
