@@ -487,6 +487,51 @@ int  smm_cov_eval(smm_ctx *ctx, smm_csr *pattern, int flags, int model, int dim,
 int  smm_cov_eval_host(smm_ctx *ctx, smm_csr *pattern, int flags, int model, int dim, const double *length, double variance, int wrt,
                        int64_t na, const double *a, int64_t lda, int64_t nb, const double *b, int64_t ldb, double *val, double *dval);
 
+/* ------------------------------------------------------------------ empirical variogram on a given pattern
+ * The look at the data that comes before a model and a first length are chosen: over the stored entries e = (i, j) of
+ * `pattern` (n x n; any legal CSR of this context: rows may be unsorted, repeat columns, be empty -- a taper from
+ * smm_taper_build is the usual one; this call searches nothing), binned by the distance of the points a_i and a_j, per bin
+ * the number of pairs, the sum of their distances and the sum of their squared increments of the values y.  a: n x dim,
+ * row-major float64, leading dimension lda >= dim, dim 1, 2 or 3; y: n x k, row-major float64, ldy >= k (k variables, or k
+ * realisations of one); 64-bit offsets.  edges: nb + 1 doubles in HOST memory, the bins [edges[b], edges[b+1]).  The three
+ * outputs are in HOST memory for both entries -- count: nb x int64, sum_h and sum_sq: nb doubles each -- and the call
+ * returns synchronised.  lag[b] = sum_h[b] / count[b] and gamma[b] = sum_sq[b] / (2 k count[b]) are the caller's divisions.
+ * The call writes neither the pattern operand nor anything cached for it.  Every product is rounded before its add; there
+ * is one mode, no SMM_EXACT flag, no other order and no float atomics.  For each stored entry e = (i, j), e its position in
+ * the pattern's stored order:
+ *   Distance    d2 = +0.0; for t = 0 .. dim-1: df = a[i,t] - a[j,t]; d2 = d2 + df * df; h = sqrt(d2) (IEEE square root): the
+ *               recipe of smm_taper_build, so an entry of a taper has h < cutoff exactly as the taper decided it.
+ *   Increment   s = +0.0; for c = 0 .. k-1: dv = y[i,c] - y[j,c]; s = s + dv * dv.  k = 0 gives +0.0.
+ *   Bin         the entry takes part iff edges[0] <= h < edges[nb] and, by default, j > i -- so each pair of a symmetric
+ *               pattern counts once and the diagonal never.  SMM_VG_ALL_ENTRIES (the only flag) drops the condition on j:
+ *               every stored entry takes part, the diagonal included.  Its bin is b = the number of q in 1 .. nb with
+ *               edges[q] <= h: comparisons only, so h == edges[b] lies in bin b and a NaN distance in no bin.  Values are
+ *               not screened: a NaN or an infinity in y reaches exactly sum_sq of the bins its pairs fall in, never count
+ *               or sum_h.
+ *   Slot        with T = SMM_VG_SLOTS and W = T / 64: run = e / SMM_VG_RUN, slot t = (run mod W) * 64 + (e mod 64) -- the
+ *               lane map of smm_cov_eval on a grid of exactly T lanes: waves take runs of SMM_VG_RUN consecutive entries
+ *               round robin.  For every bin b, slot (t, b) starts at +0.0 and adds h (for sum_h) and s (for sum_sq) of
+ *               its entries in ascending e.
+ *   Tree        for every bin: p[t] = p[t] + p[t + g] for every t that is a multiple of 2 g, for g = 1, 2, 4, ..., T / 2;
+ *               the result is p[0].  Adjacent pairs, as in smm_sddmm's default order (not the halving tree of the CG's
+ *               dot products): the steps inside a wave come first, and the result does not depend on the workgroup size.
+ *   count       exact integer counting.
+ * sum_h, sum_sq and count are bit-identical to that recipe carried out in IEEE double whatever the pattern's row
+ * structure, and two calls give the same bits.  Every term is >= 0, so each sum is within (ceil(nnz / T) + 17) * 2^-53
+ * relative of the exact sum of its rounded terms.  SMM_VG_SLOTS and SMM_VG_RUN are part of the contract.
+ * SMM_ERR_INVALID, before any launch or allocation: an unknown flag, dim outside 1..3, nb outside 1..SMM_VG_MAX_BINS, an edge
+ * that is not finite, edges[0] < 0, edges not strictly ascending, a pattern that is not square, k < 0, lda < dim, ldy < k,
+ * a NULL buffer that should hold data (edges, the three outputs; a with n > 0; y with n > 0 and k > 0).  nnz(pattern) == 0:
+ * no launch, counts 0 and sums +0.0.  An entry that its row's range does not contain, or a column outside [0, n)
+ * (reachable only through smm_csr_from_device), is skipped and reported as SMM_ERR_INTERNAL. */
+enum smm_vg_constants { SMM_VG_RUN = 256, SMM_VG_SLOTS = 65536, SMM_VG_MAX_BINS = 32 };
+enum smm_vg_flags { SMM_VG_ALL_ENTRIES = 64 };
+int  smm_variogram(smm_ctx *ctx, smm_csr *pattern, int flags, int dim, const double *d_a, int64_t lda, int64_t k, const double *d_y,
+                   int64_t ldy, int nb, const double *edges, int64_t *count, double *sum_h, double *sum_sq);
+/* Same with a and y in host memory (uploaded through pool temporaries). */
+int  smm_variogram_host(smm_ctx *ctx, smm_csr *pattern, int flags, int dim, const double *a, int64_t lda, int64_t k, const double *y,
+                        int64_t ldy, int nb, const double *edges, int64_t *count, double *sum_h, double *sum_sq);
+
 /* ------------------------------------------------------------------ observation operator from point coordinates
  * H (n x K): the matrix that interpolates a field on a rectilinear grid to n points, as a new operand owned by the caller
  * (smm_csr_destroy), as smm_taper_build returns one -- the H of smm_triple_apply, smm_innovation_solve and their _kron forms,

@@ -9,9 +9,11 @@ row-sharded multi-GPU driver (distributed.py) and the HIP sources (csrc/).
 from .matrix_ops import (DeviceCSRResult, PinnedOperand, clear_cache, pin_operand, set_exact, set_full_symmetric,
                          set_operand_cache, set_result_device, sparse_matrix_multiply, sparse_triple_product,
                          masked_matrix_multiply, sparse_dense_multiply, triple_product_apply, innovation_solve, innovation_logdet, sampled_dense_product,
-                         localization_taper, covariance_on_pattern, interpolation_operator, kronecker_product, KroneckerOperand)
+                         localization_taper, covariance_on_pattern, empirical_variogram, VariogramResult, interpolation_operator, kronecker_product,
+                         KroneckerOperand)
 
 __all__ = ['sparse_matrix_multiply', 'set_exact', 'set_full_symmetric', 'set_result_device', 'clear_cache', 'set_operand_cache',
            'pin_operand', 'PinnedOperand', 'DeviceCSRResult', 'sparse_triple_product', 'masked_matrix_multiply',
            'sparse_dense_multiply', 'triple_product_apply', 'innovation_solve', 'innovation_logdet', 'sampled_dense_product', 'localization_taper',
-           'covariance_on_pattern', 'interpolation_operator', 'kronecker_product', 'KroneckerOperand']
+           'covariance_on_pattern', 'empirical_variogram', 'VariogramResult', 'interpolation_operator', 'kronecker_product',
+           'KroneckerOperand']

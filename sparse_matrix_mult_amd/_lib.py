@@ -8,6 +8,7 @@ refuses to run without the HIP library: there is no CPU fallback in this package
 import ctypes
 import importlib.util
 import os
+import re
 import subprocess
 import sys
 import threading
@@ -37,6 +38,18 @@ SMM_INTERP_NEAREST = 1
 SMM_INTERP_REJECT = 0
 SMM_INTERP_CLAMP = 1
 SMM_INTERP_ZERO = 2
+
+
+def _header_constants(prefix):
+    """name -> value of the `NAME = integer` enumerators of include/smm_hip.h whose name starts with prefix: constants of a
+    contract that the header alone states (the tree of smm_variogram), read and never restated here."""
+    with open(os.path.join(os.path.dirname(_HERE), "include", "smm_hip.h")) as f:
+        return {name: int(value) for name, value in re.findall(r"\b(%s\w+) = (-?\d+)\b" % prefix, f.read())}
+
+
+_VG = _header_constants("SMM_VG_")
+SMM_VG_RUN, SMM_VG_SLOTS, SMM_VG_MAX_BINS = _VG["SMM_VG_RUN"], _VG["SMM_VG_SLOTS"], _VG["SMM_VG_MAX_BINS"]
+SMM_VG_ALL_ENTRIES = _VG["SMM_VG_ALL_ENTRIES"]
 SMM_ERR_INVALID = -2
 SMM_ERR_ALLOC = -3
 SMM_ERR_OVERFLOW = -5
@@ -51,6 +64,8 @@ _BLOCKS = [ctypes.c_int, _c_i64, _vp, _c_i64, _vp, _c_i64]                  # fl
 _SOLVE = _BLOCKS + [ctypes.c_double, _c_i64, _vp, _vp, _vp, _vp]            # tol, maxiter, the four per-column outputs
 # smm_cov_eval[_host] behind the context and the pattern: flags, model, dim, length, variance, wrt, na, a, lda, nb, b, ldb, val, dval
 _COV = [ctypes.c_int] * 3 + [_vp, ctypes.c_double, ctypes.c_int, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp]
+# smm_variogram[_host] behind the context and the pattern: flags, dim, a, lda, k, y, ldy, nb, edges, count, sum_h, sum_sq
+_VARIOGRAM = [ctypes.c_int] * 2 + [_vp, _c_i64, _c_i64, _vp, _c_i64, ctypes.c_int, _vp, _vp, _vp, _vp]
 
 # name -> (restype, argtypes); every v2 symbol declared in include/smm_hip.h
 V2_PROTOTYPES = {
@@ -135,6 +150,8 @@ V2_PROTOTYPES = {
                                             _pp]),
     "smm_cov_eval": (ctypes.c_int, [_vp, _vp] + _COV),
     "smm_cov_eval_host": (ctypes.c_int, [_vp, _vp] + _COV),
+    "smm_variogram": (ctypes.c_int, [_vp, _vp] + _VARIOGRAM),
+    "smm_variogram_host": (ctypes.c_int, [_vp, _vp] + _VARIOGRAM),
     "smm_interp_build": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, _c_i64, _vp, _c_i64, _pp]),
     "smm_interp_build_host": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, _c_i64, _vp, _c_i64, _pp]),
     "smm_innovation_solve": (ctypes.c_int, [_vp] * 4 + _SOLVE),

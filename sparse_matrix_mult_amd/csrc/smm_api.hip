@@ -16,6 +16,7 @@
 #include "smm_taper.hpp"
 #include "smm_interp.hpp"
 #include "smm_cov.hpp"
+#include "smm_variogram.hpp"
 #include "../../include/smm_hip.h"
 
 #include <sys/mman.h>
@@ -4407,6 +4408,103 @@ extern "C" int smm_cov_eval_host(smm_ctx *c, smm_csr *pattern, int flags, int mo
     if (val) CHK(download(c, val, dv, (size_t)nnz * sizeof(double)));
     if (dval) CHK(download(c, dval, dd, (size_t)nnz * sizeof(double)));
     return SMM_OK;
+}
+
+// ------------------------------------------------------------------------------ empirical variogram on a pattern
+// (kernels: smm_variogram.hpp; contract: include/smm_hip.h)
+
+// Everything smm_variogram[_host] refuse before any launch or allocation; on success A holds the pattern, the bins and the sizes.
+static int vg_args(smm_ctx *c, smm_csr *pat, int flags, int dim, const double *a, int64_t lda, int64_t k, const double *y, int64_t ldy,
+                   int nb, const double *edges, const int64_t *count, const double *sum_h, const double *sum_sq, const char *where, VgArgs *A)
+{
+    if (flags & ~SMM_VG_ALL_ENTRIES) return fail(SMM_ERR_INVALID, "%s: only SMM_VG_ALL_ENTRIES is a flag of this call", where);
+    if (!pat) return fail(SMM_ERR_INVALID, "%s: pattern is NULL", where);
+    if (pat->ctx != c) return fail(SMM_ERR_INVALID, "%s: pattern belongs to another context", where);
+    if (dim < 1 || dim > 3) return fail(SMM_ERR_INVALID, "%s: dim must be 1, 2 or 3, got %d", where, dim);
+    if (nb < 1 || nb > SMM_VG_MAX_BINS) return fail(SMM_ERR_INVALID, "%s: nb must be 1 .. %d, got %d", where, (int)SMM_VG_MAX_BINS, nb);
+    if (!edges || !count || !sum_h || !sum_sq) return fail(SMM_ERR_INVALID, "%s: edges, count, sum_h or sum_sq is NULL", where);
+    for (int q = 0; q <= nb; ++q)
+        if (!std::isfinite(edges[q])) return fail(SMM_ERR_INVALID, "%s: edges[%d] is not finite", where, q);
+    if (edges[0] < 0.0) return fail(SMM_ERR_INVALID, "%s: edges[0] must be >= 0, got %g", where, edges[0]);
+    for (int q = 1; q <= nb; ++q)
+        if (!(edges[q - 1] < edges[q]))
+            return fail(SMM_ERR_INVALID, "%s: edges must ascend strictly, got edges[%d] = %g, edges[%d] = %g", where, q - 1, edges[q - 1], q, edges[q]);
+    if (pat->rows != pat->cols)
+        return fail(SMM_ERR_INVALID, "%s: the pattern must be square, got %lld x %lld", where, (long long)pat->rows, (long long)pat->cols);
+    if (k < 0 || lda < dim || ldy < k)
+        return fail(SMM_ERR_INVALID, "%s: need k >= 0, lda >= dim, ldy >= k (dim %d, lda %lld, k %lld, ldy %lld)", where, dim, (long long)lda,
+                    (long long)k, (long long)ldy);
+    if (pat->rows > 0 && (!a || (k > 0 && !y))) return fail(SMM_ERR_INVALID, "%s: a or y is NULL", where);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(validate(c, pat));
+    *A = VgArgs{};
+    A->n = (int)pat->rows; A->nnz = (int)pat->nnz; A->nb = nb;
+    A->all = (flags & SMM_VG_ALL_ENTRIES) ? 1 : 0;
+    A->ptr = pat->ptr; A->idx = pat->idx;
+    A->k = k;
+    for (int q = 0; q <= VG_MAX_BINS; ++q) A->edges[q] = q <= nb ? edges[q] : HUGE_VAL;
+    A->err = c->d_err;
+    return SMM_OK;
+}
+
+// The two launches on the context's stream and the three small downloads (nnz > 0; A.a, A.y and their leading dimensions
+// set by the caller).  Pool blocks: the sums (results in front, then one partial per bin and workgroup), then the counts.
+static int vg_run(smm_ctx *c, int dim, VgArgs &A, int64_t *count, double *sum_h, double *sum_sq, const char *where)
+{
+    const size_t nb = (size_t)A.nb, per = nb * (size_t)VG_GROUPS;
+    PoolBuf<double> ds(c);
+    PoolBuf<int64_t> dc(c);
+    CHK(ds.alloc(2 * nb + 2 * per));
+    CHK(dc.alloc(nb + per));
+    double *out_h = ds, *out_s = ds + nb;
+    int64_t *out_c = dc;
+    A.part_h = ds + 2 * nb; A.part_s = A.part_h + per; A.part_c = dc + nb;
+    if (dim == 1) LAUNCH(c, "smm_variogram_bins", smm_variogram_bins<1>, VG_GROUPS, VG_BLOCK, 0, A);
+    else if (dim == 2) LAUNCH(c, "smm_variogram_bins", smm_variogram_bins<2>, VG_GROUPS, VG_BLOCK, 0, A);
+    else LAUNCH(c, "smm_variogram_bins", smm_variogram_bins<3>, VG_GROUPS, VG_BLOCK, 0, A);
+    LAUNCH_CHECK();
+    LAUNCH(c, "smm_variogram_finish", smm_variogram_finish, 1, 1024, 0, A.nb, (const double *)A.part_h, (const double *)A.part_s,
+           (const int64_t *)A.part_c, out_h, out_s, out_c);
+    LAUNCH_CHECK();
+    CHK(take_plan_error(c, where));
+    CHK(download(c, sum_h, out_h, nb * sizeof(double)));
+    CHK(download(c, sum_sq, out_s, nb * sizeof(double)));
+    return download(c, count, out_c, nb * sizeof(int64_t));
+}
+
+static void vg_zero(int nb, int64_t *count, double *sum_h, double *sum_sq)
+{
+    for (int b = 0; b < nb; ++b) { count[b] = 0; sum_h[b] = 0.0; sum_sq[b] = 0.0; }
+}
+
+extern "C" int smm_variogram(smm_ctx *c, smm_csr *pattern, int flags, int dim, const double *d_a, int64_t lda, int64_t k, const double *d_y,
+                             int64_t ldy, int nb, const double *edges, int64_t *count, double *sum_h, double *sum_sq)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    VgArgs A;
+    CHK(vg_args(c, pattern, flags, dim, d_a, lda, k, d_y, ldy, nb, edges, count, sum_h, sum_sq, "smm_variogram", &A));
+    if (pattern->nnz == 0) { vg_zero(nb, count, sum_h, sum_sq); return SMM_OK; }
+    A.a = d_a; A.lda = lda; A.y = d_y; A.ldy = ldy;
+    return vg_run(c, dim, A, count, sum_h, sum_sq, "smm_variogram");
+}
+
+extern "C" int smm_variogram_host(smm_ctx *c, smm_csr *pattern, int flags, int dim, const double *a, int64_t lda, int64_t k, const double *y,
+                                  int64_t ldy, int nb, const double *edges, int64_t *count, double *sum_h, double *sum_sq)
+{
+    if (!c) return fail(SMM_ERR_INVALID, "ctx is NULL");
+    CTX_LOCK(c);
+    VgArgs A;
+    CHK(vg_args(c, pattern, flags, dim, a, lda, k, y, ldy, nb, edges, count, sum_h, sum_sq, "smm_variogram_host", &A));
+    if (pattern->nnz == 0) { vg_zero(nb, count, sum_h, sum_sq); return SMM_OK; }
+    const int64_t n = pattern->rows;
+    PoolBuf<double> da(c), dy(c);
+    CHK(da.alloc((size_t)n * dim));
+    CHK(dy.alloc((size_t)std::max<int64_t>(n * k, 1)));
+    CHK(upload_rows(c, da, a, n, dim, lda));
+    CHK(upload_rows(c, dy, y, n, k, ldy));
+    A.a = da; A.lda = dim; A.y = dy; A.ldy = k;
+    return vg_run(c, dim, A, count, sum_h, sum_sq, "smm_variogram_host");
 }
 
 // ------------------------------------------------------------------------------ CG on (H Q H^T + R) Z = D

@@ -11,8 +11,8 @@ import numpy as np
 
 from ._lib import (SMM_COV_EXPONENTIAL, SMM_COV_GAUSSIAN, SMM_COV_MATERN32, SMM_COV_MATERN52, SMM_COV_SCALE_BY_PATTERN, SMM_COV_SPHERICAL,
                    SMM_COV_WRT_ALL, SMM_COV_WRT_NONE, SMM_EXACT, SMM_FULL_MATRIX, SMM_INTERP_CLAMP, SMM_INTERP_LINEAR, SMM_INTERP_NEAREST, SMM_INTERP_REJECT, SMM_INTERP_ZERO,
-                   SMM_MIRROR, SMM_SCALE_BY_MASK, SMM_SYMMETRIC, SMM_TAPER_BOXCAR, SMM_TAPER_GASPARI_COHN, SMM_TRANSPOSE, SmmError, SmmLibrary,
-                   check)
+                   SMM_MIRROR, SMM_SCALE_BY_MASK, SMM_SYMMETRIC, SMM_TAPER_BOXCAR, SMM_TAPER_GASPARI_COHN, SMM_TRANSPOSE, SMM_VG_ALL_ENTRIES,
+                   SmmError, SmmLibrary, check)
 
 __all__ = ["Context", "DeviceCSR", "default_context", "SmmError",
            "SMM_SYMMETRIC", "SMM_FULL_MATRIX", "SMM_EXACT", "SMM_MIRROR", "SMM_TRANSPOSE", "SMM_SCALE_BY_MASK",
@@ -642,6 +642,43 @@ class Context:
                                               ctypes.c_void_p(_dptr(d_dval))))
         del keep
         self.synchronize()
+
+    # ------------------------------------------------------------------ empirical variogram on a pattern
+    @staticmethod
+    def _variogram_bins(edges):
+        """(edges float64[nb + 1], nb, count int64, sum_h, sum_sq): the host arrays of smm_variogram.  The outputs have an
+        address whatever nb is: the library checks the number of bins and the edges' values."""
+        edges = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+        nb = int(edges.size) - 1
+        size = max(nb, 1)
+        return edges, nb, np.zeros(size, dtype=np.int64), np.zeros(size, dtype=np.float64), np.zeros(size, dtype=np.float64)
+
+    def variogram_host(self, pattern, a, y, edges, upper=True):
+        """Over the stored entries (i, j) of pattern (a square DeviceCSR, any legal CSR) -- those with j > i, or all of them
+        with upper=False --, binned by the distance h of the numpy points a[i] and a[j] (n x dim, or n on a line) into
+        [edges[b], edges[b+1]): the number of pairs, the sum of h and the sum over the columns of y (n x k, or n) of
+        (y[i] - y[j])^2, summed in the fixed order of include/smm_hip.h (smm_variogram_host).  Returns (count int64, sum_h,
+        sum_sq): numpy arrays of len(edges) - 1."""
+        a, dim = self._host_points(a, "a")
+        y, k = self._host_points(y, "y")
+        if y.shape[0] != a.shape[0]:
+            raise ValueError(f"a has {a.shape[0]} points, y has {y.shape[0]} rows")
+        edges, nb, count, sum_h, sum_sq = self._variogram_bins(edges)
+        check(self.lib, self.lib.smm_variogram_host(self.handle, pattern.handle, 0 if upper else SMM_VG_ALL_ENTRIES, dim, _ptr(a), dim, k,
+                                                    _ptr(y), k, nb, _ptr(edges), _ptr(count), _ptr(sum_h), _ptr(sum_sq)))
+        return count, sum_h, sum_sq                                # (nb >= 1 here: the library refused anything else)
+
+    def variogram_device(self, pattern, d_a, lda, dim, d_y, ldy, k, edges, upper=True):
+        """variogram_host on device buffers: a (pattern.rows x dim, leading dimension lda) at d_a and y (pattern.rows x k,
+        leading dimension ldy) at d_y (smm_variogram); the edges and the three results stay host arrays.  Ints (device
+        addresses) or torch tensors; torch's current stream is synchronised before the library reads, and the call returns
+        synchronised."""
+        edges, nb, count, sum_h, sum_sq = self._variogram_bins(edges)
+        self._sync_all(d_a, d_y)
+        check(self.lib, self.lib.smm_variogram(self.handle, pattern.handle, 0 if upper else SMM_VG_ALL_ENTRIES, int(dim),
+                                               ctypes.c_void_p(_dptr(d_a)), int(lda), int(k), ctypes.c_void_p(_dptr(d_y)), int(ldy), nb,
+                                               _ptr(edges), _ptr(count), _ptr(sum_h), _ptr(sum_sq)))
+        return count, sum_h, sum_sq                                # (nb >= 1 here: the library refused anything else)
 
     # ------------------------------------------------------------------ observation operator from coordinates
     @staticmethod

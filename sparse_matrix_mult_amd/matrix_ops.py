@@ -17,6 +17,7 @@ import os
 import numpy as np
 from scipy.sparse import csr_matrix, isspmatrix_csr
 
+from ._lib import SMM_VG_MAX_BINS
 from .engine import COV_MODELS, INTERP_METHODS, INTERP_OUTSIDE, TAPER_KINDS, SolveInfo, default_context
 # the operand and plan cache (operand_cache.py): the entry points lease their operands through with_leases and take
 # their plans from plan_for; the public names below are re-exported as the same objects
@@ -411,6 +412,95 @@ def covariance_on_pattern(pattern, coords, model, length, variance=1.0, coords_b
 
     out = with_leases(ctx, (pattern,), body)
     return tuple(out) if both else out[0]
+
+
+# ------------------------------------------------------------------ empirical variogram on a pattern
+class VariogramResult:
+    """What empirical_variogram returns, numpy arrays on the host: .edges (nb + 1), and per bin .count (int64, the pairs),
+    .sum_lag (the sum of their distances), .sum_sq (the sum of their squared increments, over all k columns of the values),
+    .lag = sum_lag / count and .gamma = sum_sq / (2 k count) -- both NaN in a bin without pairs."""
+    __slots__ = ("edges", "count", "sum_lag", "sum_sq", "lag", "gamma")
+
+    def __init__(self, edges, count, sum_lag, sum_sq, k):
+        self.edges, self.count, self.sum_lag, self.sum_sq = edges, count, sum_lag, sum_sq
+        pairs = np.where(count > 0, count, 1).astype(np.float64)
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            self.lag = np.where(count > 0, sum_lag / pairs, np.nan)
+            self.gamma = np.where(count > 0, sum_sq / (2.0 * k * pairs), np.nan) if k > 0 else np.full(count.shape, np.nan)
+
+    def __repr__(self):
+        return f"VariogramResult({self.count.size} bins, {int(self.count.sum())} pairs)"
+
+
+def _variogram_edges(bin_edges, what):
+    """The bin edges as float64[nb + 1]; ValueError for anything the library would refuse."""
+    try:
+        edges = np.array(bin_edges, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: bin_edges must be a sequence of numbers") from None
+    if edges.ndim != 1 or not 2 <= edges.size <= SMM_VG_MAX_BINS + 1:
+        raise ValueError(f"{what}: bin_edges must be 1-D with 2 to {SMM_VG_MAX_BINS + 1} entries (1 to {SMM_VG_MAX_BINS} bins), "
+                         f"got shape {edges.shape}")
+    if not np.all(np.isfinite(edges)):
+        raise ValueError(f"{what}: every bin edge must be finite, got {edges.tolist()}")
+    if edges[0] < 0.0:
+        raise ValueError(f"{what}: the first bin edge must be >= 0, got {edges[0]}")
+    if not np.all(edges[:-1] < edges[1:]):
+        raise ValueError(f"{what}: bin_edges must ascend strictly, got {edges.tolist()}")
+    return np.ascontiguousarray(edges)
+
+
+def empirical_variogram(pattern, coords, values, bin_edges, upper=True):
+    """The empirical variogram of `values` at the points `coords`, on the GPU: over the pairs (i, j) that `pattern` stores,
+    binned by their distance h into [bin_edges[b], bin_edges[b+1]), the number of pairs, the mean distance and
+    gamma = mean of (values[i] - values[j])^2 / 2 -- the look at the data that suggests a model and a first length for
+    covariance_on_pattern and the likelihood search.  Nothing is searched: the pairs are the pattern's entries, usually a
+    localization_taper of the same coordinates with the largest lag of interest as its cutoff.
+
+    pattern   : n x n; scipy CSR, anything csr_matrix() accepts, or a PinnedOperand.  It is used as stored (rows may be
+                unsorted and repeat columns: a repeated entry counts again) and is never written, nor is anything cached
+                for it.  Its values are not read.
+    coords    : n x dim (dim 1, 2 or 3) or 1-D; numpy (cast to float64) or a float64 CUDA tensor on the library's device with
+                unit column stride (a column slice of a wider tensor is used in place), as in localization_taper.
+    values    : n, or n x k (k variables, or k realisations of one: gamma averages over them); the same kinds.
+    bin_edges : 2 to 33 finite numbers, strictly ascending, the first >= 0.  A pair belongs to bin b iff
+                bin_edges[b] <= h < bin_edges[b+1]; pairs outside [bin_edges[0], bin_edges[-1]) are left out.
+    upper     : True counts the stored entries with j > i, so each pair of a symmetric pattern once and the diagonal never;
+                False counts every stored entry.
+    Returns a VariogramResult of numpy arrays.  The sums are taken in the fixed order written out in include/smm_hip.h: no
+    atomics, two calls give the same bits.  Values are not screened: a NaN makes gamma NaN in the bins its pairs fall in; a
+    NaN coordinate takes its pairs out of every bin.  Argument errors are ValueError before any device call; a pattern
+    without entries returns zero counts without one.  Nothing is printed.
+    """
+    what = "empirical_variogram"
+    pattern = _as_csr(pattern)
+    a, n, dim, a_torch = _points(coords, what, "coords")
+    if dim < 1 or dim > 3:
+        raise ValueError(f"{what}: coords has {dim} coordinates per point, expected 1, 2 or 3")
+    y, ny, k, y_torch = _points(values, what, "values")
+    shape = (int(pattern.shape[0]), int(pattern.shape[1]))
+    if shape[0] != shape[1]:
+        raise ValueError(f"{what}: the pattern must be square, got {shape[0]} x {shape[1]}")
+    if n != shape[0] or ny != n:
+        raise ValueError(f"{what}: the pattern is {shape[0]} x {shape[1]}, coords holds {n} points and values {ny} rows")
+    edges = _variogram_edges(bin_edges, what)
+    if not isinstance(upper, (bool, np.bool_)):
+        raise ValueError(f"{what}: upper must be True or False, got {upper!r}")
+    upper = bool(upper)
+    nb = edges.size - 1
+    if pattern.nnz == 0:
+        return VariogramResult(edges, np.zeros(nb, dtype=np.int64), np.zeros(nb), np.zeros(nb), k)
+    ctx = default_context()
+
+    def body(lp):
+        if not (a_torch or y_torch):
+            return ctx.variogram_host(lp.handle, a, y, edges, upper)
+        da, lda = _points_on_device(ctx, a, dim, a_torch, what, "coords")
+        dy, ldy = _points_on_device(ctx, y, k, y_torch, what, "values")
+        return _on_device(ctx, lambda: ctx.variogram_device(lp.handle, da, lda, dim, dy, ldy, k, edges, upper))
+
+    count, sum_h, sum_sq = with_leases(ctx, (pattern,), body)
+    return VariogramResult(edges, count, sum_h, sum_sq, k)
 
 
 # ------------------------------------------------------------------ observation operator from coordinates
